@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the MonoCon hot path on MI355X (contract in the task brief).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--no-cpu-baseline] [--dump-outputs DIR]
 
 BASELINE.json's metric is "images/sec (384x1280) fwd+bwd at 1/2/4/8 GPUs": one "step" is one FULL
 train step through the drop-in API (model.detector + solver) on a synthetic KITTI-shaped batch
@@ -91,7 +91,55 @@ def parse():
                          "that directory exists, else bench_full.json beside this file.  stdout carries ONE compact line")
     ap.add_argument("--no-extra-modes", action="store_true",
                     help="skip the fp32_emulated / mixed_precision legs (profiles/collect.sh: keeps the kernel trace on the headline path)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps of the headline leg, write what its LAST timed step computed as DIR/<name>.npy "
+                         "(float32, rank 0, %.0f MB at most): the ten losses and their sum, the ten prediction maps, the "
+                         "parameter gradients and the updated parameters + BN statistics (each whole, or a fixed seeded sample "
+                         "of it when larger).  The inputs are seeded, so two builds can be compared output for output"
+                         % (_dump_bytes_max() / 2 ** 20))
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (the number of timed steps)")
+    return args
+
+
+# --dump-outputs: elements kept of one output (a seeded sample of a larger one); whole prediction maps at B=32 are 255 MB,
+# the flat gradient and the model state 79 MB each
+DUMP_CAP = {"pred": 1 << 19, "grad": 1 << 21, "state": 1 << 21}
+
+
+def _dump_bytes_max():
+    from hipmonocon import netspec
+    return 4 * (len(netspec.LOSS_KEYS) + 1 + len(netspec.PRED_KEYS) * DUMP_CAP["pred"] + DUMP_CAP["grad"] + DUMP_CAP["state"])
+
+
+def _seeded_sample(flat, cap, seed):
+    """the whole 1-D tensor when it holds at most `cap` elements, else `cap` of them at sorted positions drawn without
+    replacement from a fixed seed (the same positions on every run of the same shape)"""
+    n = flat.numel()
+    if n <= cap:
+        return flat
+    idx = np.sort(np.random.default_rng(seed).choice(n, cap, replace=False))
+    return flat[torch.from_numpy(idx).to(flat.device)]
+
+
+def dump_outputs(out_dir, m, preds, loss, total):
+    """what one train step hands its caller: the losses (`_, loss = model(batch)`), the prediction maps, and after
+    backward() + optimizer.step() the gradients and the model state; float32 .npy files"""
+    from hipmonocon import netspec
+    arrays = {k: loss[k].detach() for k in netspec.LOSS_KEYS}
+    arrays["loss_total"] = total.detach()
+    for i, (k, _) in enumerate(netspec.PRED_KEYS):
+        arrays[k] = _seeded_sample(preds[k].detach().reshape(-1), DUMP_CAP["pred"], 1000 + i)
+    # dead parameters (no gradient) stay in the flat vector as zeros: its layout is the same in every build
+    grads = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1) for p in m.parameters()])
+    arrays["grad_sample"] = _seeded_sample(grads, DUMP_CAP["grad"], 2000)
+    state = torch.cat([v.detach().reshape(-1) for v in m.state_dict().values() if v.dtype == torch.float32])
+    arrays["state_sample"] = _seeded_sample(state, DUMP_CAP["state"], 3000)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+    return sorted(arrays)
 
 
 def _pick_cpu_threads():
@@ -457,28 +505,37 @@ def main():
     gen = torch.Generator(device="cuda").manual_seed(1234 + rank)
     eval_img = torch.randn((B, 3, H, W), generator=gen, device="cuda", dtype=torch.float32)
 
-    def step():
+    last = {}
+
+    def step(keep=False):
         opt.zero_grad()
-        _, loss = m(batch)
+        preds, loss = m(batch)
         total = sum(v for v in loss.values())
         total.backward()            # includes the gradient all-reduce when N > 1
         opt.step()                  # fused clip_grad_norm_(35) + AdamW
         sch.step()
+        if keep:                    # --dump-outputs: the outputs of the last timed step
+            last.update(preds=preds, loss=loss, total=total)
         return total
 
-    def train_leg(mode, steps, warmup, profile):
+    def train_leg(mode, steps, warmup, profile, dump=None):
         """W untimed + K timed full train steps in `mode`; barrier + synchronize on both sides, max over ranks"""
         m.train().set_precision(mode)
         for _ in range(max(warmup, 1)):           # the first step in a mode builds (and autotunes) its plan
             total = step()
         sync_all()
         t0 = time.perf_counter()
-        for _ in range(steps):
-            total = step()
+        for i in range(steps):
+            total = step(keep=dump is not None and i == steps - 1)
         sync_all()
         mine = time.perf_counter() - t0
         elapsed = max_over_ranks(mine)
         assert bool(torch.isfinite(total)), "non-finite loss in the timed region (%s)" % mode
+        if dump is not None:
+            if rank == 0:        # before anything below runs the model again
+                names = dump_outputs(dump, m, last["preds"], last["loss"], last["total"])
+                _phase("outputs of the last timed step: %d arrays in %s" % (len(names), dump))
+            last.clear()
         out = {"ms_per_step": elapsed / steps * 1e3, "images_per_sec": world * B * steps / elapsed}
         if dist_on:       # every rank's own clock + how long the last exchange kept its stream waiting
             eng_ = m._rt.engine
@@ -729,7 +786,7 @@ def main():
 
     # ---------------------------------------------------------------- the train step (headline)
     _phase("model + batch resident; headline mode %s: first step builds and autotunes the train plan" % headline_mode)
-    head = train_leg(headline_mode, args.steps, args.warmup, profile=True)
+    head = train_leg(headline_mode, args.steps, args.warmup, profile=True, dump=args.dump_outputs)
     _phase("timed region done: %.2f ms/step" % head["ms_per_step"])
     fwd_head = forward_leg(headline_mode, args.forward_steps) if args.forward_steps > 0 else None
 

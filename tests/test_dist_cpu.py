@@ -22,6 +22,13 @@ def _free_port():
     return p
 
 
+def _host_barrier():
+    """the ranks' closing barrier.  dist.barrier() first asks torch which accelerator the machine has, and that starts
+    the HIP runtime -- every rank would open the GPU of a GPU box; these ranks are host-only, so they meet in a
+    collective on a CPU tensor instead"""
+    dist.all_reduce(torch.zeros(1))
+
+
 def _worker(rank, world, port, out):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_RANK=str(rank))
@@ -33,7 +40,7 @@ def _worker(rank, world, port, out):
         fg.views[n].copy_(torch.from_numpy(synth.normalish(100 + rank, n, named[i][1].shape).astype(np.float32)))
     fg.allreduce_mean()
     out[rank] = {n: fg.views[n].clone() for n, _ in named}
-    dist.barrier()
+    _host_barrier()
     dist.destroy_process_group()
 
 
@@ -89,7 +96,7 @@ def _sync_worker(rank, world, port, out):
     ok_all = hdist.all_ranks_ok(rank != 1)               # rank 1 reports a bad batch: every rank must see False
     ok_none = hdist.all_ranks_ok(True)
     out[rank] = (before, hdist.state_checksum(m), n, seed, ok_all, ok_none, int(m[1].num_batches_tracked))
-    dist.barrier()
+    _host_barrier()
     dist.destroy_process_group()
 
 
@@ -210,7 +217,7 @@ def _world8_worker(rank, world, port, out):
     except RuntimeError as e:
         res["hard"] = str(e)[:40]
     out[rank] = res
-    dist.barrier()
+    _host_barrier()
     dist.destroy_process_group()
 
 
@@ -311,7 +318,7 @@ def _asym_worker(rank, world, port, out):
     except IndexError:
         res["labels"] = "IndexError"
     out[rank] = res
-    dist.barrier()
+    _host_barrier()
     dist.destroy_process_group()
 
 
