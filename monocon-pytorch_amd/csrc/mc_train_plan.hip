@@ -237,7 +237,7 @@ struct TB {   // train plan builder
         for (char c : ts->bwd_side) k += c != 0;
         return k - 1;
     }
-    // MONOCON_HIP_LAZY_Z (bit mask, default 15): which post-BatchNorm activations are never stored (TNode::la).  1: the
+    // MONOCON_HIP_LAZY_Z (bit mask, default 3): which post-BatchNorm activations are never stored (TNode::la).  1: the
     // BatchNorm + ReLU outputs without residual (stem, level0 / level1, BasicBlock conv1, Root, neck proj / node); 2: a
     // Tree's `project` branch (BatchNorm without ReLU, consumed as the residual of the block beside it); 0: every
     // activation is stored (rounds 1-5).  Outputs of a residual add are always stored.
