@@ -294,6 +294,19 @@ int mc_preprocess(mc_handle *h, const void *img_hwc, int dtype, int H, int W, co
 int mc_preprocess_augmented(mc_handle *h, const unsigned char *frames_hwc, const float *params, int B, int src_h, int src_w,
                             const double mean[3], const double std[3], int pad_h, int pad_w, float *out_bchw, void *stream);
 
+/* ---- KITTI result rows (utils/kitti_convert_utils.py convert_to_kitti_3d / convert_to_kitti_2d on the device) --------
+ * Inputs are mc_decode's outputs box2d (B,K,5), box3d (B,K,7), cls (B,K) int64, keep_thr (B,K) u8, the projection P2
+ * (B,3,4) float32 and img_hw_scale (B,4) float32 = ori_h, ori_w, inv_sx, inv_sy per image (inv_* = 1 / the resize factors
+ * of img_metas['scale_hw']); 1 <= K <= 1024.  One launch for the batch, all pointers on the device:
+ *   rows3d (B,K,14) = label, alpha, x1, y1, x2, y2, l, h, w, x, y, z, rot_y, score: the kept boxes whose projected 2D box
+ *     meets the image, in decode order, 2D box clipped to the image and scaled by inv_*; n3d (B) int32 rows per image;
+ *   rows2d (B,K,6) = label, x1, y1, x2, y2, score: the kept box2d rows grouped by class 0, 1, 2, each class in decode
+ *     order, scaled by inv_*; n2d (B) int32.
+ * Rows past n3d / n2d are left unwritten. */
+int mc_kitti_format(mc_handle *h, const float *box2d, const float *box3d, const int64_t *cls, const uint8_t *keep_thr,
+                    const float *P2, const float *img_hw_scale, int B, int K, float *rows3d, int *n3d, float *rows2d,
+                    int *n2d, void *stream);
+
 /* ---- KITTI AP evaluation (last row) -------------------------------------------------------------
  * Device part: pairwise overlaps of rotated boxes.  All pointers are device pointers; results are row-major (N, K).
  *

@@ -26,6 +26,7 @@ from torch.utils.data import Dataset
 from transforms import (Compose, DeferImage, DeferredImage, Normalize, Pad, PhotometricDistortion, RandomCrop3D, RandomHorizontalFlip, RandomShift,
                         ToTensor)
 from utils.data_classes import KITTICalibration, KITTIMultiObjects
+from utils.kitti_convert_utils import kitti_result_lines
 
 DEFAULT_FILTER_CONFIG = {'min_height': 25, 'min_depth': 2, 'max_depth': 65, 'max_truncation': 0.5, 'max_occlusion': 2}
 IMG_MEAN, IMG_STD = [123.675, 116.28, 103.53], [58.395, 57.12, 57.375]
@@ -212,11 +213,7 @@ class MonoConDataset(BaseKITTIMono3DDataset):
                 ids = np.asarray(r['sample_idx']).reshape(-1)
                 sid = int(ids[0]) if len(ids) else 0
                 with open(os.path.join(d, '%06d.txt' % sid), 'w') as f:
-                    for i in range(len(r['name'])):
-                        bb, dm, lc = r['bbox'][i], r['dimensions'][i], r['location'][i]
-                        f.write('%s -1 -1 %.4f %.4f %.4f %.4f %.4f %.4f %.4f %.4f %.4f %.4f %.4f %.4f %.4f\n'
-                                % (r['name'][i], r['alpha'][i], bb[0], bb[1], bb[2], bb[3], dm[1], dm[2], dm[0],
-                                   lc[0], lc[1], lc[2], r['rotation_y'][i], r['score'][i]))
+                    f.writelines(kitti_result_lines(r))
 
     def evaluate(self, kitti_format_results: Dict[str, Any], eval_classes: List[str] = ('Pedestrian', 'Cyclist', 'Car'),
                  eval_types: List[str] = ('bbox', 'bev', '3d'), verbose: bool = True, save_path: str = None) -> Dict[str, float]:

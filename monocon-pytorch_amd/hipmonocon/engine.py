@@ -249,7 +249,33 @@ class Engine:
                                     _ptr(box2d), _ptr(box3d), _ptr(keep), _ptr(kthr), _stream())
         _lib.check(self.h, rc, "mc_decode")
         return dict(scores=scores, flat_index=flat, cls=cls, box2d=box2d, box3d=box3d, keep=keep,
-                    box_mask=kthr.bool())
+                    box_mask=kthr.bool(), keep_thr=kthr)
+
+    def kitti_format(self, decoded, P2, img_hw_scale):
+        """KITTI result rows of a decoded batch in one launch (mc_kitti_format).  decoded: ``decode``'s dict; P2 (B,3,4) and
+        img_hw_scale (B,4) = ori_h, ori_w, inv_sx, inv_sy, CUDA fp32.  Returns rows3d (B,K,14), n3d (B) int32, rows2d (B,K,6),
+        n2d (B) int32 -- views of ONE device buffer, ``packed``, so that a single copy brings all four to the host."""
+        box2d, box3d = _need_cuda(decoded["box2d"], "box2d"), _need_cuda(decoded["box3d"], "box3d")
+        cls, kthr = _need_cuda(decoded["cls"], "cls"), _need_cuda(decoded["keep_thr"], "keep_thr")
+        _need_cuda(P2, "P2"); _need_cuda(img_hw_scale, "img_hw_scale")
+        B, K = int(box2d.shape[0]), int(box2d.shape[1])
+        if (tuple(box2d.shape) != (B, K, 5) or tuple(box3d.shape) != (B, K, 7) or tuple(cls.shape) != (B, K)
+                or tuple(kthr.shape) != (B, K) or tuple(P2.shape) != (B, 3, 4) or tuple(img_hw_scale.shape) != (B, 4)):
+            raise _lib.MonoconHipError("kitti_format: shapes box2d %s box3d %s cls %s keep_thr %s P2 %s img_hw_scale %s"
+                                       % tuple(tuple(t.shape) for t in (box2d, box3d, cls, kthr, P2, img_hw_scale)))
+        if (box2d.dtype, box3d.dtype, cls.dtype, kthr.dtype, P2.dtype, img_hw_scale.dtype) != (
+                torch.float32, torch.float32, torch.int64, torch.uint8, torch.float32, torch.float32):
+            raise _lib.MonoconHipError("kitti_format: dtypes must be float32 / int64 cls / uint8 keep_thr")
+        packed = torch.empty(B * K * 20 + 2 * B, dtype=torch.float32, device=box2d.device)
+        rows3d = packed[:B * K * 14].view(B, K, 14)
+        rows2d = packed[B * K * 14:B * K * 20].view(B, K, 6)
+        counts = packed[B * K * 20:].view(torch.int32)
+        n3d, n2d = counts[:B], counts[B:]
+        with torch.cuda.device(packed.device):
+            rc = self.lib.mc_kitti_format(self.h, _ptr(box2d), _ptr(box3d), _ptr(cls), _ptr(kthr), _ptr(P2), _ptr(img_hw_scale),
+                                          B, K, _ptr(rows3d), _ptr(n3d), _ptr(rows2d), _ptr(n2d), _stream())
+        _lib.check(self.h, rc, "mc_kitti_format")
+        return dict(rows3d=rows3d, n3d=n3d, rows2d=rows2d, n2d=n2d, packed=packed)
 
     # ------------------------------------------------------------------ targets / losses
     TARGET_SHAPES = (("center_heatmap_target", "map3", torch.float32), ("wh_target", 2, torch.float32),

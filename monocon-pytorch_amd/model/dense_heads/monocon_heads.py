@@ -141,7 +141,8 @@ class MonoConDenseHeads(nn.Module):
         P2 = np.stack([np.asarray(c.P2, dtype=np.float32).reshape(3, 4) for c in batched_calib])
         return torch.from_numpy(P2).to(device), torch.from_numpy(p2_inverse(P2)).to(device)
 
-    def _decode_dense(self, data_dict: Dict[str, Any], pred_dict: Dict[str, torch.Tensor], engine=None):
+    def _decode_dense(self, data_dict: Dict[str, Any], pred_dict: Dict[str, torch.Tensor], engine=None, calib_dev=None):
+        """mc_decode of the batch; calib_dev: the (P2, P2inv) device tensors if the caller has uploaded them already"""
         img_h, img_w = data_dict['img_metas']['pad_shape'][0]
         heat = pred_dict['center_heatmap_pred']
         k = int(self.local_maximum_kernel)
@@ -149,10 +150,12 @@ class MonoConDenseHeads(nn.Module):
             # the reference fails here too: max_pool2d(heat, k, 1, (k - 1) // 2) of an even k is one pixel smaller than
             # the heat map and `hmax == heat` does not broadcast (utils/tensor_ops.py:17-21)
             raise RuntimeError("local_maximum_kernel=%r: the peak filter needs an odd window" % self.local_maximum_kernel)
-        calib = data_dict['calib']
-        if not isinstance(calib, (list, tuple)):
-            calib = [calib] * heat.shape[0]
-        P2, P2inv = self._calib_tensors(calib, heat.device)
+        if calib_dev is None:
+            calib = data_dict['calib']
+            if not isinstance(calib, (list, tuple)):
+                calib = [calib] * heat.shape[0]
+            calib_dev = self._calib_tensors(calib, heat.device)
+        P2, P2inv = calib_dev
         eng = engine if engine is not None else self._engine()
         return eng.decode({k: v.contiguous() for k, v in pred_dict.items()}, P2, P2inv, (img_h, img_w),
                           self.topk, self.test_thres, local_maximum_kernel=k)

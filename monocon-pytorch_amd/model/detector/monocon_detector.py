@@ -68,6 +68,93 @@ class MonoConDetector(nn.Module):
         return self.head._get_eval_formats(data_dict, pred_dict, get_vis_format=get_vis_format,
                                            engine=self._rt.engine)
 
+    def detect(self, data_dict: Dict[str, Any], get_vis_format: bool = False):
+        """what ``batch_eval`` returns -- the KITTI annotation dicts {'img_bbox': [...], 'img_bbox2d': [...]} with
+        ``sample_idx``, or the visualiser's list (get_vis_format=True) -- with the per-image host tail moved to the device:
+        forward, mc_decode, mc_kitti_format (the KITTI rows of the whole batch in one launch), then ONE copy to page-locked
+        host memory and one wait for it.  The annotation dicts are built from the packed rows (utils/kitti_convert_utils.py
+        kitti_annos_from_rows); the visualiser's list from the decode's outputs (it wants every kept box, visible or not)."""
+        kitti, vis = self._detect(data_dict, want_kitti=not get_vis_format, want_vis=bool(get_vis_format))
+        return vis if get_vis_format else kitti
+
+    def detect_with_vis(self, data_dict: Dict[str, Any]):
+        """(annotation dicts, visualiser's list) of ``detect`` from one forward"""
+        return self._detect(data_dict, want_kitti=True, want_vis=True)
+
+    def _pinned(self, name: str, n: int, dtype) -> torch.Tensor:
+        """a page-locked host buffer of this detector, grown on demand (callers wait for the copies that use it)"""
+        pins = self.__dict__.setdefault('_pins', {})
+        buf = pins.get(name)
+        if buf is None or buf.numel() < n:
+            buf = pins[name] = torch.empty(n, dtype=dtype, pin_memory=True)
+        return buf[:n]
+
+    def _detect(self, data_dict: Dict[str, Any], want_kitti: bool, want_vis: bool):
+        if self.training:
+            raise Exception("Model is in training mode. Please use '.eval()' first.")
+        import numpy as np
+        from hipmonocon.engine import p2_inverse
+        from utils.kitti_convert_utils import img_hw_scale, kitti_annos_from_rows
+        img = self.finish_batch(data_dict)['img']
+        B, dev = int(img.shape[0]), img.device
+        metas = data_dict['img_metas']
+        calib = data_dict['calib'] if isinstance(data_dict['calib'], (list, tuple)) else [data_dict['calib']] * B
+        # P2, its inverse and the per-image (ori_h, ori_w, inv_sx, inv_sy) rows go up in one asynchronous copy, queued
+        # before the forward
+        P2 = np.stack([np.asarray(c.P2, dtype=np.float32).reshape(3, 4) for c in calib])
+        inp = np.concatenate([P2.reshape(-1), p2_inverse(P2).reshape(-1), img_hw_scale(metas, B).reshape(-1)])
+        host_in = self._pinned('in', inp.size, torch.float32)
+        host_in.numpy()[:] = inp
+        dev_in = host_in.to(dev, non_blocking=True)
+        P2_d, P2inv_d, hws_d = dev_in[:12 * B].view(B, 3, 4), dev_in[12 * B:28 * B].view(B, 4, 4), dev_in[28 * B:].view(B, 4)
+
+        eng = self._engine()
+        pred_dict = eng.forward_infer(img.contiguous())
+        R = self.head._decode_dense(data_dict, pred_dict, eng, calib_dev=(P2_d, P2inv_d))
+        K = int(R['box2d'].shape[1])
+        parts = []                                  # device tensors -> byte ranges of one page-locked buffer
+        if want_vis:
+            parts += [R['cls'], R['box2d'], R['box3d'], R['keep_thr']]
+        if want_kitti:
+            parts.insert(0, eng.kitti_format(R, P2_d, hws_d)['packed'])
+        nbytes = [t.numel() * t.element_size() for t in parts]
+        host = self._pinned('out', sum(nbytes), torch.uint8)
+        off = 0
+        for t, n in zip(parts, nbytes):
+            host[off:off + n].copy_(t.reshape(-1).view(torch.uint8), non_blocking=True)
+            off += n
+        done = torch.cuda.Event()
+        done.record()
+        done.synchronize()
+
+        hb, off = host.numpy(), 0
+        kitti = vis = None
+        if want_kitti:
+            f = hb[:nbytes[0]].view(np.float32)
+            counts = f[B * K * 20:].view(np.int32)
+            sample_idx = metas['sample_idx'] if 'sample_idx' in metas else metas.get('idx', list(range(B)))
+            kitti = kitti_annos_from_rows(f[:B * K * 14].reshape(B, K, 14), counts[:B], f[B * K * 14:B * K * 20].reshape(B, K, 6),
+                                          counts[B:], sample_idx)
+            off = nbytes[0]
+        if want_vis:
+            cls = hb[off:off + B * K * 8].view(np.int64).reshape(B, K)
+            off += B * K * 8
+            box2d = hb[off:off + B * K * 20].view(np.float32).reshape(B, K, 5)
+            off += B * K * 20
+            box3d = hb[off:off + B * K * 28].view(np.float32).reshape(B, K, 7)
+            off += B * K * 28
+            keep = hb[off:off + B * K].reshape(B, K).astype(bool)
+            nc = self.head.num_classes
+            vis = []
+            for i in range(B):
+                b2, b3, lab = box2d[i][keep[i]], box3d[i][keep[i]], cls[i][keep[i]]
+                per_class = ([b2[lab == c] for c in range(nc)] if len(b2) else
+                             [np.zeros((0, 5), dtype=np.float32) for _ in range(nc)])
+                vis.append({'img_bbox': dict(boxes_3d=torch.from_numpy(b3), scores_3d=torch.from_numpy(b2[:, -1].copy()),
+                                             labels_3d=torch.from_numpy(lab)),
+                            'img_bbox2d': per_class})
+        return kitti, vis
+
     def load_checkpoint(self, ckpt_file: str):
         # the reference pickles whole engine objects; torch >= 2.6 needs weights_only=False for those
         from utils.engine_utils import load_checkpoint_file

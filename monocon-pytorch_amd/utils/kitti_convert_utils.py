@@ -84,3 +84,54 @@ def convert_to_kitti_2d(results_2d: List[List[np.ndarray]], img_metas: Dict[str,
         anno['sample_idx'] = np.array([img_metas['sample_idx'][i]] * n, dtype=np.int64)
         out.append(anno)
     return out
+
+
+# ------------------------------------------------------------------------------ packed rows of mc_kitti_format
+def img_hw_scale(img_metas: Dict[str, Any], batch: int) -> np.ndarray:
+    """(B,4) float32 rows ori_h, ori_w, inv_sx, inv_sy: mc_kitti_format's view of the metas (the inverse resize factors of
+    _inv_scale, which like the conversion above takes the batch's first ``scale_hw``)"""
+    inv = _inv_scale(img_metas)
+    out = np.empty((batch, 4), np.float32)
+    for i in range(batch):
+        h, w = tuple(img_metas['ori_shape'][i])[:2]
+        out[i] = (h, w, inv[0], inv[1])
+    return out
+
+
+def kitti_annos_from_rows(rows3d: np.ndarray, n3d: np.ndarray, rows2d: np.ndarray, n2d: np.ndarray,
+                          sample_idx) -> Dict[str, List[Dict[str, Any]]]:
+    """host arrays of mc_kitti_format -> {'img_bbox': [...], 'img_bbox2d': [...]}, the annotation dicts convert_to_kitti_3d /
+    convert_to_kitti_2d build (same keys and dtypes); rows3d (B,K,14), rows2d (B,K,6), n3d / n2d (B,) rows per image"""
+    out3, out2 = [], []
+    for i in range(len(n3d)):
+        r, n = rows3d[i, :int(n3d[i])], int(n3d[i])
+        anno = _empty_anno()
+        if n:
+            anno = {'name': np.array([CLASSES[int(l)] for l in r[:, 0]]), 'truncated': np.zeros(n),
+                    'occluded': np.zeros(n, dtype=np.int64), 'alpha': r[:, 1].copy(), 'bbox': r[:, 2:6].astype(np.float64),
+                    'dimensions': r[:, 6:9].copy(), 'location': r[:, 9:12].copy(), 'rotation_y': r[:, 12].copy(),
+                    'score': r[:, 13].copy()}
+        anno['sample_idx'] = np.array([sample_idx[i]] * n, dtype=np.int64)
+        out3.append(anno)
+        r, n = rows2d[i, :int(n2d[i])], int(n2d[i])
+        anno = _empty_anno()
+        if n:
+            anno = {'name': np.array([CLASSES[int(l)] for l in r[:, 0]]), 'truncated': np.zeros(n),
+                    'occluded': np.zeros(n, dtype=np.int64), 'alpha': np.full(n, -10), 'bbox': r[:, 1:5].astype(np.float64),
+                    'dimensions': np.zeros((n, 3), np.float32), 'location': np.full((n, 3), -1000.0, np.float32),
+                    'rotation_y': np.zeros(n), 'score': r[:, 5].copy()}
+        anno['sample_idx'] = np.array([sample_idx[i]] * n, dtype=np.int64)
+        out2.append(anno)
+    return {'img_bbox': out3, 'img_bbox2d': out2}
+
+
+def kitti_result_lines(anno: Dict[str, Any]) -> List[str]:
+    """one annotation dict -> the lines of a KITTI label / submission file (type, truncation and occlusion -1, alpha, bbox,
+    dimensions h w l, location, rotation_y, score)"""
+    lines = []
+    for i in range(len(anno['name'])):
+        bb, dm, lc = anno['bbox'][i], anno['dimensions'][i], anno['location'][i]
+        lines.append('%s -1 -1 %.4f %.4f %.4f %.4f %.4f %.4f %.4f %.4f %.4f %.4f %.4f %.4f %.4f\n'
+                     % (anno['name'][i], anno['alpha'][i], bb[0], bb[1], bb[2], bb[3], dm[1], dm[2], dm[0],
+                        lc[0], lc[1], lc[2], anno['rotation_y'][i], anno['score'][i]))
+    return lines
