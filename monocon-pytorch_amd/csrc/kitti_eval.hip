@@ -15,8 +15,18 @@
 //
 // Arithmetic follows the reference kernel's float32 formulation step by step (corner rotation, the >= tests of
 // point-in-quadrilateral, the determinant form of the segment intersection, centroid-angle insertion sort, triangle
-// fan area accumulated in double); the fused-multiply-add contraction of either compiler is not reproducible, so parity
-// is to float32 round-off (tests/test_kitti_eval.py), not bit-exact.
+// fan area accumulated in double).  It is pinned to the reference's own code run at float32 and at float64
+// (tests/golden/make_rotate_iou_golden.py, tests/test_rotate_iou_reference.py): within 5e-5 (or 4x the reference's own
+// float32 error, where that is larger) on every pair where the reference's answer does not depend on round-off, and
+// finite wherever the reference is.
+//
+// Floating-point contraction is OFF for this whole file.  hipcc fuses a * b + c into one fma by default, which rounds
+// once where the reference rounds twice; in the vertex tests (point_in_quad's >=, edge_cross's strict >) that flips
+// decisions on nearly touching or nearly parallel edges, and the crossing point's determinant can reach 0 and give a
+// NaN vertex.  Measured on the golden's catalogue with contraction on (and cosf / sinf): 51 stable pairs off by up to
+// 0.67, a copy turned by pi non-finite where the reference gives 1.0, and a tail of BEV errors 2.8x the reference's own.
+// The sine and cosine of the heading are the correctly rounded float32 values (computed in double), as the golden's
+// float32 run takes them; numba's float32 cosf / sinf are within an ulp of these.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -26,18 +36,21 @@
 
 #include "mc_internal.h"
 
+#pragma clang fp contract(off)
+
 namespace mc {
 
 constexpr int RT = 64;          // tile edge (boxes and queries per workgroup)
 constexpr int RTHREADS = 256;
 constexpr int MAXV = 16;        // vertex slots: at most 8 corners inside the other box + 8 edge crossings.  (The reference's
                                 // buffer holds 8 points; nearly coincident boxes produce more and overrun it there --
-                                // undefined in the reference, computed properly here.)
+                                // undefined in the reference, computed properly here.  Measured on the golden's 11 700
+                                // pairs: at most 10 candidates, 12 pairs past 8, none near 16.)
 
 struct RBox { float cx, cy, dx, dy, ang; };
 
 __device__ __forceinline__ void rbox_corners(const RBox b, float *c /* [8] in LDS or registers */, int stride) {
-    const float a_cos = cosf(b.ang), a_sin = sinf(b.ang);
+    const float a_cos = (float)cos((double)b.ang), a_sin = (float)sin((double)b.ang);
     const float hx = b.dx / 2, hy = b.dy / 2;
     const float px[4] = {-hx, -hx, hx, hx};
     const float py[4] = {-hy, hy, hy, -hy};

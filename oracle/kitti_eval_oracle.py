@@ -14,10 +14,12 @@ engine/kitti_eval/eval.py under identity ``numba.jit`` decorators (numba is abse
 as the Python they are written in, no placeholder does any work -- meta_f4.json) and records what ITS functions return:
 image_box_overlap, clean_data, compute_statistics_jit (both passes), get_thresholds, d3_box_overlap_kernel, eval_class for
 the three metrics, get_mAP40, kitti_eval's dict.  tests/test_f4_reference_golden.py holds this file (and the product's
-native matching) to those goldens.  PARITY UNPINNED, still: ``rotate_iou`` below -- the reference's version is a float32
-numba.cuda kernel (rotate_iou.py:280-379) that cannot execute here; for the BEV / 3D goldens the reference's evaluator
-was handed THIS function's overlaps.  What holds it (tests/test_kitti_eval.py): closed-form answers (identical / disjoint
-/ axis-aligned / 45-degree boxes) and an independent float64 polygon-clipping implementation that shares no code with it.
+native matching) to those goldens; for their BEV / 3D metrics the reference's evaluator was handed THIS file's
+``rotate_iou``.  ``rotate_iou`` itself is PINNED as well: tests/golden/make_rotate_iou_golden.py executes the reference's
+float32 numba.cuda kernel (rotate_iou.py:280-379) under an emulated launch on a labelled catalogue of >10 000 box pairs,
+and tests/test_rotate_iou_reference.py holds this function to it (5e-5 on the pairs where the reference's answer does not
+depend on round-off).  Also holding it (tests/test_kitti_eval.py): closed-form answers and an independent float64
+polygon-clipping implementation that shares no code with it.
 
 Straight loops, numpy float32 scalars where the reference kernel computes in float32; meant for tens of boxes.
 """
@@ -93,7 +95,8 @@ def intersection_area(p, q):
             if hit is not None:
                 pts.append([hit[0], hit[1]])
     # (at most 8 corners + 8 crossings.  The reference's vertex buffer holds only 8 points: nearly coincident boxes, which
-    #  produce more, overrun it there -- undefined behaviour in the reference; all candidates are kept here.)
+    #  produce more -- up to 10 in tests/golden/rotate_iou_ref.npz -- overrun it there, undefined behaviour in the
+    #  reference; all candidates are kept here.)
     n = len(pts)
     if n == 0:
         return 0.0

@@ -17,14 +17,15 @@ and the script proves that no placeholder ever does any work:
     ``numba.prange`` is ``range`` (a sequential run of a parallel loop without cross-iteration dependences).  Any other
     attribute (``numba.float32``, ``cuda.local``, ``cuda.shared``, ``cuda.to_device`` ...) raises -- and is never reached:
     the ONE function of the evaluator that needs them, ``rotate_iou_gpu_eval`` (the numba.cuda kernel
-    ``rotate_iou_kernel_eval``, engine/kitti_eval/rotate_iou.py:280-379), is NOT executed.  For the BEV / 3D metrics the
+    ``rotate_iou_kernel_eval``, engine/kitti_eval/rotate_iou.py:280-379), is not executed HERE.  For the BEV / 3D metrics the
     reference's ``calculate_iou_partly`` is handed rotated overlaps by binding the name ``rotate_iou_gpu_eval`` in
     ``engine.kitti_eval.rotate_iou`` (where bev_box_overlap / d3_box_overlap look it up) to the oracle's float32 restatement (oracle/kitti_eval_oracle.py:rotate_iou).  So:
       - 2D metric: every number is the reference's (image_box_overlap, clean_data, compute_statistics_jit,
         fused_compute_statistics, get_thresholds, eval_class, get_mAP40, kitti_eval's dict and table);
       - BEV / 3D: everything DOWNSTREAM of the rotated-overlap matrix is the reference's (d3_box_overlap_kernel's height
-        overlap included); the float32 rotated-IoU kernel itself stays **parity unpinned** (closed forms + an independent
-        float64 clipper in tests/test_kitti_eval.py are what hold it).
+        overlap included).  The rotated-IoU kernel itself is pinned by its own generator, make_rotate_iou_golden.py, which
+        imports this file and EXECUTES rotate_iou.py under a numba shim (rotate_iou_ref.npz); these f4 goldens are kept
+        as they were made, with the oracle standing in.
     meta_f4.json records the placeholder list and the access log (which must be empty).
 
     PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_f4_golden.py
@@ -255,6 +256,12 @@ def eval_golden():
     save("f4_kitti_eval.npz", **out)
 
 
+ROTATED_IOU_GOLDEN = ("engine/kitti_eval/rotate_iou.py is executed by tests/golden/make_rotate_iou_golden.py (its numba.cuda "
+                      "kernel under an emulated launch, float32 and float64 storage): tests/golden/rotate_iou_ref.npz, "
+                      "meta_rotate_iou.json. The f4 BEV / 3D goldens here still come from the oracle stand-in below; the "
+                      "reference's own end-to-end kitti_eval is in rotate_iou_ref.npz (e2e.*)")
+
+
 def RE_min_overlaps(classes):
     """the overlap table kitti_eval builds (engine/kitti_eval/eval.py:684-700), cut to the classes -- rebuilt from the values
     the reference prints in its own table header ('AP40@0.70, 0.70, 0.70' ...), and cross-checked against kitti_eval's
@@ -272,13 +279,13 @@ if __name__ == "__main__":
     assert not PLACEHOLDER_LOG, PLACEHOLDER_LOG
     meta = {"torch": torch.__version__, "numpy": np.__version__, "placeholders": PLACEHOLDERS,
             "placeholder_attribute_accesses": PLACEHOLDER_LOG,
-            "not_executed": ["engine/kitti_eval/rotate_iou.py:rotate_iou_gpu_eval and every numba.cuda function it launches "
-                             "(rotated BEV overlap kernel, float32): parity unpinned"],
+            "not_executed": [],
             "stand_in": {"engine.kitti_eval.eval.rotate_iou_gpu_eval": "oracle.kitti_eval_oracle.rotate_iou (BEV / 3D metrics only)",
                          "MonoConDataset.load_image": "PIL decode to RGB instead of cv2.imread + cv2.cvtColor"},
             "reference_modules_run": [RT.__file__, sys.modules["transforms.default_transforms"].__file__,
                                       sys.modules["dataset.monocon_dataset"].__file__, sys.modules["dataset.base_dataset"].__file__,
-                                      RE.__file__]}
+                                      RE.__file__],
+            "rotated_iou": ROTATED_IOU_GOLDEN}
     with open(os.path.join(HERE, "meta_f4.json"), "w") as f:
         json.dump(meta, f, indent=1)
     print("placeholder accesses:", PLACEHOLDER_LOG)

@@ -2,10 +2,11 @@
 behind the C-ABI -- against oracle/kitti_eval_oracle.py.
 
 The oracle's host logic (ignore rules, matching, recall sampling, AP) is pinned to the reference's own functions in
-tests/test_f4_reference_golden.py (round 6).  Its rotated-overlap arithmetic stays PARITY UNPINNED (a float32 numba.cuda
-kernel upstream, not executable here) and is held by what this file does: closed-form answers and an independent float64
-polygon-clipping implementation (``clip_area`` below: Sutherland-Hodgman, shares nothing with the vertex-collection /
-angle-sort formulation)."""
+tests/test_f4_reference_golden.py (round 6).  Its rotated-overlap arithmetic, and the HIP kernels', are pinned to the
+reference's own float32 numba.cuda kernel, executed by tests/golden/make_rotate_iou_golden.py, in
+tests/test_rotate_iou_reference.py.  This file adds what does not depend on the reference: closed-form answers and an
+independent float64 polygon-clipping implementation (``clip_area`` below: Sutherland-Hodgman, shares nothing with the
+vertex-collection / angle-sort formulation)."""
 import math
 import os
 
