@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """Benchmark of the MonoCon hot path on MI355X (contract in the task brief).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--no-cpu-baseline] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full [--no-cpu-baseline] ...]
+
+A plain run measures the headline alone: it sets up, runs W untimed and K timed train steps, writes the outputs of the
+last timed step when --dump-outputs is given, and prints the result line.  Everything else below (the roofline, the
+other precision modes, the eval forward, the loops around the step, decode, the evaluator's overlaps, the CPU baseline,
+the input-feed capacity) runs only with --full, after the same headline measurement.
 
 BASELINE.json's metric is "images/sec (384x1280) fwd+bwd at 1/2/4/8 GPUs": one "step" is one FULL
 train step through the drop-in API (model.detector + solver) on a synthetic KITTI-shaped batch
@@ -30,9 +35,9 @@ handle's own RCCL communicator, launched from inside mc_backward as the backward
 (csrc/mc_comm.hip) -- timing is barrier + synchronize bracketed and the MAX over ranks is reported;
 `multi_gpu` carries every rank's own step time and the exposed part of the exchange.
 
-Rank 0 prints ONE JSON line: the throughput, `roofline` of the dominant kernel family of the step
-(forward convolutions + data gradients, timed live with HIP events around every launch on the
-launch stream), `native_fp32`, `forward_only` (BASELINE configs[1]), `mixed_precision`,
+Rank 0 prints ONE JSON line: the throughput and, with --full, `roofline` of the dominant kernel family
+of the step (forward convolutions + data gradients, timed live with HIP events around every launch on
+the launch stream), `native_fp32`, `forward_only` (BASELINE configs[1]), `mixed_precision`,
 `decode_only` (configs[4]: B=64, top-k 100) and `cpu_baseline` (the oracle's CPU restatement timed
 on the host cores: train step B=2 plus the eval-forward and decode legs of SURVEY 8d).
 """
@@ -65,6 +70,11 @@ def parse():
     ap.add_argument("--batch", type=int, default=32, help="images per GPU per step")
     ap.add_argument("--height", type=int, default=384)
     ap.add_argument("--width", type=int, default=1280)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline measurement, also run every other leg: roofline, the other precision modes, eval "
+                         "forward, realistic loop, engine feeds, decode, evaluator overlaps, CPU baseline, input feed.  "
+                         "--no-cpu-baseline, --forward-steps, --cpu-seconds, --feed-steps, --feed-workers, --realistic-steps "
+                         "and --no-extra-modes shape such a run only")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--forward-steps", type=int, default=10,
                     help="also time this many eval forwards (BASELINE configs[1]); 0 = skip")
@@ -364,20 +374,21 @@ def compact_line(out, full_path):
                                % (out["config"]["global_batch"] // max(out["n_gpus"], 1), out["config"]["precision_mode"]),
                    "global_batch": out["config"]["global_batch"], "parallelism": out["config"]["parallelism"],
                    "precision_mode": out["config"]["precision_mode"]}
-    r = out.get("roofline") or {}
-    c["roofline"] = {"bound": r.get("bound"), "kernel": "mc::conv_bf16_kernel" if "bf16" in str(r.get("kernel")) else str(r.get("kernel"))[:40],
-                     "achieved": r.get("achieved"), "peak": r.get("peak"), "unit": "TFLOP/s", "frac": r.get("frac"),
-                     "traffic": r.get("traffic"), "traffic_unit": "MB/launch (PMC)",
-                     "alg_mb_per_launch": r.get("algorithmic_mb_per_launch"), "avg_launch_ms": r.get("avg_launch_ms"),
-                     "mfma_per_mac": 3 if out["config"]["precision_mode"] == "f16x2" else (6 if out["config"]["precision_mode"] == "bf16x3" else 1),
-                     "alg_tflops_fp32eq": r.get("algorithmic_tflops_fp32_equivalent"),
-                     "mfma_busy": _num(r, "pmc", "mfma_busy"), "clock_ghz": _num(r, "pmc", "clock_ghz"),
-                     "conv_ms": r.get("conv_ms_per_step"), "wgrad_ms": _num(r, "wgrad", "ms_per_step"), "wgrad_frac": _num(r, "wgrad", "frac", nd=4),
-                     "other_ms": r.get("other_ms_per_step")}
-    # the WHOLE step against the matrix pipe: (conv + data-gradient + weight-gradient FLOPs) x MFMAs per MAC / step time / peak
-    # (`frac` above is the conv family timed alone; the buckets overlap in the step)
-    if r.get("whole_step_tflops_fp32_equivalent") and r.get("peak"):
-        c["roofline"]["whole_step_frac"] = round(r["whole_step_tflops_fp32_equivalent"] * c["roofline"]["mfma_per_mac"] / r["peak"], 4)
+    r = out.get("roofline")
+    if r:      # --full: the conv family timed live in the headline mode
+        c["roofline"] = {"bound": r.get("bound"), "kernel": "mc::conv_bf16_kernel" if "bf16" in str(r.get("kernel")) else str(r.get("kernel"))[:40],
+                         "achieved": r.get("achieved"), "peak": r.get("peak"), "unit": "TFLOP/s", "frac": r.get("frac"),
+                         "traffic": r.get("traffic"), "traffic_unit": "MB/launch (PMC)",
+                         "alg_mb_per_launch": r.get("algorithmic_mb_per_launch"), "avg_launch_ms": r.get("avg_launch_ms"),
+                         "mfma_per_mac": 3 if out["config"]["precision_mode"] == "f16x2" else (6 if out["config"]["precision_mode"] == "bf16x3" else 1),
+                         "alg_tflops_fp32eq": r.get("algorithmic_tflops_fp32_equivalent"),
+                         "mfma_busy": _num(r, "pmc", "mfma_busy"), "clock_ghz": _num(r, "pmc", "clock_ghz"),
+                         "conv_ms": r.get("conv_ms_per_step"), "wgrad_ms": _num(r, "wgrad", "ms_per_step"), "wgrad_frac": _num(r, "wgrad", "frac", nd=4),
+                         "other_ms": r.get("other_ms_per_step")}
+        # the WHOLE step against the matrix pipe: (conv + data-gradient + weight-gradient FLOPs) x MFMAs per MAC / step time / peak
+        # (`frac` above is the conv family timed alone; the buckets overlap in the step)
+        if r.get("whole_step_tflops_fp32_equivalent") and r.get("peak"):
+            c["roofline"]["whole_step_frac"] = round(r["whole_step_tflops_fp32_equivalent"] * c["roofline"]["mfma_per_mac"] / r["peak"], 4)
     c["img_s_per_gpu"] = round(out["value"] / max(out.get("n_gpus", 1), 1), 2) if isinstance(out.get("value"), (int, float)) else None
     if out.get("scaling_vs_n1") is not None:
         c["scaling_vs_n1"] = out["scaling_vs_n1"]
@@ -547,9 +558,10 @@ def main():
             out["per_rank_exposed_allreduce_ms"] = [round(float(x[1]), 3) for x in allt]
             out["comm"] = eng_.comm_info() if eng_.comm_world else {"path": "torch.distributed all_reduce after backward",
                                                                      "fallback_reason": getattr(eng_, "comm_fallback_reason", None)}
+        if rank == 0:
+            out["workspace_gb"] = m._rt.engine.workspace_bytes() / 1e9
         if profile and rank == 0:
             out["profile"] = m._rt.engine.profile_train(iters=2)   # HIP events around every launch on the launch stream
-            out["workspace_gb"] = m._rt.engine.workspace_bytes() / 1e9
         return out
 
     def realistic_leg(mode, steps):
@@ -759,6 +771,7 @@ def main():
                       "step_gflop_per_image": round((conv["flops"] + wg["flops"]) / B / 1e9, 1),
                       "whole_step_tflops_fp32_equivalent": round((conv["flops"] + wg["flops"]) / (leg["ms_per_step"] * 1e-3) / 1e12, 2)})
             out["roofline"] = r
+        if "workspace_gb" in leg:
             out["workspace_gb"] = round(leg["workspace_gb"], 2)
         return out
 
@@ -786,23 +799,24 @@ def main():
 
     # ---------------------------------------------------------------- the train step (headline)
     _phase("model + batch resident; headline mode %s: first step builds and autotunes the train plan" % headline_mode)
-    head = train_leg(headline_mode, args.steps, args.warmup, profile=True, dump=args.dump_outputs)
+    full = args.full            # every leg below the headline's timed steps runs only with --full
+    head = train_leg(headline_mode, args.steps, args.warmup, profile=full, dump=args.dump_outputs)
     _phase("timed region done: %.2f ms/step" % head["ms_per_step"])
-    fwd_head = forward_leg(headline_mode, args.forward_steps) if args.forward_steps > 0 else None
+    fwd_head = forward_leg(headline_mode, args.forward_steps) if full and args.forward_steps > 0 else None
 
     extra = {}
-    if args.forward_steps > 0 and not args.no_extra_modes:
+    if full and args.forward_steps > 0 and not args.no_extra_modes:
         for other in [o for o in ("fp32", "bf16x3", "f16x2") if o != headline_mode]:
             _phase("mode %s" % other)
             extra[other] = (train_leg(other, args.steps, 2, profile=True), forward_leg(other, args.forward_steps))
         _phase("mode bf16")
         extra["bf16"] = (train_leg("bf16", args.steps, 2, profile=False), forward_leg("bf16", args.forward_steps))
     real = None
-    if args.realistic_steps > 0:
+    if full and args.realistic_steps > 0:
         _phase("realistic loop (fresh labels, H2D of uint8 frames on a second stream, loss.item() per step)")
         real = realistic_leg(headline_mode, args.realistic_steps)
     feed = kfeed = None
-    if args.feed_steps > 0 and world == 1:
+    if full and args.feed_steps > 0 and world == 1:
         _phase("engine feed (RingLoader workers -> pinned ring -> copy stream -> step)")
         try:
             feed = engine_feed_leg(headline_mode, args.feed_steps, args.feed_workers)
@@ -813,12 +827,13 @@ def main():
             kfeed = kitti_feed_leg(headline_mode, args.feed_steps, args.feed_workers)
         except Exception as e:      # noqa: BLE001
             kfeed = {"error": "%s: %s" % (type(e).__name__, e)}
-    m.set_precision(headline_mode)
-    eng = m.eval()._engine()
+    if full:
+        m.set_precision(headline_mode)
+        eng = m.eval()._engine()
 
     # ---------------------------------------------------------------- decode only (configs[4])
     dec = None
-    if args.forward_steps > 0 and rank == 0:
+    if full and args.forward_steps > 0 and rank == 0:
         _phase("decode")
         K, DB = 100, 64
         from hipmonocon.engine import p2_inverse
@@ -939,7 +954,7 @@ def main():
         if dec is not None:
             out["decode_only"] = dec
             out["kitti_eval_overlaps"] = evl
-        if not args.no_cpu_baseline:
+        if full and not args.no_cpu_baseline:
             _phase("CPU baseline (oracle: train step B=2, eval forward B=2 / B=32, decode B=64)")
             out["cpu_baseline"] = cpu_baseline(sd, H, W, args.cpu_seconds)
         if real is not None:

@@ -1,7 +1,7 @@
 #!/bin/bash
 # train / eval-forward numbers of bench.py at other per-GPU batch sizes
 for b in 1 8 16 64; do
-  python bench.py --batch $b --steps 5 --warmup 2 --forward-steps 10 --realistic-steps 0 --no-cpu-baseline --no-extra-modes > /tmp/sweep_$b.json 2> /tmp/sweep_$b.err
+  python bench.py --full --batch $b --steps 5 --warmup 2 --forward-steps 10 --realistic-steps 0 --no-cpu-baseline --no-extra-modes > /tmp/sweep_$b.json 2> /tmp/sweep_$b.err
   python - $b <<'PY'
 import json, sys
 b = sys.argv[1]

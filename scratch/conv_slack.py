@@ -1,5 +1,5 @@
 """per conv closure of the train step: time against max(matrix time at the power ceiling, HBM time): where is slack left?
-   usage (on the GPU box): MONOCON_HIP_PROFILE_DUMP=1 python bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-extra-modes 2> dump.txt; python scratch/conv_slack.py dump.txt"""
+   usage (on an MI355X): MONOCON_HIP_PROFILE_DUMP=1 python bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-extra-modes 2> dump.txt; python scratch/conv_slack.py dump.txt"""
 import sys, collections
 rows = []
 for l in open(sys.argv[1]):

@@ -55,7 +55,7 @@ def test_bench_cli_contract_without_a_gpu():
     import sys
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
-    for flag in ("--gpus", "--steps", "--warmup", "--batch", "--precision", "--no-cpu-baseline"):
+    for flag in ("--gpus", "--steps", "--warmup", "--batch", "--precision", "--full", "--no-cpu-baseline"):
         assert flag in r.stdout, flag
     src = open(os.path.join(REPO, "bench.py")).read()
     assert 'choices=("f16x2", "bf16x3", "fp32")' in src and '"--gpus", type=int, default=1' in src
@@ -84,6 +84,27 @@ def test_bench_compact_line_carries_every_baseline_config():
     assert set(line["modes"]) == {"fp32", "bf16x3", "bf16"} and line["modes"]["fp32"]["train_ms"] == full["native_fp32"]["train"]["ms_per_step"]
     assert line["decode_only"]["img_s"] == full["decode_only"]["images_per_sec"]
     assert all(not isinstance(v, str) or len(v) < 120 for v in line["roofline"].values())
+
+
+def test_bench_compact_line_of_a_plain_run():
+    """a run without --full reports the headline alone (its verbose report holds no roofline and no other leg): the line
+    keeps the contract keys and does not invent a roofline block of nulls"""
+    import importlib.util
+    import json
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(REPO, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    full = json.load(open(os.path.join(REPO, "profiles", "r3h_bench.json")))
+    plain = {k: full[k] for k in ("metric", "value", "unit", "n_gpus", "world_size", "collective_backend", "steps", "warmup",
+                                  "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config")}
+    plain.update(roofline=None, workspace_gb=24.85)
+    line = bench.compact_line(plain, None)
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better"):
+        assert line[k] == plain[k], k
+    assert line["dtype"] == "f32 (%s)" % full["config"]["precision_mode"] and line["config"]["global_batch"] == 32
+    for k in ("roofline", "forward_only", "modes", "decode_only", "cpu_baseline", "realistic_loop", "input_feed"):
+        assert k not in line, k
+    assert line["workspace_gb"] == 24.85 and line["full_report"] is None
 
 
 def test_committed_bench_reports_are_headline_runs():

@@ -415,7 +415,7 @@ def test_bench_multi_rank_path_end_to_end(tmp_path):
     import json
     env = dict(os.environ, MONOCON_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", PYTHONDONTWRITEBYTECODE="1")
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4",
-           "--height", "64", "--width", "128", "--forward-steps", "2", "--no-cpu-baseline", "--no-extra-modes",
+           "--height", "64", "--width", "128", "--full", "--forward-steps", "2", "--no-cpu-baseline", "--no-extra-modes",
            # (its verbose report must not land on the default gpurun_out/bench_full.json: round 4 copied a report overwritten
            #  by this test into profiles/ as the headline run's)
            "--full-json", os.path.join(str(tmp_path), "bench_full.json")]
@@ -429,6 +429,31 @@ def test_bench_multi_rank_path_end_to_end(tmp_path):
     assert d["value"] > 0 and d["ms_per_step"] > 0 and d["steps"] == 2
     assert abs(d["value"] - 8 / (d["ms_per_step"] * 1e-3)) <= 0.02 * d["value"]      # whole-job images / second
     assert d["roofline"]["bound"] == "mfma" and d["roofline"]["achieved"] > 0
+
+
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """`python bench.py` without --full times the headline train step and nothing else: one JSON line with the contract
+    keys and none of the --full legs, and --dump-outputs still writes the outputs of the last timed step"""
+    import json
+    env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
+    dump = os.path.join(str(tmp_path), "dump")
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "4",
+           "--height", "64", "--width", "128", "--dump-outputs", dump, "--full-json", os.path.join(str(tmp_path), "report.json")]
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+        assert k in d, k
+    assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["dtype"].startswith("f32 (")
+    assert abs(d["value"] - 4 / (d["ms_per_step"] * 1e-3)) <= 0.02 * d["value"]
+    for k in ("roofline", "forward_only", "modes", "realistic_loop", "engine_feed", "engine_feed_kitti", "input_feed",
+              "decode_only", "kitti_eval_overlaps", "cpu_baseline"):
+        assert k not in d, k
+    names = {f[:-4] for f in os.listdir(dump) if f.endswith(".npy")}
+    assert names == set(netspec.LOSS_KEYS) | {k for k, _ in netspec.PRED_KEYS} | {"loss_total", "grad_sample", "state_sample"}
+    assert all(np.isfinite(np.load(os.path.join(dump, n + ".npy"))).all() for n in names)
 
 
 # ------------------------------------------------------------------------------------- round 3: advisor findings
