@@ -65,6 +65,7 @@ constexpr int NUM_HEADS = 9;        // 8 regression/heat-map branches + dir_feat
 constexpr int HEAD_CH = 64;
 constexpr int NUM_AFFINE = 10;
 constexpr int NUM_OUT_ROWS = 65;    // 3+2+2+18+9+2+3+2+12+12
+constexpr int PRED_CH[10] = {3, 9, 2, 2, 2, 18, 3, 2, 12, 12};   // channels of the ten prediction maps (MC_PRED_* order)
 
 // per-head parameter pointers for the AttnBN attention path (eval mode)
 struct HeadAttnParams {

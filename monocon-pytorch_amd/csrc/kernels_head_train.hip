@@ -347,8 +347,7 @@ hipError_t launch_dpred_pack(const float *const dpred[10], int ld, int B, int HW
     DpredPackArgs a;
     a.ld = ld; a.B = B; a.HW = HW; a.out = out;
     const HeadRow *rows = head_rows();
-    static const int PC[10] = {3, 9, 2, 2, 2, 18, 3, 2, 12, 12};
-    for (int i = 0; i < 10; ++i) { a.dpred[i] = dpred[i]; a.pred_c[i] = PC[i]; }
+    for (int i = 0; i < 10; ++i) { a.dpred[i] = dpred[i]; a.pred_c[i] = PRED_CH[i]; }
     for (int r = 0; r < NUM_OUT_ROWS; ++r) { a.row_pred[r] = rows[r].pred; a.row_ch[r] = rows[r].ch; }
     hipLaunchKernelGGL(dpred_pack_kernel, dim3(B * ((HW + 63) / 64)), dim3(256), 0, st, a);
     return hipGetLastError();

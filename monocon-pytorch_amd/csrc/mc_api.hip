@@ -27,135 +27,194 @@
 
 std::string g_create_err;
 
-static const char *HEAD_NAMES[NUM_HEADS] = {"heatmap_head", "wh_head", "offset_head", "center2kpt_offset_head",
-                                            "kpt_heatmap_head", "kpt_heatmap_offset_head", "dim_head", "depth_head",
-                                            "dir_feat"};
-static const int PRED_CH[MC_NUM_PREDS] = {3, 9, 2, 2, 2, 18, 3, 2, 12, 12};
-
 // ------------------------------------------------------------------------------ allocation
-static int dev_alloc(mc_handle *h, float **p, size_t nfloats, std::vector<void *> &track, size_t &acct) {
-    void *q = nullptr;
-    const size_t bytes = (nfloats == 0 ? 4 : nfloats) * sizeof(float);
+float *PlanAlloc::alloc(size_t nfloats) {
+    const size_t bytes = (nfloats ? nfloats : empty_floats) * sizeof(float);
     if (h->dry_alloc) {                       // mc_query_workspace: count only
         h->dry_next += (bytes + 255) / 256 * 256;
-        acct += bytes;
-        *p = reinterpret_cast<float *>((uintptr_t)0x100000 + h->dry_next);
-        return 0;
+        m.bytes += bytes;
+        return reinterpret_cast<float *>((uintptr_t)0x100000 + h->dry_next);
     }
-    HIPCHK(h, hipMalloc(&q, bytes));
-    HIPCHK(h, hipMemset(q, 0, bytes));
-    track.push_back(q);
-    acct += bytes;
-    *p = static_cast<float *>(q);
-    return 0;
+    void *q = nullptr;
+    hipError_t e = hipMalloc(&q, bytes);
+    if (e == hipSuccess) {
+        m.bufs.push_back(q);
+        e = hipMemset(q, 0, bytes);
+    }
+    if (e != hipSuccess) {
+        ok = false;
+        fail(h, "plan: %zu bytes of device memory: %s", bytes, hipGetErrorString(e));
+        return nullptr;
+    }
+    m.bytes += bytes;
+    return static_cast<float *>(q);
+}
+
+unsigned *PlanAlloc::slot() {
+    if (h->prec != 3) return nullptr;
+    if (!m.amax_arena) m.amax_arena = reinterpret_cast<unsigned *>(alloc((size_t)amax_slots * AMAX_WORDS));
+    if (m.amax_used >= amax_slots) { ok = false; h->err = "plan: amax slot table overflow"; return nullptr; }
+    return m.amax_arena ? m.amax_arena + (size_t)(m.amax_used++) * AMAX_WORDS : nullptr;
+}
+
+void *mc_param(mc_handle *h, const std::string &name, int64_t numel, int dtype) {
+    auto it = h->bound.find(name);
+    if (it == h->bound.end()) { fail(h, "parameter not bound: %s", name.c_str()); return nullptr; }
+    const Bound &b = it->second;
+    if (b.dtype != dtype) {
+        fail(h, "parameter is not %s: %s", dtype == MC_I64 ? "int64" : "fp32", name.c_str());
+        return nullptr;
+    }
+    if (b.numel != numel) {
+        fail(h, "parameter has wrong size: %s (%lld elements bound, %lld expected)", name.c_str(), (long long)b.numel,
+             (long long)numel);
+        return nullptr;
+    }
+    return b.ptr;
+}
+
+// ------------------------------------------------------------------------------ network graph
+namespace {
+struct GraphBuilder {
+    NetGraph g;
+    std::map<int, int> pooled;   // node -> its 2x2 max-pool (a nested tree pools its input again)
+
+    int node(int C) {
+        g.node_c.push_back(C);
+        return (int)g.node_c.size() - 1;
+    }
+    int push(NetStep s, int C) {
+        s.out = s.dead ? -1 : node(C);
+        g.steps.push_back(std::move(s));
+        return g.steps.back().out;
+    }
+    int conv(const std::string &n, const std::string &bn, std::vector<int> srcs, int res, bool relu, int cout, int ks,
+             int stride, bool dead = false) {
+        NetStep s{STEP_CONV, n, bn, std::move(srcs)};
+        s.res = res; s.relu = relu; s.cout = cout; s.ks = ks; s.stride = stride; s.dead = dead;
+        return push(std::move(s), cout);
+    }
+    int pool(int x) {
+        auto it = pooled.find(x);
+        if (it != pooled.end()) return it->second;
+        return pooled[x] = push(NetStep{STEP_POOL, "", "", {x}}, g.node_c[x]);
+    }
+    int deconv(const std::string &n, int x) { return push(NetStep{STEP_DECONV, n, "", {x}}, g.node_c[x]); }
+
+    // reference model/backbone/dla.py:34-51
+    int block(const std::string &n, int x, int residual, int cout, int stride) {
+        const int y = conv(n + ".conv1", n + ".bn1", {x}, -1, true, cout, 3, stride);
+        return conv(n + ".conv2", n + ".bn2", {y}, residual, true, cout, 3, 1);
+    }
+    // reference model/backbone/dla.py:187-205
+    int tree(const std::string &n, int levels, int cout, int stride, bool level_root, int x, std::vector<int> children) {
+        const int cin = g.node_c[x];
+        const int bottom = stride > 1 ? pool(x) : x;
+        if (level_root) children.push_back(bottom);
+        if (levels == 1) {
+            const int residual = cin != cout ? conv(n + ".project.0", n + ".project.1", {bottom}, -1, false, cout, 1, 1) : bottom;
+            const int x1 = block(n + ".tree1", x, residual, cout, stride);
+            const int x2 = block(n + ".tree2", x1, x1, cout, 1);
+            std::vector<int> cat = {x2, x1};
+            cat.insert(cat.end(), children.begin(), children.end());
+            return conv(n + ".root.conv", n + ".root.bn", cat, -1, true, cout, 1, 1);
+        }
+        // the outer `project` of a two-level tree is dead: the nested tree recomputes its own residual (dla.py:193-194)
+        if (cin != cout) conv(n + ".project.0", n + ".project.1", {bottom}, -1, false, cout, 1, 1, /*dead=*/true);
+        const int x1 = tree(n + ".tree1", levels - 1, cout, stride, false, x, {});
+        children.push_back(x1);
+        return tree(n + ".tree2", levels - 1, cout, 1, false, x1, children);
+    }
+};
+}  // namespace
+
+static NetGraph build_net() {
+    GraphBuilder b;
+    int *lv = b.g.lv;
+    b.node(16);                               // node 0: the stem's output (reference dla.py:231-234)
+    lv[0] = b.conv("backbone.level0.0", "backbone.level0.1", {0}, -1, true, 16, 3, 1);
+    lv[1] = b.conv("backbone.level1.0", "backbone.level1.1", {lv[0]}, -1, true, 32, 3, 2);
+    lv[2] = b.tree("backbone.level2", 1, 64, 2, false, lv[1], {});
+    lv[3] = b.tree("backbone.level3", 2, 128, 2, true, lv[2], {});
+    lv[4] = b.tree("backbone.level4", 2, 256, 2, true, lv[3], {});
+    lv[5] = b.tree("backbone.level5", 1, 512, 2, true, lv[4], {});
+    b.g.n_backbone = (int)b.g.steps.size();
+    // DLAUp (reference dla_neck.py:94-106,136-143): layers = [l2, l3, l4, l5]
+    int layers[4] = {lv[2], lv[3], lv[4], lv[5]};
+    for (int i = 0; i < 3; ++i) {
+        const int j = 4 - i - 2;              // first level of this IDA
+        const int out = b.g.node_c[layers[j]];
+        const std::string pre = "neck.ida_" + std::to_string(i) + ".";
+        for (int t = 1; t < 4 - j; ++t) {
+            const std::string ts = std::to_string(t);
+            const int p = b.conv(pre + "proj_" + ts + ".conv", pre + "proj_" + ts + ".bn1", {layers[j + t]}, -1, true, out, 3, 1);
+            b.g.steps.back().elementwise_consumers = true;
+            const int u = b.deconv(pre + "up_" + ts, p);
+            layers[j + t] = b.conv(pre + "node_" + ts + ".conv", pre + "node_" + ts + ".bn1", {layers[j + t - 1], u}, -1, true,
+                                   out, 3, 1);
+        }
+    }
+    b.g.feat = layers[3];
+    // `feat` feeds the fused head conv and its weight gradient, the two longest launches of the train step (mc_train_plan.hip)
+    b.g.steps.back().never_lazy = true;
+    return b.g;
 }
 
 // ------------------------------------------------------------------------------ layer table
-static void add_conv(mc_handle *h, const std::string &conv, const std::string &bn, int cin, int cout, int ks,
-                     int stride) {
-    ConvLayer L;
-    L.conv = conv; L.bn = bn; L.cin = cin; L.cout = cout; L.ks = ks; L.stride = stride;
-    L.coutp = conv_coutp(cout);
-    h->convs[conv] = L;
-}
-static void add_block(mc_handle *h, const std::string &n, int cin, int cout, int stride) {
-    add_conv(h, n + ".conv1", n + ".bn1", cin, cout, 3, stride);
-    add_conv(h, n + ".conv2", n + ".bn2", cout, cout, 3, 1);
-}
-static void add_tree(mc_handle *h, const std::string &n, int levels, int cin, int cout, int stride, bool level_root,
-                     int root_dim) {
-    if (root_dim == 0) root_dim = 2 * cout;
-    if (level_root) root_dim += cin;
-    if (levels == 1) {
-        add_block(h, n + ".tree1", cin, cout, stride);
-        add_block(h, n + ".tree2", cout, cout, 1);
-        add_conv(h, n + ".root.conv", n + ".root.bn", root_dim, cout, 1, 1);
-    } else {
-        add_tree(h, n + ".tree1", levels - 1, cin, cout, stride, false, 0);
-        add_tree(h, n + ".tree2", levels - 1, cout, cout, 1, false, root_dim + cout);
-    }
-    if (cin != cout) add_conv(h, n + ".project.0", n + ".project.1", cin, cout, 1, 1);
-}
-
 static int build_layers(mc_handle *h) {
     if (h->layers_built) return 0;
-    add_conv(h, "backbone.level0.0", "backbone.level0.1", 16, 16, 3, 1);
-    add_conv(h, "backbone.level1.0", "backbone.level1.1", 16, 32, 3, 2);
-    add_tree(h, "backbone.level2", 1, 32, 64, 2, false, 0);
-    add_tree(h, "backbone.level3", 2, 64, 128, 2, true, 0);
-    add_tree(h, "backbone.level4", 2, 128, 256, 2, true, 0);
-    add_tree(h, "backbone.level5", 1, 256, 512, 2, true, 0);
-    int neck_in[4] = {64, 128, 256, 512};
-    for (int i = 0; i < 3; ++i) {
-        const int j = 4 - i - 2;   // first level of this IDA
-        const int out = neck_in[j];
-        for (int t = 1; t < 4 - j; ++t) {
-            const std::string pre = "neck.ida_" + std::to_string(i) + ".";
-            const std::string ts = std::to_string(t);
-            add_conv(h, pre + "proj_" + ts + ".conv", pre + "proj_" + ts + ".bn1", neck_in[j + t], out, 3, 1);
-            add_conv(h, pre + "node_" + ts + ".conv", pre + "node_" + ts + ".bn1", 2 * out, out, 3, 1);
+    h->net = build_net();
+    for (const NetStep &s : h->net.steps) {
+        if (s.kind == STEP_CONV) {
+            ConvLayer L;
+            L.conv = s.name; L.bn = s.bn; L.cout = s.cout; L.ks = s.ks; L.stride = s.stride;
+            for (int x : s.srcs) L.cin += h->net.node_c[x];
+            L.coutp = conv_coutp(L.cout);
+            h->convs[s.name] = L;
+        } else if (s.kind == STEP_DECONV) {
             DeconvLayer D;
-            D.name = pre + "up_" + ts;
-            D.C = out;
+            D.name = s.name;
+            D.C = h->net.node_c[s.srcs[0]];
             h->deconvs[D.name] = D;
         }
-        for (int t = j + 1; t < 4; ++t) neck_in[t] = out;
     }
+    bool ok = true;
+    PlanAlloc mem{h, h->params, ok, 4, 0};
     for (auto &kv : h->convs) {
         ConvLayer &L = kv.second;
         const size_t wn = (size_t)L.ks * L.ks * L.cin * L.coutp;
-        if (dev_alloc(h, &L.wpk, wn, h->param_bufs, h->param_bytes)) return -1;
-        { float *q = nullptr; if (dev_alloc(h, &q, (3 * wn + 1) / 2, h->param_bufs, h->param_bytes)) return -1; L.wpk16 = q; }   // up to 3 bf16 pieces
-        if (dev_alloc(h, &L.scale, L.cout, h->param_bufs, h->param_bytes)) return -1;
-        if (dev_alloc(h, &L.shift, L.cout, h->param_bufs, h->param_bytes)) return -1;
+        L.wpk = mem.alloc(wn);
+        L.wpk16 = mem.alloc((3 * wn + 1) / 2);   // up to 3 bf16 pieces
+        L.scale = mem.alloc(L.cout);
+        L.shift = mem.alloc(L.cout);
     }
-    for (auto &kv : h->deconvs)
-        if (dev_alloc(h, &kv.second.wpk, (size_t)16 * kv.second.C, h->param_bufs, h->param_bytes)) return -1;
-    if (dev_alloc(h, &h->stem_w, 147 * 16, h->param_bufs, h->param_bytes)) return -1;
-    if (dev_alloc(h, &h->stem_scale, 16, h->param_bufs, h->param_bytes)) return -1;
-    if (dev_alloc(h, &h->stem_shift, 16, h->param_bufs, h->param_bytes)) return -1;
+    for (auto &kv : h->deconvs) kv.second.wpk = mem.alloc((size_t)16 * kv.second.C);
+    h->stem_w = mem.alloc(147 * 16);
+    h->stem_scale = mem.alloc(16);
+    h->stem_shift = mem.alloc(16);
     ConvLayer &H3 = h->head3;
     H3.conv = "head.*.0"; H3.ks = 3; H3.stride = 1; H3.cin = 64; H3.cout = NUM_HEADS * HEAD_CH;
     H3.cfg = CFG_128x64m | CFG_WRES;      // one head per 64-column tile (weight-resident kernel where the launch is eligible)
     H3.coutp = H3.cout;
-    if (dev_alloc(h, &H3.wpk, (size_t)9 * 64 * H3.coutp, h->param_bufs, h->param_bytes)) return -1;
-    { float *q = nullptr; if (dev_alloc(h, &q, (size_t)3 * 9 * 64 * H3.coutp / 2, h->param_bufs, h->param_bytes)) return -1; H3.wpk16 = q; }
-    if (dev_alloc(h, &h->head_bias, H3.cout, h->param_bufs, h->param_bytes)) return -1;
-    if (dev_alloc(h, &h->head_rm, H3.cout, h->param_bufs, h->param_bytes)) return -1;
-    if (dev_alloc(h, &h->att_scale, NUM_HEADS * NUM_AFFINE, h->param_bufs, h->param_bytes)) return -1;
-    if (dev_alloc(h, &h->att_shift, NUM_HEADS * NUM_AFFINE, h->param_bufs, h->param_bytes)) return -1;
-    if (dev_alloc(h, &h->head_w1, NUM_OUT_ROWS * HEAD_CH, h->param_bufs, h->param_bytes)) return -1;
-    if (dev_alloc(h, &h->head_w1t, NUM_OUT_ROWS * HEAD_CH, h->param_bufs, h->param_bytes)) return -1;
-    if (dev_alloc(h, &h->head_b1, NUM_OUT_ROWS, h->param_bufs, h->param_bytes)) return -1;
-    {   // precision mode 3: one max-|w| slot per conv layer + one for the fused head panel
-        float *q = nullptr;
-        h->w_amax_n = (int)h->convs.size() + 1;
-        if (dev_alloc(h, &q, (size_t)h->w_amax_n, h->param_bufs, h->param_bytes)) return -1;
-        h->w_amax_arena = reinterpret_cast<unsigned *>(q);
-        int i = 0;
-        for (auto &kv : h->convs) kv.second.w_amax = h->w_amax_arena + i++;
-        H3.w_amax = h->w_amax_arena + i;
-    }
+    H3.wpk = mem.alloc((size_t)9 * 64 * H3.coutp);
+    H3.wpk16 = mem.alloc((size_t)3 * 9 * 64 * H3.coutp / 2);
+    h->head_bias = mem.alloc(H3.cout);
+    h->head_rm = mem.alloc(H3.cout);
+    h->att_scale = mem.alloc(NUM_HEADS * NUM_AFFINE);
+    h->att_shift = mem.alloc(NUM_HEADS * NUM_AFFINE);
+    h->head_w1 = mem.alloc(NUM_OUT_ROWS * HEAD_CH);
+    h->head_w1t = mem.alloc(NUM_OUT_ROWS * HEAD_CH);
+    h->head_b1 = mem.alloc(NUM_OUT_ROWS);
+    // precision mode 3: one max-|w| slot per conv layer + one for the fused head panel
+    h->w_amax_n = (int)h->convs.size() + 1;
+    h->w_amax_arena = reinterpret_cast<unsigned *>(mem.alloc((size_t)h->w_amax_n));
+    if (!ok) return -1;
+    int i = 0;
+    for (auto &kv : h->convs) kv.second.w_amax = h->w_amax_arena + i++;
+    H3.w_amax = h->w_amax_arena + i;
     HIPCHK(h, hipDeviceSynchronize());   // zero-fills above ran on the null stream
     h->layers_built = true;
     return 0;
-}
-
-static float *P(mc_handle *h, const std::string &name, int64_t expect_numel = -1) {
-    auto it = h->bound.find(name);
-    if (it == h->bound.end()) {
-        h->err = "parameter not bound: " + name;
-        return nullptr;
-    }
-    if (it->second.dtype != MC_F32) {
-        h->err = "parameter is not fp32: " + name;
-        return nullptr;
-    }
-    if (expect_numel >= 0 && it->second.numel != expect_numel) {
-        h->err = "parameter has wrong size: " + name;
-        return nullptr;
-    }
-    return static_cast<float *>(it->second.ptr);
 }
 
 // ------------------------------------------------------------------------------ plan builder
@@ -164,28 +223,14 @@ struct Builder {
     mc_handle *h;
     Plan *pl;
     bool ok = true;
-    std::map<const float *, Tensor> pooled;   // max-pool de-duplication (nested trees re-pool the same input)
+    PlanAlloc mem{h, pl->mem, ok, 4, 256};
 
-    static constexpr int AMAX_SLOTS = 256;
     Tensor alloc(int B, int H, int W, int C) {
         Tensor t;
         t.B = B; t.H = H; t.W = W; t.C = C;
-        if (dev_alloc(h, &t.p, t.numel(), pl->bufs, pl->bytes)) ok = false;
-        if (h->prec == 3) {        // max-|x| slot of the tensor (operand scale of the convs that read it)
-            if (!pl->amax_arena) {
-                float *q = nullptr;
-                if (dev_alloc(h, &q, (size_t)AMAX_SLOTS * AMAX_WORDS, pl->bufs, pl->bytes)) ok = false;
-                pl->amax_arena = reinterpret_cast<unsigned *>(q);
-            }
-            if (pl->amax_used >= AMAX_SLOTS) { ok = false; h->err = "plan: amax slot table overflow"; }
-            else if (pl->amax_arena) t.amax = pl->amax_arena + (size_t)(pl->amax_used++) * AMAX_WORDS;
-        }
+        t.p = mem.alloc(t.numel());
+        t.amax = mem.slot();       // mode 3: max |x| of the tensor (operand scale of the convs that read it)
         return t;
-    }
-    float *alloc_raw(size_t n) {
-        float *p = nullptr;
-        if (dev_alloc(h, &p, n, pl->bufs, pl->bytes)) ok = false;
-        return p;
     }
 
     Tensor conv(const ConvLayer &L, const std::vector<Tensor> &srcs, const Tensor *res, bool relu,
@@ -228,7 +273,7 @@ struct Builder {
         a.cfg = L.cfg ? L.cfg : (ok ? mc_choose_conv_cfg(h, a, L.ks, L.stride) : CFG_128x32);
         const int chunks = conv_chunks_per_image(a.cfg, Ho, Wo);
         if (stats_out) {
-            *stats_out = alloc_raw((size_t)s0.B * chunks * L.coutp * 2);
+            *stats_out = mem.alloc((size_t)s0.B * chunks * L.coutp * 2);
             a.stats = *stats_out;
             a.stat_shift = stat_shift;
         }
@@ -240,8 +285,6 @@ struct Builder {
     }
 
     Tensor pool(const Tensor &x) {
-        auto it = pooled.find(x.p);
-        if (it != pooled.end()) return it->second;
         Tensor o = alloc(x.B, x.H / 2, x.W / 2, x.C);
         o.amax = x.amax;           // max |pool(x)| <= max |x|: the input's slot serves
         Op op{};
@@ -249,7 +292,6 @@ struct Builder {
         op.in = x.p; op.out = o.p; op.B = x.B; op.H = x.H; op.W = x.W; op.C = x.C;
         op.bytes = 4.0 * ((double)x.numel() + (double)o.numel());
         pl->ops.push_back(op);
-        pooled[x.p] = o;
         return o;
     }
 
@@ -269,33 +311,6 @@ struct Builder {
         auto it = h->convs.find(n);
         if (it == h->convs.end()) { ok = false; h->err = "no layer " + n; static ConvLayer d; return d; }
         return it->second;
-    }
-
-    Tensor block(const std::string &n, const Tensor &x, const Tensor *residual) {
-        // reference model/backbone/dla.py:34-51
-        Tensor y = conv(L(n + ".conv1"), {x}, nullptr, true);
-        const Tensor &r = residual ? *residual : x;
-        return conv(L(n + ".conv2"), {y}, &r, true);
-    }
-
-    Tensor tree(const std::string &n, int levels, int cin, int cout, int stride, bool level_root, const Tensor &x,
-                std::vector<Tensor> children) {
-        // reference model/backbone/dla.py:187-205.  In eval mode the outer `project` of a two-level
-        // tree is dead (the nested tree recomputes its own residual, dla.py:193-194) and is skipped.
-        Tensor bottom = stride > 1 ? pool(x) : x;
-        if (level_root) children.push_back(bottom);
-        if (levels == 1) {
-            Tensor residual = bottom;
-            if (cin != cout) residual = conv(L(n + ".project.0"), {bottom}, nullptr, false);
-            Tensor x1 = block(n + ".tree1", x, &residual);
-            Tensor x2 = block(n + ".tree2", x1, nullptr);
-            std::vector<Tensor> cat = {x2, x1};
-            for (auto &c : children) cat.push_back(c);
-            return conv(L(n + ".root.conv"), cat, nullptr, true);
-        }
-        Tensor x1 = tree(n + ".tree1", levels - 1, cin, cout, stride, false, x, {});
-        children.push_back(x1);
-        return tree(n + ".tree2", levels - 1, cout, cout, 1, false, x1, children);
     }
 };
 }  // namespace
@@ -401,28 +416,26 @@ static Plan *get_plan(mc_handle *h, int B, int H, int W) {
         pl->stem_op = (int)pl->ops.size();
         pl->ops.push_back(op);
     }
-    Tensor l0 = bd.conv(bd.L("backbone.level0.0"), {x0}, nullptr, true);
-    Tensor l1 = bd.conv(bd.L("backbone.level1.0"), {l0}, nullptr, true);
-    Tensor l2 = bd.tree("backbone.level2", 1, 32, 64, 2, false, l1, {});
-    Tensor l3 = bd.tree("backbone.level3", 2, 64, 128, 2, true, l2, {});
-    Tensor l4 = bd.tree("backbone.level4", 2, 128, 256, 2, true, l3, {});
-    Tensor l5 = bd.tree("backbone.level5", 1, 256, 512, 2, true, l4, {});
-    pl->n_backbone_ops = (int)pl->ops.size();
-    { Tensor lv[6] = {l0, l1, l2, l3, l4, l5}; for (int i = 0; i < 6; ++i) pl->lv[i] = lv[i]; }
-
-    // DLAUp (reference dla_neck.py:94-106,136-143): layers = [l2,l3,l4,l5]
-    std::vector<Tensor> layers = {l2, l3, l4, l5};
-    for (int i = 0; i < 3; ++i) {
-        const int j = 4 - i - 2;
-        for (int t = 1; t < 4 - j; ++t) {
-            const std::string pre = "neck.ida_" + std::to_string(i) + ".";
-            const std::string ts = std::to_string(t);
-            Tensor p = bd.conv(bd.L(pre + "proj_" + ts + ".conv"), {layers[j + t]}, nullptr, true);
-            Tensor u = bd.deconv(h->deconvs[pre + "up_" + ts], p);
-            layers[j + t] = bd.conv(bd.L(pre + "node_" + ts + ".conv"), {layers[j + t - 1], u}, nullptr, true);
+    // backbone and neck: the steps of the network graph, one op each (dead steps skipped)
+    const NetGraph &g = h->net;
+    std::vector<Tensor> t(g.node_c.size());
+    t[0] = x0;
+    for (size_t i = 0; i < g.steps.size(); ++i) {
+        const NetStep &s = g.steps[i];
+        if ((int)i == g.n_backbone) pl->n_backbone_ops = (int)pl->ops.size();
+        if (s.dead) continue;
+        if (s.kind == STEP_CONV) {
+            std::vector<Tensor> srcs;
+            for (int x : s.srcs) srcs.push_back(t[x]);
+            t[s.out] = bd.conv(bd.L(s.name), srcs, s.res >= 0 ? &t[s.res] : nullptr, s.relu);
+        } else if (s.kind == STEP_POOL) {
+            t[s.out] = bd.pool(t[s.srcs[0]]);
+        } else {
+            t[s.out] = bd.deconv(h->deconvs[s.name], t[s.srcs[0]]);
         }
     }
-    Tensor feat = layers[3];
+    for (int i = 0; i < 6; ++i) pl->lv[i] = t[g.lv[i]];
+    const Tensor feat = t[g.feat];
     pl->feat = feat;
     pl->n_neck_ops = (int)pl->ops.size();
 
@@ -431,8 +444,8 @@ static Plan *get_plan(mc_handle *h, int B, int H, int W) {
     int chunks = 0;
     Tensor hidden = bd.conv(h->head3, {feat}, nullptr, false, nullptr, nullptr, h->head_bias, false, &stats,
                             h->head_rm, &chunks);
-    float *hs_scale = bd.alloc_raw((size_t)B * NUM_HEADS * HEAD_CH);
-    float *hs_shift = bd.alloc_raw((size_t)B * NUM_HEADS * HEAD_CH);
+    float *hs_scale = bd.mem.alloc((size_t)B * NUM_HEADS * HEAD_CH);
+    float *hs_shift = bd.mem.alloc((size_t)B * NUM_HEADS * HEAD_CH);
     {
         Op op{};
         op.kind = OP_HEAD_ATTN;
@@ -454,7 +467,7 @@ static Plan *get_plan(mc_handle *h, int B, int H, int W) {
         pl->ops.push_back(op);
     }
     if (!bd.ok) {
-        for (void *q : pl->bufs) (void)hipFree(q);
+        pl->mem.release();
         return nullptr;
     }
     for (auto &op : pl->ops) {
@@ -462,7 +475,7 @@ static Plan *get_plan(mc_handle *h, int B, int H, int W) {
         pl->hbm_bytes += op.bytes;
     }
     if (h->dry_alloc) {                       // counted only: hand the size back through dry_next, keep nothing
-        h->dry_next = pl->bytes;
+        h->dry_next = pl->mem.bytes;
         return nullptr;
     }
     if (hipDeviceSynchronize() != hipSuccess) return nullptr;   // buffer zero-fills ran on the null stream
@@ -473,8 +486,8 @@ static Plan *get_plan(mc_handle *h, int B, int H, int W) {
 
 // precision mode 3: the max-|x| slots of a plan's tensors start every forward at zero (producers only raise them)
 static int plan_reset_amax(mc_handle *h, Plan *pl, hipStream_t st) {
-    if (pl->amax_arena && pl->amax_used)
-        HIPCHK(h, hipMemsetAsync(pl->amax_arena, 0, (size_t)pl->amax_used * AMAX_WORDS * sizeof(unsigned), st));
+    if (pl->mem.amax_arena && pl->mem.amax_used)
+        HIPCHK(h, hipMemsetAsync(pl->mem.amax_arena, 0, (size_t)pl->mem.amax_used * AMAX_WORDS * sizeof(unsigned), st));
     return 0;
 }
 // ... and a tensor that enters a plan from outside (stage-level forwards) gets its maximum from a pass of its own
@@ -573,9 +586,8 @@ int mc_create(int device, mc_handle **out) {
 int mc_destroy(mc_handle *h) {
     if (!h) return 0;
     (void)hipSetDevice(h->device);
-    for (auto &kv : h->plans)
-        for (void *q : kv.second->bufs) (void)hipFree(q);
-    for (void *q : h->param_bufs) (void)hipFree(q);
+    for (auto &kv : h->plans) kv.second->mem.release();
+    h->params.release();
     if (h->decode_filt) (void)hipFree(h->decode_filt);
     if (h->loss_ws) (void)hipFree(h->loss_ws);
     if (h->train && h->train_free) h->train_free(h->train);
@@ -608,7 +620,7 @@ int mc_pack_params(mc_handle *h, int train_mode, void *stream) {
     if (build_layers(h)) return -1;
     hipStream_t st = static_cast<hipStream_t>(stream);
 #define NEEDP(var, name, numel)                    \
-    float *var = P(h, (name), (numel));            \
+    float *var = static_cast<float *>(mc_param(h, (name), (numel))); \
     if (!var) return -1;
     const bool has_bb = h->bound.count("backbone.base_layer.0.weight") != 0;
     const bool has_neck = h->bound.count("neck.ida_0.proj_1.conv.weight") != 0;
@@ -1148,8 +1160,7 @@ int mc_set_conv_cfg(mc_handle *h, int cfg) {
     h->force_cfg = cfg;
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipDeviceSynchronize());
-    for (auto &kv : h->plans)   // plans bake the shape into their launch arguments
-        for (void *q : kv.second->bufs) (void)hipFree(q);
+    for (auto &kv : h->plans) kv.second->mem.release();   // plans bake the shape into their launch arguments
     h->plans.clear();
     return 0;
 }
@@ -1213,8 +1224,7 @@ int mc_set_precision(mc_handle *h, int mode) {
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipDeviceSynchronize());
     h->prec = mode;
-    for (auto &kv : h->plans)
-        for (void *q : kv.second->bufs) (void)hipFree(q);
+    for (auto &kv : h->plans) kv.second->mem.release();
     h->plans.clear();
     h->bind_gen++;          // the train plan bakes the precision into its launches: rebuilt on next use
     h->pack_clean = false;  // bf16 panels are packed by the next mc_pack_params
@@ -1231,7 +1241,7 @@ int mc_query_workspace(mc_handle *h, int B, int H, int W, int mode, size_t *byte
     if (mode == 0) {
         if (!h->packed) return fail(h, "mc_query_workspace: bind all parameters and call mc_pack_params first");
         auto it = h->plans.find(std::make_tuple(B, H, W));
-        if (it != h->plans.end()) { *bytes = it->second->bytes; return 0; }
+        if (it != h->plans.end()) { *bytes = it->second->mem.bytes; return 0; }
         h->dry_alloc = true; h->dry_next = 0;
         (void)get_plan(h, B, H, W);
         h->dry_alloc = false;
@@ -1244,8 +1254,8 @@ int mc_query_workspace(mc_handle *h, int B, int H, int W, int mode, size_t *byte
 
 size_t mc_workspace_bytes(mc_handle *h) {
     if (!h) return 0;
-    size_t n = h->param_bytes + (3 * h->decode_filt_n + h->decode_count_n) * sizeof(float) + h->train_bytes;
-    for (auto &kv : h->plans) n += kv.second->bytes;
+    size_t n = h->params.bytes + (3 * h->decode_filt_n + h->decode_count_n) * sizeof(float) + h->train_bytes;
+    for (auto &kv : h->plans) n += kv.second->mem.bytes;
     return n;
 }
 

@@ -64,6 +64,64 @@ struct DeconvLayer {
     float *wpk = nullptr;
 };
 
+constexpr const char *HEAD_NAMES[NUM_HEADS] = {"heatmap_head", "wh_head", "offset_head", "center2kpt_offset_head",
+                                               "kpt_heatmap_head", "kpt_heatmap_offset_head", "dim_head", "depth_head",
+                                               "dir_feat"};
+
+// The backbone (DLA-34) and neck (DLAUp) as one list of steps in forward order, from the stem's output (node 0) to `feat`.
+// Built once per handle (build_layers): the layer table, the eval plan and the train plan are all derived from it.  Every
+// step that is not dead makes one new node; node ids are the train plan's TNode indices.
+enum StepKind { STEP_CONV, STEP_POOL, STEP_DECONV };
+struct NetStep {
+    StepKind kind;
+    std::string name, bn;     // conv: layer-table key and its BatchNorm prefix; deconv: its name
+    std::vector<int> srcs;    // input nodes (pool / deconv: one)
+    int res = -1;             // conv: residual node (-1: none)
+    int out = -1;             // output node (-1: dead)
+    int ks = 1, stride = 1, cout = 0;
+    bool relu = true;
+    bool dead = false;                    // output never read (the outer `project` of a two-level tree: its BatchNorm
+                                          // statistics still tick in train mode)
+    bool elementwise_consumers = false;   // read by element-wise kernels only (a neck projection: by its deconv)
+    bool never_lazy = false;              // stored even where a lazy activation would do (`feat`)
+};
+struct NetGraph {
+    std::vector<NetStep> steps;
+    std::vector<int> node_c;    // channels of every node
+    int lv[6] = {};             // nodes of the level outputs l0..l5
+    int n_backbone = 0;         // steps [0, n_backbone) are the backbone, the rest the neck
+    int feat = -1;
+};
+
+// Device memory of a launch plan (or of the handle's parameter tables).
+struct PlanMem {
+    std::vector<void *> bufs;
+    size_t bytes = 0;                  // requested sizes, summed (mc_query_workspace / mc_workspace_bytes)
+    unsigned *amax_arena = nullptr;    // precision mode 3: one max-|x| slot per tensor, zeroed at the start of every forward
+    int amax_used = 0;
+    void release() {
+        for (void *q : bufs) (void)hipFree(q);
+        bufs.clear();
+    }
+};
+
+// The allocator of every plan builder: zero-filled buffers owned by `m`.  With h->dry_alloc (mc_query_workspace) a buffer
+// is only counted: its address is a fake that is never dereferenced.  A failed request sets h->err, clears `ok` and
+// returns null.
+struct PlanAlloc {
+    mc_handle *h;
+    PlanMem &m;
+    bool &ok;
+    size_t empty_floats;    // the size of an empty request (eval plan and parameter tables: 4 floats, train plan: 1)
+    int amax_slots;         // capacity of the slot arena
+    float *alloc(size_t nfloats);
+    unsigned *slot();       // mode 3: a fresh max-|x| slot (null in the other modes)
+};
+
+// A bound tensor checked against what a plan reads: `dtype` (MC_F32; MC_I64 for num_batches_tracked) and `numel`
+// elements, also for "<key>#grad" buffers.  Missing or mismatched: h->err names the key, null is returned.
+void *mc_param(mc_handle *h, const std::string &name, int64_t numel, int dtype = MC_F32);
+
 enum OpKind { OP_STEM, OP_CONV, OP_POOL, OP_DECONV, OP_HEAD_ATTN, OP_HEAD_APPLY, OP_TO_NCHW };
 
 struct Op {
@@ -85,11 +143,8 @@ struct Op {
 struct Plan {
     int B = 0, H = 0, W = 0;
     std::vector<Op> ops;
-    std::vector<void *> bufs;
-    size_t bytes = 0;
+    PlanMem mem;
     Tensor feat, lv[6];
-    unsigned *amax_arena = nullptr;   // mode 3: one slot per activation tensor, zeroed at the start of every forward
-    int amax_used = 0;
     int stem_op = -1, head_apply_op = -1;
     int n_backbone_ops = 0, n_neck_ops = 0;
     double flops = 0, hbm_bytes = 0;
@@ -99,6 +154,7 @@ struct mc_handle {
     int device = 0;
     std::string err;
     std::unordered_map<std::string, Bound> bound;
+    NetGraph net;
     std::map<std::string, ConvLayer> convs;
     std::map<std::string, DeconvLayer> deconvs;
     // stem
@@ -111,8 +167,7 @@ struct mc_handle {
     HeadAttnParams hap{};
     bool layers_built = false, packed = false;
     int packed_groups = 0;   // bit0 backbone, bit1 neck, bit2 head
-    size_t param_bytes = 0;
-    std::vector<void *> param_bufs;
+    PlanMem params;
     std::map<std::tuple<int, int, int>, std::unique_ptr<Plan>> plans;
     Plan *last_plan = nullptr;
     float *decode_filt = nullptr;

@@ -132,14 +132,13 @@ static int losses_backward_impl(mc_handle *h, const float *const preds[MC_NUM_PR
     const int npf = mc::focal_partial_floats();
     float *aux = h->loss_ws + 2 * npf;
     float *scratch_losses = aux + 8;
-    static const int PC[10] = {3, 9, 2, 2, 2, 18, 3, 2, 12, 12};
     // recompute the reductions the gradients need (npos, object count, dim compensation weight)
     HIPCHK(h, mc::launch_focal(preds[0], t->center_heatmap_target, (size_t)B * 3 * HW, h->loss_ws, scratch_losses + 0, aux + 0, st));
     HIPCHK(h, mc::launch_focal(preds[1], t->kpt_heatmap_target, (size_t)B * 9 * HW, h->loss_ws + npf, scratch_losses + 5, aux + 1, st));
     if (h->dp_arena && dpreds[2] == h->dp_arena) {
         HIPCHK(h, hipMemsetAsync(h->dp_arena, 0, h->dp_arena_bytes, st));
     } else {
-        for (int i = 2; i < 10; ++i) HIPCHK(h, hipMemsetAsync(dpreds[i], 0, (size_t)B * PC[i] * HW * 4, st));
+        for (int i = 2; i < 10; ++i) HIPCHK(h, hipMemsetAsync(dpreds[i], 0, (size_t)B * mc::PRED_CH[i] * HW * 4, st));
     }
     HIPCHK(h, mc::launch_focal_grad(preds[0], t->center_heatmap_target, (size_t)B * 3 * HW, aux + 0, grad_losses, 0, dpreds[0], st, wrt_pred));
     HIPCHK(h, mc::launch_focal_grad(preds[1], t->kpt_heatmap_target, (size_t)B * 9 * HW, aux + 1, grad_losses, 5, dpreds[1], st, wrt_pred));

@@ -73,8 +73,7 @@ struct Rec {
 struct TrainState {
     int B = 0, H = 0, W = 0;
     unsigned long long bind_gen = 0;
-    std::vector<void *> bufs;
-    size_t bytes = 0;
+    PlanMem mem;
     std::vector<TNode> nodes;
     std::vector<Rec> recs;
     std::vector<Fn> fwd, bwd;
@@ -113,9 +112,6 @@ struct TrainState {
     float *gfeat_ext = nullptr;
     bool skip_feat_dgrad = false;    // head-only plan, mc_head_backward(grad_feat = NULL)
     int feat_dgrad_closure = -1;     // index in `bwd` of the data gradient into the external feat node
-    // precision mode 3: one max-|x| slot per activation / gradient tensor, zeroed at the start of every forward
-    unsigned *amax_arena = nullptr;
-    int amax_used = 0;
     // plan-owned
     mc_targets targets{};
     float *dpred[10] = {nullptr};
@@ -133,7 +129,7 @@ static void train_free(TrainState *t) {
         if (e) (void)hipEventDestroy(e);
     if (t->side_done) (void)hipEventDestroy(t->side_done);
     if (t->side) (void)hipStreamDestroy(t->side);
-    for (void *q : t->bufs) (void)hipFree(q);
+    t->mem.release();
     delete t;
 }
 
@@ -142,44 +138,20 @@ namespace {
 struct TB {   // train plan builder
     mc_handle *h;
     TrainState *ts;
-    std::map<int, int> pooled;      // node -> its 2x2 max-pooled node
+    PlanAlloc mem{h, ts->mem, ts->ok, 1, 1024};
     void *last_panel16 = nullptr;   // bf16 twin of the panel the last pack_job() made
 
-    static constexpr int AMAX_SLOTS = 1024;
     // bn_backward(): the caller consumes (d, y, coef) itself -- no element-wise dY pass (the stem, whose dY is read by its
     // weight gradient only); honoured on the backward-statistics-epilogue path, reported back in did_skip_affine
     bool want_skip_affine = false, did_skip_affine = false;
     float *skip_coef = nullptr;
-    unsigned *slot() {        // mode 3: a fresh max-|x| slot (null in the other modes)
-        if (h->prec != 3) return nullptr;
-        if (!ts->amax_arena) ts->amax_arena = reinterpret_cast<unsigned *>(alloc((size_t)AMAX_SLOTS * AMAX_WORDS));
-        if (ts->amax_used >= AMAX_SLOTS) { ts->ok = false; h->err = "train plan: amax slot table overflow"; return nullptr; }
-        return ts->amax_arena ? ts->amax_arena + (size_t)(ts->amax_used++) * AMAX_WORDS : nullptr;
-    }
+    float *alloc(size_t n) { return mem.alloc(n); }
+    unsigned *slot() { return mem.slot(); }
     unsigned *w_slot(const float *w_master) {
         if (h->prec != 3) return nullptr;
         auto it = h->w_amax_of.find(w_master);
         if (it == h->w_amax_of.end()) { ts->ok = false; h->err = "train plan: no max-|w| slot for a master weight"; return nullptr; }
         return it->second;
-    }
-    float *alloc(size_t n) {
-        float *p = nullptr;
-        void *q = nullptr;
-        const size_t bytes = (n ? n : 1) * sizeof(float);
-        if (h->dry_alloc) {                   // mc_query_workspace: count only (never dereferenced)
-            h->dry_next += (bytes + 255) / 256 * 256;
-            ts->bytes += bytes;
-            return reinterpret_cast<float *>((uintptr_t)0x100000 + h->dry_next);
-        }
-        if (hipMalloc(&q, bytes) != hipSuccess || hipMemset(q, 0, bytes) != hipSuccess) {
-            ts->ok = false;
-            h->err = "train plan: out of device memory";
-            return nullptr;
-        }
-        ts->bufs.push_back(q);
-        ts->bytes += bytes;
-        p = static_cast<float *>(q);
-        return p;
     }
     // activation / gradient maps the autotuner times kernels on: optionally ReLU-shaped noise instead of zeros (see
     // launch_noise_fill).  MEASURED (round 4, one session, B=32): 56.52 / 56.56 ms per step tuned on zeros, 56.51 / 56.62
@@ -189,7 +161,7 @@ struct TB {   // train plan builder
     float *alloc_map(size_t n) {
         float *p = alloc(n);
         if (p && !h->dry_alloc && h->autotune && tune_noise && n >= 4096)
-            (void)launch_noise_fill(p, n, (unsigned)ts->bufs.size() * 7919u, nullptr);
+            (void)launch_noise_fill(p, n, (unsigned)ts->mem.bufs.size() * 7919u, nullptr);
         return p;
     }
     // ---- gradient maps.  The backward closures are BUILT in the order they run, so the life of a map's gradient is known
@@ -284,13 +256,15 @@ struct TB {   // train plan builder
         ts->nodes.push_back(n);
         return (int)ts->nodes.size() - 1;
     }
-    float *P(const std::string &name) {
-        auto it = h->bound.find(name);
-        if (it == h->bound.end()) { ts->ok = false; h->err = "parameter not bound: " + name; return nullptr; }
-        return static_cast<float *>(it->second.ptr);
+    // bound tensors, checked by mc_param: a missing or mismatched one fails the build
+    void *bound(const std::string &name, int64_t numel, int dtype) {
+        void *p = mc_param(h, name, numel, dtype);
+        if (!p) ts->ok = false;
+        return p;
     }
-    float *G(const std::string &name) { return P(name + "#grad"); }
-    long long *NBT(const std::string &name) { return reinterpret_cast<long long *>(P(name)); }
+    float *P(const std::string &name, int64_t numel) { return static_cast<float *>(bound(name, numel, MC_F32)); }
+    float *G(const std::string &name, int64_t numel) { return P(name + "#grad", numel); }
+    long long *NBT(const std::string &name) { return static_cast<long long *>(bound(name, 1, MC_I64)); }
     ConvLayer &L(const std::string &n) {
         auto it = h->convs.find(n);
         if (it == h->convs.end()) { ts->ok = false; h->err = "no layer " + n; static ConvLayer d; return d; }
@@ -306,10 +280,10 @@ struct TB {   // train plan builder
     void bn_train_ops(const Tensor &y, const float *stats, int nb, int cstride, const std::string &bn, float eps,
                       float mom, float *a, float *b, float *mean, float *rstd, const unsigned *ymax = nullptr,
                       unsigned *zmax = nullptr, int zrelu = 1) {
-        float *g = P(bn + ".weight"), *be = P(bn + ".bias"), *rm = P(bn + ".running_mean"), *rv = P(bn + ".running_var");
+        const int C = y.C;
+        float *g = P(bn + ".weight", C), *be = P(bn + ".bias", C), *rm = P(bn + ".running_mean", C), *rv = P(bn + ".running_var", C);
         long long *nbt = NBT(bn + ".num_batches_tracked");
         const double n = (double)y.B * y.H * y.W;
-        const int C = y.C;
         double *fold = fold_scratch(nb, C);
         ts->fwd.push_back([=](mc_handle *hh, hipStream_t st) {
             HIPCHK(hh, launch_bn_finalize(stats, nb, cstride, n, C, rm, g, be, eps, mom, rm, rv, nbt, a, b, mean, rstd, st, fold,
@@ -318,8 +292,16 @@ struct TB {   // train plan builder
         });
     }
 
-    int conv_bn(ConvLayer &Lr, const std::vector<int> &srcs, int res, bool relu, bool dead = false, bool elementwise_consumers = false,
-                bool never_lazy = false) {
+    // the neck's LAST node is `feat` (NetStep::never_lazy): its consumers are the fused 64 -> 576 head conv and that conv's
+    // weight gradient, the two longest launches of the step -- formed on load it cost them 0.15 + 0.22 ms (alone) to save a
+    // 0.095 ms pass: stored (MONOCON_HIP_LAZY_FEAT=1: lazy like the other nodes)
+    bool lazy_feat = [] { const char *e = std::getenv("MONOCON_HIP_LAZY_FEAT"); return e && std::atoi(e) != 0; }();
+
+    int conv_bn(const NetStep &s) {
+        ConvLayer &Lr = L(s.name);
+        const std::vector<int> &srcs = s.srcs;
+        const int res = s.res;
+        const bool relu = s.relu, dead = s.dead, never_lazy = s.never_lazy && !lazy_feat;
         const Tensor s0 = ts->nodes[srcs[0]].t;   // by value: node() below may reallocate ts->nodes
         const int B = s0.B;
         const int Ho = (s0.H + 2 * (Lr.ks / 2) - Lr.ks) / Lr.stride + 1, Wo = (s0.W + 2 * (Lr.ks / 2) - Lr.ks) / Lr.stride + 1;
@@ -329,7 +311,7 @@ struct TB {   // train plan builder
         r.y.p = alloc(r.y.numel());
         // lazy output: BatchNorm (+ ReLU) without residual in mode 3 (the convs of every kernel family leave max |y|)
         const bool lazy = !dead && !never_lazy && res < 0 && h->prec == 3 && (lazy_mask & (relu ? 1 : 2)) != 0 &&
-                          (!relu || elementwise_consumers || (long long)Ho * Wo * Lr.cout >= lazy_min);
+                          (!relu || s.elementwise_consumers || (long long)Ho * Wo * Lr.cout >= lazy_min);
         r.z = dead ? -1 : node(B, Ho, Wo, Lr.cout, true, !lazy);
         ConvArgs a{};
         a.nsrc = (int)srcs.size();
@@ -360,7 +342,7 @@ struct TB {   // train plan builder
         const int chunks = conv_chunks_per_image(a.cfg, Ho, Wo);
         float *stats = alloc((size_t)B * chunks * Lr.coutp * 2);
         a.stats = stats;
-        a.stat_shift = P(Lr.bn + ".running_mean");
+        a.stat_shift = P(Lr.bn + ".running_mean", Lr.cout);
         const int ks = Lr.ks, stride = Lr.stride;
         ts->fwd.push_back([=](mc_handle *hh, hipStream_t st) { HIPCHK(hh, launch_conv(a, ks, stride, st)); return 0; });
         float *ca = alloc(Lr.cout), *cb = alloc(Lr.cout);
@@ -398,8 +380,6 @@ struct TB {   // train plan builder
 
     int pool(int x) {
         const Tensor t = ts->nodes[x].t;           // by value (see conv_bn)
-        auto it = pooled.find(x);
-        if (it != pooled.end()) return it->second;
         if (ts->nodes[x].la && !ts->nodes[x].lrelu) materialise(x);
         const Tensor tx = ts->nodes[x].t;
         const int o = node(t.B, t.H / 2, t.W / 2, t.C, true);
@@ -414,7 +394,6 @@ struct TB {   // train plan builder
         Rec r;
         r.kind = REC_POOL; r.in = x; r.z = o;
         ts->recs.push_back(r);
-        pooled[x] = o;
         return o;
     }
 
@@ -434,33 +413,6 @@ struct TB {   // train plan builder
         r.kind = REC_DECONV; r.in = x; r.z = o; r.D = &D;
         ts->recs.push_back(r);
         return o;
-    }
-
-    int block(const std::string &n, int x, int residual) {
-        const int y = conv_bn(L(n + ".conv1"), {x}, -1, true);
-        return conv_bn(L(n + ".conv2"), {y}, residual >= 0 ? residual : x, true);
-    }
-
-    int tree(const std::string &n, int levels, int cin, int cout, int stride, bool level_root, int x, std::vector<int> children,
-             bool outer_of_nested = false) {
-        // reference model/backbone/dla.py:187-205; the outer `project` of a two-level tree only ticks
-        // its BN running statistics (its output is recomputed inside the nested tree and never used)
-        (void)outer_of_nested;
-        const int bottom = stride > 1 ? pool(x) : x;
-        if (level_root) children.push_back(bottom);
-        if (levels == 1) {
-            int residual = bottom;
-            if (cin != cout) residual = conv_bn(L(n + ".project.0"), {bottom}, -1, false);
-            const int x1 = block(n + ".tree1", x, residual);
-            const int x2 = block(n + ".tree2", x1, -1);
-            std::vector<int> cat = {x2, x1};
-            for (int c : children) cat.push_back(c);
-            return conv_bn(L(n + ".root.conv"), cat, -1, true);
-        }
-        if (cin != cout) conv_bn(L(n + ".project.0"), {bottom}, -1, false, /*dead=*/true);
-        const int x1 = tree(n + ".tree1", levels - 1, cin, cout, stride, false, x, {});
-        children.push_back(x1);
-        return tree(n + ".tree2", levels - 1, cout, cout, 1, false, x1, children);
     }
 
     // ---------------------------------------------------------------- backward pieces
@@ -605,8 +557,8 @@ struct TB {   // train plan builder
         dy.amax = slot();
         unsigned *dymax = dy.amax;
         const int B = r.y.B, C = r.y.C, rows = r.y.H * r.y.W;
-        const float *yp = r.y.p, *gz = zn.g, *zp = zn.t.p, *gamma = P(bn + ".weight"), *mean = r.mean, *rstd = r.rstd;
-        float *dg = G(bn + ".weight"), *db = G(bn + ".bias"), *dyp = dy.p;
+        const float *yp = r.y.p, *gz = zn.g, *zp = zn.t.p, *gamma = P(bn + ".weight", C), *mean = r.mean, *rstd = r.rstd;
+        float *dg = G(bn + ".weight", C), *db = G(bn + ".bias", C), *dyp = dy.p;
         float *coef = alloc((size_t)C * 4);
         // ReLU without residual: the mask is recomputed from y (bit-identical to z > 0), z is not read
         const int relu = r.relu ? ((r.res < 0 && r.ca && r.cb) ? 2 : 1) : 0;
@@ -620,6 +572,24 @@ struct TB {   // train plan builder
             ts->nodes[r.res].last_conv = nullptr; ts->nodes[r.res].last_pool = nullptr;
         }
         const double n = (double)B * rows;
+        // every branch below only decides where the (sum d, sum d*y) partials come from; this pushes the ONE closure of the
+        // BatchNorm backward: the reduction pass (reduce: no launch of the step left them), bn_bwd_finalize, and the
+        // affine pass (dZ -> dY in place, the residual's share; it applies the ReLU mask only after the reduction pass --
+        // a launch that leaves the partials has masked the gradient already)
+        auto closure = [&](float *partial, int nbp, int cstride, bool reduce, bool affine) {
+            double *fold = fold_scratch(nbp, C);  // (61 440 partial rows at full resolution: 16 workgroups walking them took 87 us)
+            const int arelu = reduce ? relu : 0;
+            const float *aa = reduce ? fa : nullptr, *ab = reduce ? fb : nullptr;
+            ts->bwd.push_back([=](mc_handle *hh, hipStream_t st) {
+                if (reduce) HIPCHK(hh, launch_chan_reduce(yp, gz, zp, nullptr, B, rows, C, 1, relu, partial, C, st, fa, fb));
+                HIPCHK(hh, launch_bn_bwd_finalize(partial, nbp, cstride, n, C, gamma, mean, rstd, dg, db, coef, st, fold));
+                if (affine)
+                    HIPCHK(hh, launch_affine_bwd(gz, zp, yp, coef, B, (size_t)rows, C, 0, arelu, dyp, gres, gmode, st, aa, ab, nullptr,
+                                                 nullptr, dymax));
+                return 0;
+            });
+            return dy;
+        };
         ConvArgs *lc = zn.last_conv;
         // MONOCON_HIP_BM_EPILOGUE: 0 = never take over the reductions in the data gradient's epilogue (always the reduction
         // pass), N > 1 = only for maps of at most N pixels per image
@@ -642,25 +612,15 @@ struct TB {   // train plan builder
             if (std::getenv("MONOCON_HIP_PLAN_DEBUG"))
                 fprintf(stderr, "[plan]   twin of %-36s cfg %3d  K %4d  Cout %3d  %dx%d  res %d  nsrc %d srcC %d wres %d\n", bn.c_str(), lc->cfg,
                         lc->Cin, lc->Cout, lc->Hout, lc->Wout, lc->res != nullptr, lc->nsrc, lc->src[0].C, (lc->cfg & CFG_WRES) != 0);
-            double *fold = fold_scratch(nbp, C);
-            if (want_skip_affine && !gres) {
-                // the epilogue also leaves max |d| (for the consumer's operand scale); only the coefficients are computed here
+            const bool skip_affine = want_skip_affine && !gres;
+            if (skip_affine) {
+                // the epilogue also leaves max |d| (for the consumer's operand scale); only the coefficients are computed here:
+                // dy.p = the masked gradient d, dy.amax = max |d|
                 lc->amax_out = dymax;
-                ts->bwd.push_back([=](mc_handle *hh, hipStream_t st) {
-                    HIPCHK(hh, launch_bn_bwd_finalize(partial, nbp, cstride, n, C, gamma, mean, rstd, dg, db, coef, st, fold));
-                    return 0;
-                });
                 did_skip_affine = true;
                 skip_coef = coef;
-                return dy;        // .p = the masked gradient d, .amax = max |d|
             }
-            ts->bwd.push_back([=](mc_handle *hh, hipStream_t st) {
-                HIPCHK(hh, launch_bn_bwd_finalize(partial, nbp, cstride, n, C, gamma, mean, rstd, dg, db, coef, st, fold));
-                HIPCHK(hh, launch_affine_bwd(gz, zp, yp, coef, B, (size_t)rows, C, 0, 0, dyp, gres, gmode, st, nullptr, nullptr, nullptr,
-                                             nullptr, dymax));
-                return 0;
-            });
-            return dy;
+            return closure(partial, nbp, cstride, false, !skip_affine);
         }
         // the gradient of this map was completed by a max-pool backward over a LAZY map (it holds y, forms z for its window
         // comparison anyway): that launch masks the total and leaves the partials -- no reduction pass (MONOCON_HIP_POOL_STATS=0: off)
@@ -672,16 +632,9 @@ struct TB {   // train plan builder
                 const int nbp = maxpool2_bwd_blocks(B, pl->H, pl->W, C);
                 float *partial = alloc((size_t)nbp * C * 2);
                 pl->stats = partial;
-                double *fold = fold_scratch(nbp, C);
                 if (std::getenv("MONOCON_HIP_PLAN_DEBUG"))
                     fprintf(stderr, "[plan]   statistics of %-36s left by the max-pool backward (%d partial rows)\n", bn.c_str(), nbp);
-                ts->bwd.push_back([=](mc_handle *hh, hipStream_t st) {
-                    HIPCHK(hh, launch_bn_bwd_finalize(partial, nbp, C, n, C, gamma, mean, rstd, dg, db, coef, st, fold));
-                    HIPCHK(hh, launch_affine_bwd(gz, zp, yp, coef, B, (size_t)rows, C, 0, 0, dyp, gres, gmode, st, nullptr, nullptr, nullptr,
-                                                 nullptr, dymax));
-                    return 0;
-                });
-                return dy;
+                return closure(partial, nbp, C, false, true);
             }
         }
         // ... or by the fused backward of the depthwise deconv that is its only consumer (neck proj -> up): same contract
@@ -691,29 +644,13 @@ struct TB {   // train plan builder
                 const int nbp = B * r.y.H;            // one workgroup per (image, row) of the deconv's input
                 float *partial = alloc((size_t)nbp * C * 2);
                 *ds = partial;
-                double *fold = fold_scratch(nbp, C);
                 if (std::getenv("MONOCON_HIP_PLAN_DEBUG"))
                     fprintf(stderr, "[plan]   statistics of %-36s left by the deconv backward (%d partial rows)\n", bn.c_str(), nbp);
-                ts->bwd.push_back([=](mc_handle *hh, hipStream_t st) {
-                    HIPCHK(hh, launch_bn_bwd_finalize(partial, nbp, C, n, C, gamma, mean, rstd, dg, db, coef, st, fold));
-                    HIPCHK(hh, launch_affine_bwd(gz, zp, yp, coef, B, (size_t)rows, C, 0, 0, dyp, nullptr, 0, st, nullptr, nullptr, nullptr,
-                                                 nullptr, dymax));
-                    return 0;
-                });
-                return dy;
+                return closure(partial, nbp, C, false, true);       // (gres is null here)
             }
         }
         const int nb = chan_reduce_blocks(B, rows);
-        float *partial = alloc((size_t)nb * C * 2);
-        double *fold2 = fold_scratch(nb, C);      // (61 440 partial rows at full resolution: 16 workgroups walking them took 87 us)
-        ts->bwd.push_back([=](mc_handle *hh, hipStream_t st) {
-            HIPCHK(hh, launch_chan_reduce(yp, gz, zp, nullptr, B, rows, C, 1, relu, partial, C, st, fa, fb));
-            HIPCHK(hh, launch_bn_bwd_finalize(partial, nb, C, n, C, gamma, mean, rstd, dg, db, coef, st, fold2));
-            HIPCHK(hh, launch_affine_bwd(gz, zp, yp, coef, B, (size_t)rows, C, 0, relu, dyp, gres, gmode, st, fa, fb, nullptr, nullptr,
-                                             dymax));
-            return 0;
-        });
-        return dy;
+        return closure(alloc((size_t)nb * C * 2), nb, C, true, true);
     }
 };
 
@@ -729,9 +666,9 @@ static TrainState *build_train(mc_handle *h, int B, int H, int W, bool head_only
     int feat = -1;
     if (h->prec == 3) {      // the max-|x| slots start every forward at zero: their producers only raise them
         (void)b.slot();
-        --ts->amax_used;
+        --ts->mem.amax_used;
         ts->fwd.push_back([=](mc_handle *hh, hipStream_t st) {
-            HIPCHK(hh, hipMemsetAsync(ts->amax_arena, 0, (size_t)ts->amax_used * AMAX_WORDS * sizeof(unsigned), st));
+            HIPCHK(hh, hipMemsetAsync(ts->mem.amax_arena, 0, (size_t)ts->mem.amax_used * AMAX_WORDS * sizeof(unsigned), st));
             return 0;
         });
     }
@@ -766,7 +703,7 @@ static TrainState *build_train(mc_handle *h, int B, int H, int W, bool head_only
         const int nb = fused_stats ? B * H : chan_reduce_blocks(B, H * W);
         float *partial = b.alloc((size_t)nb * 16 * 2), *ca = b.alloc(16), *cb = b.alloc(16);
         stem.mean = b.alloc(16); stem.rstd = b.alloc(16);
-        float *yp = stem.y.p, *zp = ts->nodes[stem.z].t.p, *rm = b.P(stem.bn + ".running_mean");
+        float *yp = stem.y.p, *zp = ts->nodes[stem.z].t.p, *rm = b.P(stem.bn + ".running_mean", 16);
         unsigned *zmax = ts->nodes[stem.z].t.amax;
         unsigned *imax = fused_stats ? b.slot() : nullptr;     // max |image|, left by the forward stem for its weight gradient
         ts->img_amax = imax;
@@ -797,30 +734,12 @@ static TrainState *build_train(mc_handle *h, int B, int H, int W, bool head_only
         }
         ts->recs.push_back(stem);
     }
-    const int x0 = stem.z;
-    const int l0 = b.conv_bn(b.L("backbone.level0.0"), {x0}, -1, true);
-    const int l1 = b.conv_bn(b.L("backbone.level1.0"), {l0}, -1, true);
-    const int l2 = b.tree("backbone.level2", 1, 32, 64, 2, false, l1, {});
-    const int l3 = b.tree("backbone.level3", 2, 64, 128, 2, true, l2, {});
-    const int l4 = b.tree("backbone.level4", 2, 128, 256, 2, true, l3, {});
-    const int l5 = b.tree("backbone.level5", 1, 256, 512, 2, true, l4, {});
-    std::vector<int> layers = {l2, l3, l4, l5};
-    for (int i = 0; i < 3; ++i) {
-        const int j = 4 - i - 2;
-        for (int t = 1; t < 4 - j; ++t) {
-            const std::string pre = "neck.ida_" + std::to_string(i) + ".", tsn = std::to_string(t);
-            const int p = b.conv_bn(b.L(pre + "proj_" + tsn + ".conv"), {layers[j + t]}, -1, true, false, /*elementwise_consumers=*/true);
-            const int u = b.deconv(h->deconvs[pre + "up_" + tsn], p);
-            // the neck's LAST node is `feat`: its consumers are the fused 64 -> 576 head conv and that conv's weight gradient, the
-            // two longest launches of the step -- formed on load it cost them 0.15 + 0.22 ms (alone) to save a 0.095 ms pass:
-            // stored (MONOCON_HIP_LAZY_FEAT=1: lazy like the other nodes)
-            const char *lf_env = std::getenv("MONOCON_HIP_LAZY_FEAT");                  // read per plan build
-            const bool lazy_feat = lf_env && std::atoi(lf_env) != 0;
-            const bool is_feat = i == 2 && t == 3;
-            layers[j + t] = b.conv_bn(b.L(pre + "node_" + tsn + ".conv"), {layers[j + t - 1], u}, -1, true, false, false, is_feat && !lazy_feat);
-        }
+    // ---- backbone and neck: the steps of the network graph (the nodes they make are the graph's; node 0 is the stem's)
+    for (const NetStep &s : h->net.steps) {
+        const int o = s.kind == STEP_CONV ? b.conv_bn(s) : s.kind == STEP_POOL ? b.pool(s.srcs[0]) : b.deconv(h->deconvs[s.name], s.srcs[0]);
+        if (o != s.out) { ts->ok = false; h->err = "train plan: node order differs from the network graph"; }
     }
-    feat = layers[3];
+    feat = h->net.feat;
     }   // !head_only
 
     // ---- heads
@@ -831,24 +750,23 @@ static TrainState *build_train(mc_handle *h, int B, int H, int W, bool head_only
 
     Tensor raw; raw.B = B; raw.H = fh; raw.W = fw; raw.C = LD; raw.p = b.alloc(raw.numel());
     AttnTrainArgs at{};
-    static const char *HN[NUM_HEADS] = {"heatmap_head", "wh_head", "offset_head", "center2kpt_offset_head", "kpt_heatmap_head",
-                                        "kpt_heatmap_offset_head", "dim_head", "depth_head", "dir_feat"};
     AttnGradPtrs gp{};
     for (int hd = 0; hd < NUM_HEADS; ++hd) {
-        const std::string an = std::string("head.") + HN[hd] + ".1";
-        at.rm[hd] = b.P(an + ".running_mean"); at.rv[hd] = b.P(an + ".running_var");
+        const std::string an = std::string("head.") + HEAD_NAMES[hd] + ".1";
+        const int A = NUM_AFFINE, AC = NUM_AFFINE * HEAD_CH;
+        at.rm[hd] = b.P(an + ".running_mean", HEAD_CH); at.rv[hd] = b.P(an + ".running_var", HEAD_CH);
         at.nbt[hd] = b.NBT(an + ".num_batches_tracked");
-        at.att_w[hd] = b.P(an + ".attn_weights.attention.0.weight");
-        at.att_g[hd] = b.P(an + ".attn_weights.attention.1.weight");
-        at.att_b[hd] = b.P(an + ".attn_weights.attention.1.bias");
-        at.att_rm[hd] = b.P(an + ".attn_weights.attention.1.running_mean");
-        at.att_rv[hd] = b.P(an + ".attn_weights.attention.1.running_var");
+        at.att_w[hd] = b.P(an + ".attn_weights.attention.0.weight", AC);
+        at.att_g[hd] = b.P(an + ".attn_weights.attention.1.weight", A);
+        at.att_b[hd] = b.P(an + ".attn_weights.attention.1.bias", A);
+        at.att_rm[hd] = b.P(an + ".attn_weights.attention.1.running_mean", A);
+        at.att_rv[hd] = b.P(an + ".attn_weights.attention.1.running_var", A);
         at.att_nbt[hd] = b.NBT(an + ".attn_weights.attention.1.num_batches_tracked");
-        at.weight_[hd] = b.P(an + ".weight_"); at.bias_[hd] = b.P(an + ".bias_");
-        gp.d_weight_[hd] = b.G(an + ".weight_"); gp.d_bias_[hd] = b.G(an + ".bias_");
-        gp.d_att_w[hd] = b.G(an + ".attn_weights.attention.0.weight");
-        gp.d_att_g[hd] = b.G(an + ".attn_weights.attention.1.weight");
-        gp.d_att_b[hd] = b.G(an + ".attn_weights.attention.1.bias");
+        at.weight_[hd] = b.P(an + ".weight_", AC); at.bias_[hd] = b.P(an + ".bias_", AC);
+        gp.d_weight_[hd] = b.G(an + ".weight_", AC); gp.d_bias_[hd] = b.G(an + ".bias_", AC);
+        gp.d_att_w[hd] = b.G(an + ".attn_weights.attention.0.weight", AC);
+        gp.d_att_g[hd] = b.G(an + ".attn_weights.attention.1.weight", A);
+        gp.d_att_b[hd] = b.G(an + ".attn_weights.attention.1.bias", A);
     }
     ConvArgs c3{};
     {
@@ -880,8 +798,7 @@ static TrainState *build_train(mc_handle *h, int B, int H, int W, bool head_only
     {
         ha.hidden = xh.p; ha.scale = at.scale; ha.shift = at.shift; ha.w = h->head_w1t; ha.b = h->head_b1;
         ha.B = B; ha.HW = HW; ha.z_out = nullptr;
-        static const int PCH[10] = {3, 9, 2, 2, 2, 18, 3, 2, 12, 12};
-        for (int i = 0; i < 10; ++i) ha.pred_c[i] = PCH[i];     // the prediction pointers are per call (ts->preds)
+        for (int i = 0; i < 10; ++i) ha.pred_c[i] = PRED_CH[i];     // the prediction pointers are per call (ts->preds)
         // one closure per kernel family so that mc_profile_train attributes the durations correctly
         ts->fwd.push_back([=](mc_handle *hh, hipStream_t st) { HIPCHK(hh, launch_conv(c3, 3, 1, st)); return 0; });
         ts->fwd.push_back([=](mc_handle *hh, hipStream_t st) {
@@ -913,13 +830,12 @@ static TrainState *build_train(mc_handle *h, int B, int H, int W, bool head_only
         T.mask_target = reinterpret_cast<uint8_t *>(tp[12]);
         T.mask_center2kpt_offset = tp[13]; T.mask_kpt_heatmap_offset = tp[14];
         h->tgt_arena = ta; h->tgt_arena_bytes = ttot * sizeof(float);
-        static const int PC[10] = {3, 9, 2, 2, 2, 18, 3, 2, 12, 12};
-        ts->dpred[0] = b.alloc((size_t)B * PC[0] * HW);
-        ts->dpred[1] = b.alloc((size_t)B * PC[1] * HW);
+        ts->dpred[0] = b.alloc((size_t)B * PRED_CH[0] * HW);
+        ts->dpred[1] = b.alloc((size_t)B * PRED_CH[1] * HW);
         size_t dtot = 0;
-        for (int i = 2; i < 10; ++i) dtot += up((size_t)B * PC[i] * HW);
+        for (int i = 2; i < 10; ++i) dtot += up((size_t)B * PRED_CH[i] * HW);
         float *da = b.alloc(dtot);
-        { size_t o = 0; for (int i = 2; i < 10; ++i) { ts->dpred[i] = da ? da + o : nullptr; o += up((size_t)B * PC[i] * HW); } }
+        { size_t o = 0; for (int i = 2; i < 10; ++i) { ts->dpred[i] = da ? da + o : nullptr; o += up((size_t)B * PRED_CH[i] * HW); } }
         h->dp_arena = da; h->dp_arena_bytes = dtot * sizeof(float);
         ts->fwd.push_back([=](mc_handle *hh, hipStream_t st) {
             if (mc_make_targets(hh, &ts->labels, B, ts->max_objs, ts->pad_h, ts->pad_w, fh, fw, &ts->targets, st)) return -1;
@@ -955,11 +871,13 @@ static TrainState *build_train(mc_handle *h, int B, int H, int W, bool head_only
         const int *rb = head_row_begin();
         struct Seg { float *dst_w, *dst_b; int r0, nr; };
         std::vector<Seg> segs;
-        for (int hd = 0; hd < 8; ++hd)
-            segs.push_back(Seg{b.G(std::string("head.") + HN[hd] + ".3.weight"), b.G(std::string("head.") + HN[hd] + ".3.bias"),
-                               rb[hd], rb[hd + 1] - rb[hd]});
-        segs.push_back(Seg{b.G("head.dir_cls.0.weight"), b.G("head.dir_cls.0.bias"), rb[8], 12});
-        segs.push_back(Seg{b.G("head.dir_reg.0.weight"), b.G("head.dir_reg.0.bias"), rb[8] + 12, 12});
+        for (int hd = 0; hd < 8; ++hd) {
+            const int nr = rb[hd + 1] - rb[hd];
+            segs.push_back(Seg{b.G(std::string("head.") + HEAD_NAMES[hd] + ".3.weight", nr * HEAD_CH),
+                               b.G(std::string("head.") + HEAD_NAMES[hd] + ".3.bias", nr), rb[hd], nr});
+        }
+        segs.push_back(Seg{b.G("head.dir_cls.0.weight", 12 * HEAD_CH), b.G("head.dir_cls.0.bias", 12), rb[8], 12});
+        segs.push_back(Seg{b.G("head.dir_reg.0.weight", 12 * HEAD_CH), b.G("head.dir_reg.0.bias", 12), rb[8] + 12, 12});
         CopyBatch segcb;
         for (const Seg &s : segs) {
             if (!segcb.add(dw1 + (size_t)s.r0 * HEAD_CH, s.dst_w, (size_t)s.nr * HEAD_CH) || !segcb.add(db1 + s.r0, s.dst_b, s.nr))
@@ -1000,8 +918,8 @@ static TrainState *build_train(mc_handle *h, int B, int H, int W, bool head_only
         const size_t head_wgrad_first = ts->bwd_side.size();
         std::vector<float *> g3w, g3b;
         for (int hd = 0; hd < NUM_HEADS; ++hd) {
-            g3w.push_back(b.G(std::string("head.") + HN[hd] + ".0.weight"));
-            g3b.push_back(b.G(std::string("head.") + HN[hd] + ".0.bias"));
+            g3w.push_back(b.G(std::string("head.") + HEAD_NAMES[hd] + ".0.weight", 9 * HEAD_CH * HEAD_CH));
+            g3b.push_back(b.G(std::string("head.") + HEAD_NAMES[hd] + ".0.bias", HEAD_CH));
         }
         CopyBatch g3cb;
         for (int hd = 0; hd < NUM_HEADS; ++hd) {
@@ -1013,7 +931,7 @@ static TrainState *build_train(mc_handle *h, int B, int H, int W, bool head_only
         ts->bwd_side.resize(ts->bwd.size(), 1);
         // dense OIHW (576,64,3,3) copy of the nine head convs for the dgrad panel
         std::vector<const float *> w3;
-        for (int hd = 0; hd < NUM_HEADS; ++hd) w3.push_back(b.P(std::string("head.") + HN[hd] + ".0.weight"));
+        for (int hd = 0; hd < NUM_HEADS; ++hd) w3.push_back(b.P(std::string("head.") + HEAD_NAMES[hd] + ".0.weight", 9 * HEAD_CH * HEAD_CH));
         CopyBatch w3cb;
         for (int hd = 0; hd < NUM_HEADS; ++hd)
             if (!w3cb.add(w3[hd], w3dense + (size_t)hd * 64 * 64 * 9, (size_t)64 * 64 * 9)) ts->ok = false;
@@ -1054,7 +972,7 @@ static TrainState *build_train(mc_handle *h, int B, int H, int W, bool head_only
             if (!o.ginit) continue;
             if (in.ginit) { ts->ok = false; h->err = "train plan: deconv input has more than one consumer"; }
             const float *xp = in.t.p, *go = o.g, *wp = r.D->wpk, *xla = in.la, *xlb = in.lb;
-            float *gi = b.g_acquire(r.in), *dw = b.G(r.D->name + ".weight");
+            float *gi = b.g_acquire(r.in), *dw = b.G(r.D->name + ".weight", (int64_t)r.D->C * 16);
             const int Bq = in.t.B, Hq = in.t.H, Wq = in.t.W, Cq = in.t.C;
             float *part = b.alloc(deconv4_bwd_w_partial_floats(Bq, Hq, Cq));
             // MONOCON_HIP_DECONV_FUSE=0: the data gradient and the weight gradient of the depthwise deconv as two passes (rounds 1-5)
@@ -1078,9 +996,10 @@ static TrainState *build_train(mc_handle *h, int B, int H, int W, bool head_only
             if (r.dead || !ts->nodes[r.z].ginit) continue;
             Tensor dy = b.bn_backward(r, r.bn);
             ts->bwd_side.resize(ts->bwd.size(), 0);
-            b.emit_wgrad(r.srcs, dy, r.L->cout, r.L->cout, r.L->ks, r.L->stride, b.G(r.L->conv + ".weight"));
+            const int64_t wn = (int64_t)r.L->cout * r.L->cin * r.L->ks * r.L->ks;
+            b.emit_wgrad(r.srcs, dy, r.L->cout, r.L->cout, r.L->ks, r.L->stride, b.G(r.L->conv + ".weight", wn));
             ts->bwd_side.resize(ts->bwd.size(), 1);   // the closure(s) emit_wgrad just added
-            const float *wm = b.P(r.L->conv + ".weight");
+            const float *wm = b.P(r.L->conv + ".weight", wn);
             int c_off = 0;
             for (int s : r.srcs) {
                 b.emit_dgrad(wm, dy, r.L->cout, r.L->cin, r.L->ks, r.L->stride, c_off, s, r.L->cout);
@@ -1097,7 +1016,7 @@ static TrainState *build_train(mc_handle *h, int B, int H, int W, bool head_only
             Tensor dy = b.bn_backward(r, r.bn);
             b.want_skip_affine = false;
             const bool fused = b.did_skip_affine;
-            float *part = b.alloc((size_t)stem_wgrad_blocks(B, H, W) * 147 * 16), *dw = b.G("backbone.base_layer.0.weight");
+            float *part = b.alloc((size_t)stem_wgrad_blocks(B, H, W) * 147 * 16), *dw = b.G("backbone.base_layer.0.weight", 16 * 147);
             const float *dyp = dy.p, *yfp = fused ? r.y.p : nullptr, *cfp = fused ? b.skip_coef : nullptr;
             const unsigned *imax = ts->img_amax, *dymax = dy.amax, *yfmax = fused ? r.y.amax : nullptr;
             ts->bwd_side.resize(ts->bwd.size(), 0);
@@ -1128,7 +1047,7 @@ static TrainState *build_train(mc_handle *h, int B, int H, int W, bool head_only
     if (!ts->ok) return nullptr;
     if (std::getenv("MONOCON_HIP_PLAN_DEBUG"))
         fprintf(stderr, "[plan] lazy activations: %d never stored, %d stored after all (lazy mask %d), %.2f GB\n", b.n_lazy - b.n_materialised,
-                b.n_materialised, b.lazy_mask, ts->bytes * 1e-9);
+                b.n_materialised, b.lazy_mask, ts->mem.bytes * 1e-9);
     if (h->dry_alloc) return tsp.release();   // mc_query_workspace: sizes only
     ts->bwd_side.resize(ts->bwd.size(), 0);
     if (const char *e = std::getenv("MONOCON_HIP_DUAL_STREAM")) ts->dual = std::atoi(e) != 0;
@@ -1170,7 +1089,7 @@ static TrainState *ensure_train_plan(mc_handle *h, int B, int H, int W, bool hea
         ts = build_train(h, B, H, W, head_only);
         if (!ts) return nullptr;
         h->train = ts;
-        h->train_bytes = ts->bytes;
+        h->train_bytes = ts->mem.bytes;
         h->train_free = train_free;
     }
     return ts;
@@ -1247,7 +1166,7 @@ int mc_train_query_workspace(mc_handle *h, int B, int H, int W, int head_only, s
         return fail(h, "mc_query_workspace: bind the parameters (and their \"#grad\" buffers) and call mc_pack_params first");
     TrainState *cur = h->train;
     if (cur && cur->B == B && cur->H == H && cur->W == W && cur->head_only == (head_only != 0) && cur->bind_gen == h->bind_gen) {
-        *bytes = cur->bytes;
+        *bytes = cur->mem.bytes;
         return 0;
     }
     void *ta = h->tgt_arena, *da = h->dp_arena;
@@ -1257,8 +1176,8 @@ int mc_train_query_workspace(mc_handle *h, int B, int H, int W, int head_only, s
     h->dry_alloc = false;
     h->tgt_arena = ta; h->dp_arena = da; h->tgt_arena_bytes = tb; h->dp_arena_bytes = db;   // (the builder points these at its arenas)
     if (!ts) return -1;
-    *bytes = ts->bytes;
-    ts->bufs.clear();
+    *bytes = ts->mem.bytes;
+    ts->mem.bufs.clear();
     train_free(ts);
     return 0;
 }

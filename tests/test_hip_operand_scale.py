@@ -39,7 +39,7 @@ STRESS_SEED = 1234
 
 # ------------------------------------------------------------------------------------------------ the stressed state
 def _bn_of(conv):
-    """BatchNorm behind a train-plan conv (mc_api.hip add_conv)"""
+    """BatchNorm behind a train-plan conv (mc_api.hip build_net)"""
     if conv.endswith(".project.0") or conv.endswith("level0.0") or conv.endswith("level1.0") or conv.endswith("base_layer.0"):
         return conv[:-1] + "1"
     if conv.endswith(".root.conv"):

@@ -263,6 +263,22 @@ def test_query_workspace_predicts_what_the_plans_allocate(golden_sd):
     assert 26e9 < q32 < 34e9, q32      # (45.3 GB before round 3: dY in place over dZ, recycled gradient maps)
 
 
+def test_train_plan_rejects_a_grad_buffer_of_the_wrong_size(golden_sd):
+    """the train plan checks every tensor it binds -- "#grad" buffers included -- for dtype and size: a gradient buffer one
+    element too large (which would keep an unchecked build in bounds) fails the build with an error naming its key"""
+    from hipmonocon.engine import Engine
+    from hipmonocon.lib import MonoconHipError
+    from hipmonocon.train import _binding
+    m = build(golden_sd)
+    st = _binding(m).state(m)
+    key = "backbone.level3.tree1.tree2.conv1.weight#grad"
+    st[key] = torch.zeros(st[key].numel() + 1, device="cuda")
+    eng = Engine(0)
+    eng.bind_state(st)
+    with pytest.raises(MonoconHipError, match=key):
+        eng.build_train_plan(2, 64, 128)
+
+
 def test_recycled_gradient_buffers_do_not_change_a_bit(golden_sd, monkeypatch):
     """round 3: dY in place over dZ + gradient maps from a pool (a buffer last read by the weight-gradient stream is waited for
     before its next first write).  Same kernels, other addresses: losses and every gradient must be bit-identical to the plan
