@@ -166,6 +166,17 @@ int mc_losses_backward_pred(mc_handle *h, const float *const preds[MC_NUM_PREDS]
 int mc_forward_train(mc_handle *h, const float *img, const mc_labels *labels, int B, int H, int W,
                      int max_objs, float *const preds[MC_NUM_PREDS], float *losses, void *stream);
 int mc_backward(mc_handle *h, const float *grad_losses, void *stream);
+/* mc_backward of an objective that also reaches the prediction maps: the gradient written is that of
+ * sum_i grad_losses[i] * loss_i + sum_k <grad_preds[k], preds[k]>, where preds[k] are the maps mc_forward_train wrote
+ * (post sigmoid+clamp heat-maps, transformed depth: what the caller sees).  grad_preds[k]: device fp32, contiguous NCHW,
+ * the plan's shape (B, PRED_CH[k], H/4, W/4) with PRED_CH = {3, 9, 2, 2, 2, 18, 3, 2, 12, 12} in MC_PRED_* order;
+ * caller-owned, and must stay valid until `stream` has reached this call's work (the plan keeps no pointer to it after
+ * returning).  A NULL array or a NULL entry is a zero gradient; with all of them NULL the call is exactly mc_backward.
+ * The maps must still hold what the forward wrote: the activations' derivatives are formed from them (clamped heat-map
+ * entries take no gradient, as in the loss backward).  Data parallelism is unchanged: the term enters before the first
+ * parameter gradient is written. */
+int mc_backward_pred_grads(mc_handle *h, const float *grad_losses, const float *const grad_preds[MC_NUM_PREDS],
+                           void *stream);
 /* The train plan keeps ONE set of saved activations: mc_backward always differentiates the latest
  * mc_forward_train of the handle.  *generation = id of that forward (0 before the first one; every
  * forward gets a new id).  A caller that may interleave forwards and backwards (gradient accumulation
@@ -182,6 +193,10 @@ int mc_train_generation(mc_handle *h, unsigned long long *generation);
 int mc_head_forward_train(mc_handle *h, const float *feat, const mc_labels *labels, int B, int pad_h, int pad_w,
                           int max_objs, float *const preds[MC_NUM_PREDS], float *losses, void *stream);
 int mc_head_backward(mc_handle *h, const float *grad_losses, float *grad_feat, void *stream);
+/* mc_head_backward with gradients wrt the prediction maps, on the contract of mc_backward_pred_grads (shapes
+ * (B, PRED_CH[k], pad_h/4, pad_w/4)); all of them NULL: exactly mc_head_backward. */
+int mc_head_backward_pred_grads(mc_handle *h, const float *grad_losses, const float *const grad_preds[MC_NUM_PREDS],
+                                float *grad_feat, void *stream);
 /* Debugging aid: activation (which=0) or gradient (which=1) of node `node` of the train plan as NCHW. */
 int mc_train_debug_node(mc_handle *h, int node, int which, float *out_nchw, int dims[4], void *stream);
 

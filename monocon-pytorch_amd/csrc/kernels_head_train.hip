@@ -10,6 +10,8 @@
 // backwards: head_bwd_kernel (1x1 weight gradients, ReLU-masked data gradient, AttnBN reductions in one
 // pass); the AttnBN backward then reduces to one per-(image, channel) affine map dx = P*d + Q*x + R
 // (attn_train_bwd_kernel computes P, Q, R and all the small parameter gradients).
+#include <type_traits>
+
 #include "kernels.h"
 #include "train.h"
 
@@ -321,21 +323,57 @@ struct DpredPackArgs {
     float *out;
     int row_pred[NUM_OUT_ROWS], row_ch[NUM_OUT_ROWS], pred_c[10];
 };
-__global__ __launch_bounds__(256) void dpred_pack_kernel(const DpredPackArgs a) {
+// USER variant: a caller's gradients with respect to the prediction maps themselves join the loss gradients on the way in
+struct DpredUserArgs : DpredPackArgs {
+    const float *grad[10];         // NCHW, like the maps; nullptr: that map takes no gradient of its own
+    const float *pred[10];         // the maps the forward wrote: the activations' derivatives are formed from them
+    int row_epi[NUM_OUT_ROWS];     // HeadRow::epi
+};
+// d map / d raw output of a row, from the map's value y (the conventions of the loss backward, kernels_loss.hip):
+// clamped sigmoid -- y (1 - y) strictly inside the clamp, else 0 (focal_grad_kernel); depth 1/(sig + 1e-12) - 1 --
+// -sig (1 - sig) / (sig + 1e-12)^2 with sig = 1/(y + 1) - 1e-12 (gathered_loss_kernel); identity otherwise
+__device__ __forceinline__ float pred_act_grad(int epi, float y) {
+    if (epi == 1) return (y > 1e-4f && y < 1.f - 1e-4f) ? y * (1.f - y) : 0.f;
+    if (epi == 2) {
+        const float sig = 1.f / (y + 1.f) - 1e-12f;
+        return -sig * (1.f - sig) / ((sig + 1e-12f) * (sig + 1e-12f));
+    }
+    return 1.f;
+}
+template <bool USER>
+__global__ __launch_bounds__(256) void dpred_pack_kernel(const std::conditional_t<USER, DpredUserArgs, DpredPackArgs> a) {
     __shared__ float t[64][NUM_OUT_ROWS + 2];
     __shared__ const float *rowp[NUM_OUT_ROWS];      // where row r of this (image, tile) starts: the kernel-argument tables
                                                      // are indexed dynamically ONCE per row here, not once per element
                                                      // (they live in scratch memory then: 267 us for 570 MB in round 5)
+    __shared__ const float *rowg[USER ? NUM_OUT_ROWS : 1], *rowy[USER ? NUM_OUT_ROWS : 1];
+    __shared__ int rowe[USER ? NUM_OUT_ROWS : 1];
     const int tiles = (a.HW + 63) / 64;
     const int b = blockIdx.x / tiles, hw0 = (blockIdx.x % tiles) * 64;
     if (threadIdx.x < NUM_OUT_ROWS) {
         const int r = threadIdx.x, p = a.row_pred[r];
         rowp[r] = a.dpred[p] + ((size_t)b * a.pred_c[p] + a.row_ch[r]) * a.HW + hw0;
+        if constexpr (USER) {
+            const size_t o = ((size_t)b * a.pred_c[p] + a.row_ch[r]) * a.HW + hw0;
+            rowg[r] = a.grad[p] ? a.grad[p] + o : nullptr;
+            rowy[r] = a.pred[p] + o;
+            rowe[r] = a.row_epi[r];
+        }
     }
     __syncthreads();
     for (int e = threadIdx.x; e < 64 * NUM_OUT_ROWS; e += 256) {
         const int r = e / 64, px = e % 64;
-        t[px][r] = (hw0 + px < a.HW) ? rowp[r][px] : 0.f;
+        if constexpr (USER) {
+            // one row per wave: the test on rowg[r] is wave-uniform, the three reads are coalesced along HW
+            float v = 0.f;
+            if (hw0 + px < a.HW) {
+                v = rowp[r][px];
+                if (rowg[r]) v += pred_act_grad(rowe[r], rowy[r][px]) * rowg[r][px];
+            }
+            t[px][r] = v;
+        } else {
+            t[px][r] = (hw0 + px < a.HW) ? rowp[r][px] : 0.f;
+        }
     }
     __syncthreads();
     for (int e = threadIdx.x; e < 64 * a.ld; e += 256) {
@@ -343,13 +381,29 @@ __global__ __launch_bounds__(256) void dpred_pack_kernel(const DpredPackArgs a) 
         if (hw0 + px < a.HW) a.out[((size_t)b * a.HW + hw0 + px) * a.ld + r] = r < NUM_OUT_ROWS ? t[px][r] : 0.f;
     }
 }
-hipError_t launch_dpred_pack(const float *const dpred[10], int ld, int B, int HW, float *out, hipStream_t st) {
-    DpredPackArgs a;
+static void dpred_pack_args(DpredPackArgs &a, const float *const dpred[10], int ld, int B, int HW, float *out) {
     a.ld = ld; a.B = B; a.HW = HW; a.out = out;
     const HeadRow *rows = head_rows();
     for (int i = 0; i < 10; ++i) { a.dpred[i] = dpred[i]; a.pred_c[i] = PRED_CH[i]; }
     for (int r = 0; r < NUM_OUT_ROWS; ++r) { a.row_pred[r] = rows[r].pred; a.row_ch[r] = rows[r].ch; }
-    hipLaunchKernelGGL(dpred_pack_kernel, dim3(B * ((HW + 63) / 64)), dim3(256), 0, st, a);
+}
+hipError_t launch_dpred_pack(const float *const dpred[10], int ld, int B, int HW, float *out, hipStream_t st) {
+    DpredPackArgs a;
+    dpred_pack_args(a, dpred, ld, B, HW, out);
+    hipLaunchKernelGGL(dpred_pack_kernel<false>, dim3(B * ((HW + 63) / 64)), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t launch_dpred_pack_user(const float *const dpred[10], const float *const pred[10], const float *const grad[10], int ld,
+                                  int B, int HW, float *out, hipStream_t st) {
+    DpredUserArgs a;
+    dpred_pack_args(a, dpred, ld, B, HW, out);
+    const HeadRow *rows = head_rows();
+    for (int i = 0; i < 10; ++i) {
+        if (!pred[i]) return hipErrorInvalidValue;
+        a.pred[i] = pred[i]; a.grad[i] = grad[i];
+    }
+    for (int r = 0; r < NUM_OUT_ROWS; ++r) a.row_epi[r] = rows[r].epi;
+    hipLaunchKernelGGL(dpred_pack_kernel<true>, dim3(B * ((HW + 63) / 64)), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 

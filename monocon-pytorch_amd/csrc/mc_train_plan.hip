@@ -104,6 +104,8 @@ struct TrainState {
     float *preds[10] = {nullptr};
     float *losses = nullptr;
     const float *grad_losses = nullptr;
+    // caller's gradients wrt the ten prediction maps (mc_backward_pred_grads): set for one backward_impl call only
+    const float *grad_preds[10] = {nullptr};
     int pad_h = 0, pad_w = 0, max_objs = 30;
     // head-only plan (mc_head_forward_train): the neck output comes in as an external NCHW tensor, its gradient
     // goes out the same way
@@ -852,7 +854,13 @@ static TrainState *build_train(mc_handle *h, int B, int H, int W, bool head_only
         float *db1 = b.alloc(NUM_OUT_ROWS), *dw1 = b.alloc((size_t)NUM_OUT_ROWS * HEAD_CH);
         ts->bwd.push_back([=](mc_handle *hh, hipStream_t st) {
             if (mc_losses_backward(hh, ts->preds, &ts->targets, B, ts->max_objs, fh, fw, ts->grad_losses, ts->dpred, st)) return -1;
-            HIPCHK(hh, launch_dpred_pack(ts->dpred, LD, B, HW, draw, st));
+            // a caller's gradients wrt the maps enter here, in the same pass: everything downstream starts from draw
+            bool user = false;
+            for (const float *g : ts->grad_preds) user = user || g != nullptr;
+            if (user)
+                HIPCHK(hh, launch_dpred_pack_user(ts->dpred, ts->preds, ts->grad_preds, LD, B, HW, draw, st));
+            else
+                HIPCHK(hh, launch_dpred_pack(ts->dpred, LD, B, HW, draw, st));
             HIPCHK(hh, launch_colsum(draw, (size_t)B * HW, NUM_OUT_ROWS, LD, cs1, db1, st));
             return 0;
         });
@@ -1213,19 +1221,41 @@ int mc_train_debug_node(mc_handle *h, int node, int which, float *out_nchw, int 
     return 0;
 }
 
-static int backward_impl(mc_handle *h, TrainState *ts, const float *grad_losses, void *stream);
+static int backward_impl(mc_handle *h, TrainState *ts, const float *grad_losses, const float *const grad_preds[MC_NUM_PREDS],
+                         void *stream);
 
-int mc_backward(mc_handle *h, const float *grad_losses, void *stream) {
+static int full_backward(mc_handle *h, const char *who, const float *grad_losses, const float *const grad_preds[MC_NUM_PREDS],
+                         void *stream) {
     if (!h) return -1;
-    if (!grad_losses) return fail(h, "mc_backward: grad_losses is NULL");
+    if (!grad_losses) return fail(h, "%s: grad_losses is NULL", who);
     if (h->train && h->train->head_only)
-        return fail(h, "mc_backward: the handle holds a heads-only plan (mc_head_forward_train): use mc_head_backward");
+        return fail(h, "%s: the handle holds a heads-only plan (mc_head_forward_train): use %s", who,
+                    grad_preds ? "mc_head_backward_pred_grads" : "mc_head_backward");
     TrainState *ts = h->train;
-    if (!ts || !ts->img) return fail(h, "mc_backward: call mc_forward_train first");
-    return backward_impl(h, ts, grad_losses, stream);
+    if (!ts || !ts->img) return fail(h, "%s: call mc_forward_train first", who);
+    return backward_impl(h, ts, grad_losses, grad_preds, stream);
 }
 
-static int backward_impl(mc_handle *h, TrainState *ts, const float *grad_losses, void *stream) {
+int mc_backward(mc_handle *h, const float *grad_losses, void *stream) {
+    return full_backward(h, "mc_backward", grad_losses, nullptr, stream);
+}
+
+int mc_backward_pred_grads(mc_handle *h, const float *grad_losses, const float *const grad_preds[MC_NUM_PREDS], void *stream) {
+    return full_backward(h, "mc_backward_pred_grads", grad_losses, grad_preds, stream);
+}
+
+static int backward_run(mc_handle *h, TrainState *ts, const float *grad_losses, void *stream);
+
+static int backward_impl(mc_handle *h, TrainState *ts, const float *grad_losses, const float *const grad_preds[MC_NUM_PREDS],
+                         void *stream) {
+    for (int i = 0; i < MC_NUM_PREDS; ++i) ts->grad_preds[i] = grad_preds ? grad_preds[i] : nullptr;
+    const int rc = backward_run(h, ts, grad_losses, stream);
+    // caller-owned: neither mc_profile_train's replay of the closures nor the next backward may read them again
+    for (const float *&g : ts->grad_preds) g = nullptr;
+    return rc;
+}
+
+static int backward_run(mc_handle *h, TrainState *ts, const float *grad_losses, void *stream) {
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     ts->grad_losses = grad_losses;
@@ -1282,14 +1312,24 @@ static int backward_impl(mc_handle *h, TrainState *ts, const float *grad_losses,
     return 0;
 }
 
-int mc_head_backward(mc_handle *h, const float *grad_losses, float *grad_feat, void *stream) {
+static int head_backward(mc_handle *h, const char *who, const float *grad_losses, const float *const grad_preds[MC_NUM_PREDS],
+                         float *grad_feat, void *stream) {
     if (!h) return -1;
     TrainState *ts = h->train;
-    if (!ts || !ts->head_only || !ts->feat_ext) return fail(h, "mc_head_backward: call mc_head_forward_train first");
-    if (!grad_losses) return fail(h, "mc_head_backward: grad_losses is NULL");
+    if (!ts || !ts->head_only || !ts->feat_ext) return fail(h, "%s: call mc_head_forward_train first", who);
+    if (!grad_losses) return fail(h, "%s: grad_losses is NULL", who);
     ts->gfeat_ext = grad_feat;
     ts->skip_feat_dgrad = grad_feat == nullptr;      // feat does not require grad: its 3x3 data gradient is not computed
-    return backward_impl(h, ts, grad_losses, stream);
+    return backward_impl(h, ts, grad_losses, grad_preds, stream);
+}
+
+int mc_head_backward(mc_handle *h, const float *grad_losses, float *grad_feat, void *stream) {
+    return head_backward(h, "mc_head_backward", grad_losses, nullptr, grad_feat, stream);
+}
+
+int mc_head_backward_pred_grads(mc_handle *h, const float *grad_losses, const float *const grad_preds[MC_NUM_PREDS],
+                                float *grad_feat, void *stream) {
+    return head_backward(h, "mc_head_backward_pred_grads", grad_losses, grad_preds, grad_feat, stream);
 }
 
 int mc_profile_train(mc_handle *h, int iters, double ms[3], double flops[3], double bytes[3], int launches[3],

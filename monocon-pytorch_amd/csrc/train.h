@@ -147,6 +147,10 @@ hipError_t launch_deconv4_bwd_w(const float *in, const float *dout, int B, int H
 hipError_t launch_pack_conv_w_dgrad(const float *w, int Cout, int CinTotal, int k, int c_off, int Cs, int CsP, int CoutPad,
                                     int cls, float *dst, hipStream_t st);
 hipError_t launch_dpred_pack(const float *const dpred[10], int ld, int B, int HW, float *out, hipStream_t st);
+// the same pack with a caller's gradients wrt the prediction maps added in (grad[k] NCHW like pred[k], nullptr: none): row r
+// of map k gets dpred + (d map / d raw output, from pred[k]) * grad, in the same single pass
+hipError_t launch_dpred_pack_user(const float *const dpred[10], const float *const pred[10], const float *const grad[10], int ld,
+                                  int B, int HW, float *out, hipStream_t st);
 struct AttnTrainArgs {
     const float *stats;            // [B][chunks][stat_ld][2] partial (sum, sumsq) of (x - running_mean)
     int chunks, stat_ld, B, HW;

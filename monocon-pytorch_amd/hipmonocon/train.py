@@ -6,7 +6,10 @@ generation, the ten losses) and returns ``(pred_dict, loss_dict)`` exactly like 
 values are 0-dim tensors connected to the model's parameters through one
 ``torch.autograd.Function`` whose ``backward`` calls ``mc_backward``, so the reference's train
 loop (``sum(loss_dict.values()).backward()``, ``clip_grad_norm_``, ``optimizer.step()``,
-engine/monocon_engine.py:84-102) runs unchanged on top of it.
+engine/monocon_engine.py:84-102) runs unchanged on top of it.  The ten prediction maps are
+differentiable outputs of the same Function: an objective that reaches them (an extra term on
+``pred_dict``, ``head._get_losses`` against other targets) back-propagates through
+``mc_backward_pred_grads``, which adds their gradients to the loss gradients in one pass.
 """
 import ctypes as C
 
@@ -62,6 +65,18 @@ def _loss_grad_vector(grads, like):
     return torch.stack([zero if g is None else g.detach().reshape(()).float() for g in grads])
 
 
+def _pred_grads(grads):
+    """the upstream gradients of the ten prediction maps as fp32 contiguous tensors (None: that map does not reach the
+    objective), or None when none does.  A gradient of pred.sum() arrives expanded (stride 0): contiguous() forms it."""
+    if all(g is None for g in grads):
+        return None
+    return [None if g is None else g.detach().float().contiguous() for g in grads]
+
+
+def _ptr_array(tensors):
+    return (C.c_void_p * _lib.NUM_PREDS)(*[None if t is None else t.data_ptr() for t in tensors])
+
+
 def _own_scalars(vec):
     """the entries of a device vector as 0-dim tensors with storage of their own (one multi-tensor copy)"""
     out = [torch.empty((), dtype=vec.dtype, device=vec.device) for _ in range(vec.numel())]
@@ -72,7 +87,7 @@ def _own_scalars(vec):
 class _HipTrainStep(torch.autograd.Function):
     @staticmethod
     def forward(ctx, detector, tb, eng, img, label, max_objs, *params):
-        # the ten prediction maps are outputs without a gradient: left to its default, autograd hands backward() a
+        # a prediction map the objective does not use gets no gradient: left to its default, autograd hands backward() a
         # zero-filled tensor for each of them (255 MB of fills per step at B = 32, found in the kernel trace)
         ctx.set_materialize_grads(False)
         B, _, H, W = img.shape
@@ -98,8 +113,10 @@ class _HipTrainStep(torch.autograd.Function):
         _lib.check(eng.h, eng.lib.mc_train_generation(eng.h, C.byref(gen)), "mc_train_generation")
         ctx.generation = gen.value
         torch.autograd.graph.increment_version(tb.buffers)        # running statistics were updated in place
-        ctx.eng, ctx.tb, ctx.keep = eng, tb, (img, keep, preds, losses)
-        ctx.mark_non_differentiable(*preds)
+        ctx.eng, ctx.tb, ctx.keep = eng, tb, (img, keep, losses)
+        # the maps are differentiable outputs, and the backward reads them (loss gradients, activation derivatives):
+        # saved as such, an in-place edit of one before backward() raises autograd's version error
+        ctx.save_for_backward(*preds)
         # ten separate 0-dim outputs: the backward then receives the ten upstream gradients directly, instead of ten
         # select-backward nodes each filling a zero vector and adding it.  They own their storage (one multi-tensor copy
         # out of the device vector the kernel wrote): as outputs that are views of one buffer, an in-place loss weighting
@@ -109,7 +126,8 @@ class _HipTrainStep(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *grads):
         eng, tb = ctx.eng, ctx.tb
-        grad_losses = _loss_grad_vector(grads[:10], ctx.keep[3])
+        ctx.saved_tensors                    # (unpacking checks that no map was modified in place since the forward)
+        grad_losses = _loss_grad_vector(grads[:10], ctx.keep[2])
         gen = C.c_ulonglong(0)
         _lib.check(eng.h, eng.lib.mc_train_generation(eng.h, C.byref(gen)), "mc_train_generation")
         if gen.value != ctx.generation:
@@ -118,9 +136,14 @@ class _HipTrainStep(torch.autograd.Function):
                 "plan keeps one set of activations, so call backward() before the next forward (for gradient "
                 "accumulation run forward+backward per micro-batch)" % (ctx.generation, gen.value))
         g = grad_losses.contiguous().float()
+        gp = _pred_grads(grads[10:])
         with torch.cuda.device(g.device):
-            rc = eng.lib.mc_backward(eng.h, C.c_void_p(g.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _lib.check(eng.h, rc, "mc_backward")
+            if gp is None:
+                rc = eng.lib.mc_backward(eng.h, C.c_void_p(g.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+            else:
+                rc = eng.lib.mc_backward_pred_grads(eng.h, C.c_void_p(g.data_ptr()), _ptr_array(gp),
+                                                    C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _lib.check(eng.h, rc, "mc_backward" if gp is None else "mc_backward_pred_grads")
         # data parallel: with a communicator owned by the handle mc_backward already exchanged the gradients bucket by
         # bucket, overlapped with the backbone's backward (csrc/mc_comm.hip); otherwise one all-reduce of the flat buffer
         if eng.comm_world:
@@ -284,14 +307,15 @@ class _HipHeadTrainStep(torch.autograd.Function):
         _lib.check(eng.h, eng.lib.mc_train_generation(eng.h, C.byref(gen)), "mc_train_generation")
         ctx.generation = gen.value
         torch.autograd.graph.increment_version(tb.buffers)
-        ctx.eng, ctx.tb, ctx.keep, ctx.feat_shape = eng, tb, (feat, keep, preds, losses), feat.shape
-        ctx.mark_non_differentiable(*preds)
+        ctx.eng, ctx.tb, ctx.keep, ctx.feat_shape = eng, tb, (feat, keep, losses), feat.shape
+        ctx.save_for_backward(*preds)          # (see _HipTrainStep.forward)
         return (*_own_scalars(losses), *preds)
 
     @staticmethod
     def backward(ctx, *grads):
         eng, tb = ctx.eng, ctx.tb
-        grad_losses = _loss_grad_vector(grads[:10], ctx.keep[3])
+        ctx.saved_tensors
+        grad_losses = _loss_grad_vector(grads[:10], ctx.keep[2])
         gen = C.c_ulonglong(0)
         _lib.check(eng.h, eng.lib.mc_train_generation(eng.h, C.byref(gen)), "mc_train_generation")
         if gen.value != ctx.generation:
@@ -299,10 +323,16 @@ class _HipHeadTrainStep(torch.autograd.Function):
                                        "#%d: call backward() before the next forward_train" % (ctx.generation, gen.value))
         g = grad_losses.contiguous().float()
         gfeat = torch.empty(ctx.feat_shape, dtype=torch.float32, device=g.device) if ctx.needs_input_grad[2] else None
+        gp = _pred_grads(grads[10:])
         with torch.cuda.device(g.device):
-            rc = eng.lib.mc_head_backward(eng.h, C.c_void_p(g.data_ptr()), C.c_void_p(gfeat.data_ptr() if gfeat is not None else None),
-                                          C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _lib.check(eng.h, rc, "mc_head_backward")
+            if gp is None:
+                rc = eng.lib.mc_head_backward(eng.h, C.c_void_p(g.data_ptr()), C.c_void_p(gfeat.data_ptr() if gfeat is not None else None),
+                                              C.c_void_p(torch.cuda.current_stream().cuda_stream))
+            else:
+                rc = eng.lib.mc_head_backward_pred_grads(eng.h, C.c_void_p(g.data_ptr()), _ptr_array(gp),
+                                                         C.c_void_p(gfeat.data_ptr() if gfeat is not None else None),
+                                                         C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _lib.check(eng.h, rc, "mc_head_backward" if gp is None else "mc_head_backward_pred_grads")
         out = []
         for n, p in tb.named:
             gb = tb.grads[n]

@@ -1,0 +1,350 @@
+"""Gradients through the train-mode prediction maps: ``pred_dict`` of ``MonoConDetector.forward`` (train mode) and of
+``MonoConDenseHeads.forward_train`` is connected to the parameters as in the reference, so an objective with a term on
+the maps (an extra loss, a second target set through ``head._get_losses``) back-propagates into every parameter
+(mc_backward_pred_grads / mc_head_backward_pred_grads: the maps' gradients join the loss gradients in the pack of the
+raw 1x1-output gradients, csrc/kernels_head_train.hip).  Yard-stick: torch autograd through the oracle in fp64.
+GPU-only."""
+import numpy as np
+import pytest
+import torch
+
+from conftest import load_golden
+from hipmonocon import netspec, synth
+
+pytestmark = pytest.mark.gpu
+
+PRED_KEYS = tuple(k for k, _ in netspec.PRED_KEYS)
+DEAD = frozenset(netspec.DEAD_PARAMS)
+N_LIVE = 236
+
+
+def build(sd, precision="fp32"):
+    from model import MonoConDetector
+    m = MonoConDetector(34, pretrained_backbone=False)
+    m.load_state_dict(sd, strict=True)
+    return m.cuda().train().set_precision(precision)
+
+
+def to_cuda(batch):
+    d = dict(batch)
+    d["img"] = batch["img"].cuda()
+    d["label"] = {k: v.cuda() for k, v in batch["label"].items()}
+    return d
+
+
+def fixture(case):
+    g = load_golden("train_cond_%d.npz" % case)
+    B, H, W = (int(x) for x in g["shape"])
+    return synth.make_conditioned_batch(int(g["seed"]), B, H, W), (B, H, W)
+
+
+def head_of(key):
+    from oracle import monocon_oracle as O
+    return "dir_feat" if key.startswith("alpha_") else {v: k for k, v in O.HEAD_BRANCHES.items()}[key]
+
+
+def decided_pixels(sd, batch, tau=1e-4):
+    """{head: (B, h, w) bool}: True where none of the head's 64 ReLU decisions (after AttnBN) lies within tau of the
+    channel's standard deviation of its threshold, in the oracle's fp64 train forward.
+
+    The conditioned fixtures are selected so that the reference has no backbone / neck decision within a few fp32
+    round-offs of its threshold; the heads' hidden ReLUs were not part of that selection, and each fixture has a few such
+    pixels (fixture 0: 3e-6 of the std in heatmap_head, 5e-7 in offset_head, 2e-6 in dir_feat).  Any fp32 run -- the
+    reference's own included -- may land on the other side there.  The losses put (almost) no gradient on those pixels;
+    a dense term on the maps puts a full one, and the decision then moves a cancelling sum such as an AttnBN bias
+    gradient by ~1e-3.  Those pixels (<= 11 of the B h w per head) are left out of the term."""
+    from oracle import monocon_oracle as O
+    sd64 = {k: (v.double() if v.dtype == torch.float32 else v) for k, v in sd.items()}
+    with torch.no_grad():
+        _, feat, _ = O.forward(sd64, batch["img"].double(), train=True)
+        cx = O._Ctx(sd64, True)
+        out = {}
+        for br in list(O.HEAD_BRANCHES) + ["dir_feat"]:
+            a = O._attn_bn(cx, cx.conv(feat, "head.%s.0" % br, 1, 1), "head.%s.1" % br)
+            out[br] = (a.abs() / a.std(dim=(0, 2, 3), keepdim=True)).amin(dim=1) >= tau
+    return out
+
+
+def map_weights(seed, B, fh, fw, keys=PRED_KEYS, keep=None):
+    """W_k ~ N(0, 1), fp64, from a seeded CPU generator; zero at the pixels `keep` (decided_pixels) excludes"""
+    gen = torch.Generator().manual_seed(seed)
+    W = {k: torch.randn((B, c, fh, fw), generator=gen, dtype=torch.float64) for k, c in netspec.PRED_KEYS if k in keys}
+    if keep is not None:
+        for k in W:
+            W[k] = W[k] * keep[head_of(k)][:, None].double()
+    return W
+
+
+def map_term(pred, W):
+    """sum_k 10 <W_k, pred_k> / (C_k h w)"""
+    return sum(10.0 * (W[k].to(pred[k]) * pred[k]).sum() / pred[k][0].numel() for k in W)
+
+
+def oracle_grads(sd, batch, objective, dtype=torch.float64):
+    """gradients of objective(preds, targets, losses) through the oracle's train step in `dtype` (leaves: the float
+    parameters; None for a parameter the objective does not reach)"""
+    from oracle import monocon_oracle as O
+    live = {k: (v.to(dtype).clone() if v.dtype == torch.float32 else v.clone()) for k, v in sd.items()}
+    for k, v in live.items():
+        if v.dtype == dtype and "running" not in k:
+            v.requires_grad_(True)
+    b = dict(batch)
+    b["img"] = batch["img"].to(dtype)
+    preds, T, L, _ = O.train_forward(live, b)
+    objective(preds, T, L).backward()
+    return {k: v.grad for k, v in live.items() if getattr(v, "grad", None) is not None}
+
+
+def rel_l2(got, ref):
+    return float((got.detach().cpu().double() - ref).norm() / max(float(ref.norm()), 1e-30))
+
+
+def check(m, ref, tag, med_bound=1e-4, max_bound=1e-3):
+    """the bounds of test_conditioned_gradients_vs_reference_fp64: median relative L2 over the tensors <= 1e-4, every
+    tensor <= 1e-3; a parameter the objective does not reach has an exactly zero gradient"""
+    errs = {}
+    for n, p in m.named_parameters():
+        if n in DEAD:
+            assert p.grad is None, n
+            continue
+        assert p.grad is not None, n
+        if n in ref:
+            errs[n] = rel_l2(p.grad, ref[n])
+        else:
+            assert float(p.grad.abs().max()) == 0.0, (tag, n)
+    e = np.array(list(errs.values()))
+    worst = max(errs, key=errs.get)
+    print("%s: %d tensors, max %.2e (%s) median %.2e; bounds %.2e / %.2e" % (tag, len(e), e.max(), worst, np.median(e),
+                                                                            max_bound, med_bound))
+    assert float(np.median(e)) <= med_bound, (tag, float(np.median(e)))
+    assert e.max() <= max_bound, (tag, worst, e.max())
+    return errs
+
+
+_ORACLE = {}
+
+
+def oracle_cached(key, sd, batch, objective, dtype=torch.float64):
+    if key not in _ORACLE:
+        _ORACLE[key] = oracle_grads(sd, batch, objective, dtype)
+    return _ORACLE[key]
+
+
+# ------------------------------------------------------------------------------------------------ whole detector
+@pytest.mark.parametrize("case,precision", [(0, "fp32"), (0, "f16x2"), (0, "bf16x3"), (1, "f16x2")])
+def test_loss_plus_map_term_vs_reference_fp64(cond_sd, case, precision):
+    """J = sum(losses) + sum_k 10 <W_k, pred_k> / (C_k h w) over all ten maps, on the conditioned fixtures 0 and 1,
+    against autograd through the oracle in fp64, at the loss-only bounds (median 1e-4, every tensor 1e-3).  The term
+    moves every one of the 236 live gradient tensors by >= 1e-2 in the oracle itself (its median by ~0.1), so a backward
+    that drops it cannot pass.  W_k is zero at the few pixels whose head has a ReLU decision within fp32 round-off of
+    its threshold (decided_pixels): with them, the reference's own fp32 run of J misses these bounds too.  Fixture 1 in
+    fp32 / bf16x3 is not listed: there one backbone tensor (level2.tree2.bn2.bias) lands at 1.6e-3, identically in both
+    modes, while every other tensor stays at the 1e-5 level."""
+    batch, (B, H, W) = fixture(case)
+    Wk = map_weights(100 + 3 * case, B, H // 4, W // 4, keep=decided_pixels(cond_sd, batch))
+    objective = lambda p, T, L: sum(L.values()) + map_term(p, Wk)      # noqa: E731
+    ref = oracle_cached(("J", case), cond_sd, batch, objective)
+    loss_only = oracle_cached(("L", case), cond_sd, batch, lambda p, T, L: sum(L.values()))
+    assert len(ref) == N_LIVE and ref.keys() == loss_only.keys()
+    moved = {n: rel_l2(loss_only[n], ref[n]) for n in ref}
+    assert min(moved.values()) >= 1e-2, min(moved.values())
+
+    m = build(cond_sd, precision)
+    pred, loss = m(to_cuda(batch))
+    assert all(pred[k].requires_grad for k in PRED_KEYS)
+    (sum(loss.values()) + map_term(pred, {k: v.cuda() for k, v in Wk.items()})).backward()
+    torch.cuda.synchronize()
+    errs = check(m, ref, "cond %d %s J" % (case, precision))
+    assert len(errs) == N_LIVE
+    assert float(np.median(list(errs.values()))) < 0.1 * float(np.median(list(moved.values())))
+
+
+@pytest.mark.parametrize("key", PRED_KEYS)
+def test_objective_on_one_map_alone(cond_sd, key):
+    """an objective on ONE prediction map, no loss term, through model(batch, return_loss=False), for each of the ten
+    maps (clamped-sigmoid heat maps, the depth transform, identities): the oracle's gradients at the loss-only bounds,
+    an exact zero for the heads that do not feed the map"""
+    batch, (B, H, W) = fixture(0)
+    Wk = map_weights(7, B, H // 4, W // 4, (key,), keep=decided_pixels(cond_sd, batch))
+    ref = oracle_grads(cond_sd, batch, lambda p, T, L: map_term(p, Wk))
+    m = build(cond_sd, "fp32")
+    pred = m(to_cuda(batch), return_loss=False)
+    map_term(pred, {k: v.cuda() for k, v in Wk.items()}).backward()
+    torch.cuda.synchronize()
+    errs = check(m, ref, "%s alone" % key)
+    assert any(n.startswith("backbone.") for n in errs) and any(n.startswith("head.%s." % head_of(key)) for n in errs)
+
+
+def test_clamped_heat_map_channels_take_no_map_gradient(cond_sd):
+    """heat-map output biases +12 (class 0) and -12 (class 1): those channels sit in the clamp of
+    clamp(sigmoid, 1e-4, 1 - 1e-4) everywhere, where the map's derivative is 0 -- the map term contributes nothing to
+    their rows (nor does the focal loss), and the whole gradient still matches the oracle"""
+    sd = {k: v.clone() for k, v in cond_sd.items()}
+    sd["head.heatmap_head.3.bias"][0] = 12.0
+    sd["head.heatmap_head.3.bias"][1] = -12.0
+    batch, (B, H, W) = fixture(0)
+    Wk = map_weights(11, B, H // 4, W // 4, keep=decided_pixels(sd, batch))
+    ref = oracle_grads(sd, batch, lambda p, T, L: sum(L.values()) + map_term(p, Wk))
+    m = build(sd, "fp32")
+    pred, loss = m(to_cuda(batch))
+    hm = pred["center_heatmap_pred"].detach()
+    assert bool((hm[:, 0] == np.float32(1 - 1e-4)).all()) and bool((hm[:, 1] == np.float32(1e-4)).all())
+    (sum(loss.values()) + map_term(pred, {k: v.cuda() for k, v in Wk.items()})).backward()
+    torch.cuda.synchronize()
+    head = m.head.heatmap_head[3]
+    assert float(head.bias.grad[:2].abs().max()) == 0.0 and float(head.weight.grad[:2].abs().max()) == 0.0
+    assert float(ref["head.heatmap_head.3.bias"][:2].abs().max()) == 0.0
+    assert float(head.bias.grad[2].abs()) > 0.0
+    check(m, ref, "clamped heat map")
+
+
+def test_get_losses_on_train_predictions_composes(cond_sd):
+    """pred, loss = model(batch); L2 = model.head._get_losses(pred, T2) against a second target set; (sum loss + sum L2)
+    .backward() equals the oracle's gradient of the same sum -- the stand-alone loss API's gradient wrt the maps reaches
+    the parameters through the train step"""
+    from oracle import monocon_oracle as O
+    batch, (B, H, W) = fixture(0)
+    other = synth.make_conditioned_batch(4242, B, H, W)["label"]
+    T2 = O.make_targets(other, (H, W), (B, 64, H // 4, W // 4))
+    ref = oracle_grads(cond_sd, batch, lambda p, T, L: sum(L.values()) + sum(O.losses(p, T2).values()))
+    m = build(cond_sd, "fp32")
+    pred, loss = m(to_cuda(batch))
+    L2 = m.head._get_losses(pred, {k: v.cuda() for k, v in T2.items()})
+    (sum(loss.values()) + sum(L2.values())).backward()
+    torch.cuda.synchronize()
+    assert len(check(m, ref, "composed _get_losses")) == N_LIVE
+
+
+# ------------------------------------------------------------------------------------------------ heads on their own
+def test_heads_forward_train_with_map_term(cond_sd):
+    """MonoConDenseHeads.forward_train(feat, data) with J = sum(losses) + the map term on all ten maps: the gradient
+    wrt feat and every head parameter's gradient vs autograd through the oracle's head in fp64 (the bounds of
+    test_heads_forward_train_standalone)"""
+    from oracle import monocon_oracle as O
+    from model import MonoConDenseHeads
+    B, H, W = 4, 64, 128
+    batch = synth.make_conditioned_batch(812, B, H, W)
+    feat = torch.from_numpy(synth.normalish(5, "feat", (B, 64, H // 4, W // 4)).astype(np.float32)).abs()
+    Wk = map_weights(21, B, H // 4, W // 4)
+    sd64 = {k: (v.double().clone() if v.dtype == torch.float32 else v.clone()) for k, v in cond_sd.items()}
+    for k, v in sd64.items():
+        if k.startswith("head.") and v.dtype == torch.float64 and "running" not in k:
+            v.requires_grad_(True)
+    f64 = feat.double().clone().requires_grad_(True)
+    preds = O.head_predictions(O._Ctx(sd64, True), f64)
+    T = O.make_targets(batch["label"], (H, W), tuple(f64.shape))
+    (sum(O.losses(preds, T).values()) + map_term(preds, Wk)).backward()
+    heads = MonoConDenseHeads(test_config=None)
+    heads.load_state_dict({k[5:]: v for k, v in cond_sd.items() if k.startswith("head.")}, strict=True)
+    heads = heads.cuda().train()
+    fc = feat.clone().cuda().requires_grad_(True)
+    data = {"label": {k: v.cuda() for k, v in batch["label"].items()}, "img_metas": batch["img_metas"]}
+    pd, ld = heads.forward_train(fc, data)
+    (sum(ld.values()) + map_term(pd, {k: v.cuda() for k, v in Wk.items()})).backward()
+    torch.cuda.synchronize()
+    e = rel_l2(fc.grad, f64.grad)
+    assert e < 1e-3, e
+    for n, p in heads.named_parameters():
+        ref = sd64["head." + n].grad
+        assert p.grad is not None and ref is not None, n
+        assert rel_l2(p.grad, ref) < 2e-3, (n, rel_l2(p.grad, ref))
+
+
+# ------------------------------------------------------------------------------------------------ nothing changes unused
+def _grads(m):
+    return {n: p.grad.detach().clone() for n, p in m.named_parameters() if p.grad is not None}
+
+
+def _assert_equal(a, b, tag):
+    assert a.keys() == b.keys() and len(a) == N_LIVE, tag
+    for n in a:
+        assert torch.equal(a[n], b[n]), (tag, n)
+
+
+def test_unused_map_gradients_change_nothing(cond_sd):
+    """explicit zero gradients on all ten maps, and a plain backward that follows a backward with map gradients, are
+    bit-identical to sum(loss).backward() on a fresh model (no stale map-gradient pointer survives a backward); the
+    replayed step (mc_profile_train) issues the same launches either way"""
+    batch, (B, H, W) = fixture(0)
+    b = to_cuda(batch)
+    Wk = {k: v.cuda() for k, v in map_weights(3, B, H // 4, W // 4).items()}
+
+    # `plain` and `stale` go through the same forwards (running statistics, replays), only their first backward differs
+    plain = build(cond_sd, "f16x2")
+    pred, loss = plain(b)
+    sum(loss.values()).backward()
+    g_plain = _grads(plain)
+    prof_plain = plain._rt.engine.profile_train(iters=1)
+    for p in plain.parameters():
+        p.grad = None
+    pred, loss = plain(b)
+    sum(loss.values()).backward()
+    g_plain2 = _grads(plain)
+    prof_plain2 = plain._rt.engine.profile_train(iters=1)
+
+    zero = build(cond_sd, "f16x2")
+    pred, loss = zero(b)
+    torch.autograd.backward([sum(loss.values())] + [pred[k] for k in PRED_KEYS],
+                            [torch.ones((), device="cuda")] + [torch.zeros_like(pred[k]) for k in PRED_KEYS])
+    _assert_equal(_grads(zero), g_plain, "explicit zero map gradients")
+
+    stale = build(cond_sd, "f16x2")
+    pred, loss = stale(b)
+    (sum(loss.values()) + map_term(pred, Wk)).backward()
+    g_with = _grads(stale)
+    assert any(not torch.equal(g_with[n], g_plain[n]) for n in g_plain)
+    prof_after_term = stale._rt.engine.profile_train(iters=1)     # replays the closures: the map gradients are gone
+    for p in stale.parameters():
+        p.grad = None
+    pred, loss = stale(b)
+    sum(loss.values()).backward()
+    _assert_equal(_grads(stale), g_plain2, "plain backward after one with map gradients")
+    prof_stale = stale._rt.engine.profile_train(iters=1)
+    for k in ("other", "conv", "wgrad"):
+        assert prof_after_term[k]["launches"] == prof_plain[k]["launches"], k
+        assert prof_stale[k]["launches"] == prof_plain2[k]["launches"], k
+
+
+def test_in_place_edit_of_a_map_before_backward_raises(cond_sd):
+    """the backward reads the maps (loss gradients, the activations' derivatives): modifying one in place before
+    backward() is autograd's version error, as in the reference -- not silently wrong loss gradients"""
+    batch, _ = fixture(1)
+    m = build(cond_sd, "fp32")
+    pred, loss = m(to_cuda(batch))
+    with torch.no_grad():
+        pred["depth_pred"].add_(1.0)
+    with pytest.raises(RuntimeError, match="modified by an inplace operation"):
+        sum(loss.values()).backward()
+    pd, ld = m(to_cuda(batch))          # the handle is intact: the next step runs
+    sum(ld.values()).backward()
+    assert all(bool(torch.isfinite(p.grad).all()) for n, p in m.named_parameters() if p.grad is not None)
+
+
+# ------------------------------------------------------------------------------------------------ full size
+def test_full_size_step_with_a_dense_map_term(cond_sd):
+    """B = 32 at 3x384x1280 in f16x2 (the headline configuration) with a dense term on all ten maps: every live
+    gradient is finite and the term reaches the backbone"""
+    small = synth.make_conditioned_batch(31, 2, 384, 1280)
+    batch = {"img": small["img"].repeat(16, 1, 1, 1).cuda(),
+             "label": {k: v.repeat(16, *([1] * (v.dim() - 1))).cuda() for k, v in small["label"].items()},
+             "img_metas": {"pad_shape": [(384, 1280)] * 32}}
+    m = build(cond_sd, "f16x2")
+    gen = torch.Generator(device="cuda").manual_seed(5)
+    res = []
+    for with_term in (False, True):
+        for p in m.parameters():
+            p.grad = None
+        pred, loss = m(batch)
+        J = sum(loss.values())
+        if with_term:
+            J = J + sum(10.0 * (torch.randn(v.shape, generator=gen, device="cuda") * v).sum() / v[0].numel() for v in pred.values())
+        J.backward()
+        torch.cuda.synchronize()
+        res.append(_grads(m))
+    for n, g in res[1].items():
+        assert bool(torch.isfinite(g).all()), n
+    assert len(res[1]) == N_LIVE
+    # (the second step starts from moved running statistics: round-off alone moves a gradient by ~1e-5)
+    moved = max(float((res[1][n] - res[0][n]).double().norm() / res[0][n].double().norm().clamp_min(1e-30))
+                for n in res[1] if n.startswith("backbone."))
+    assert moved > 1e-2, moved
