@@ -19,29 +19,89 @@ namespace {
 
 using Fn = std::function<int(mc_handle *, hipStream_t)>;
 
-struct TNode {
-    Tensor t;
-    float *g = nullptr;
-    bool ginit = false, needs_grad = true;
-    // the launch that wrote g last, when that is a generic stride-1 data-gradient conv (else null): its epilogue
-    // sees the COMPLETE gradient of this map and can take over the reductions of the BatchNorm backward
-    ConvArgs *last_conv = nullptr;
-    // ... or, when it was a max-pool backward that accumulated into g (round 6): that launch can mask the total and leave the
-    // BatchNorm-backward partials (launch_maxpool2_bwd's stats_partial)
-    struct PoolBwdArgs *last_pool = nullptr;
-    float **last_deconv_stats = nullptr;      // ... or the fused depthwise-deconv backward (this map's only consumer): where to attach `stats`
-    // LAZY activation (round 6, precision mode 3): the post-BatchNorm map z = act(la[c] * y + lb[c]) is never written --
-    // t.p is the producing layer's raw conv output y, and every consumer forms z while it loads its operand (ConvSrc::la
-    // in conv_mfma.h; act = ReLU when lrelu).  null: t.p holds the values.  TB::materialise() turns a lazy node into a
-    // stored one (an affine_act pass appended to the forward) for a consumer that cannot form it.
-    const float *la = nullptr, *lb = nullptr;
-    bool lrelu = true;
+// ---- the planner's switches.  CONTRACT: a switch is read from the environment when a train plan is built (the dry build
+// of mc_query_workspace included) -- by read_switches(), once, and nowhere else; the plan keeps its copy, so a plan never
+// changes behaviour after its build and two plans of one process may differ.  Why a default is what it is stands next to
+// the branch that tests the switch.
+struct PlanSwitches {
+    long long lazy_z;           // bit mask: which post-BatchNorm activations are never stored (TB::conv_bn)
+    long long lazy_min;         // elements per image from which a ReLU'd map with conv consumers is lazy
+    long long lazy_feat;        // the neck's last node lazy like the others
+    long long zbits;            // residual layers leave their ReLU mask bit-packed
+    long long grad_pool;        // gradient maps from a recycling pool (TB::g_acquire)
+    long long grad_pool_cool;   // head start of a returned buffer, in younger buffers of its size
+    long long head_dx_fuse;     // the heads' masked gradient is never stored
+    long long dgrad_s2_thin;    // level1's stride-2 data gradient in one pass
+    long long stem_fuse;        // the stem's weight gradient forms dY on the fly
+    long long bm_epilogue;      // 0 / 1 / <pixels per image>: BatchNorm-backward reductions in the data gradient's epilogue
+    long long wres_bwd;         // 0 / 1 / 2: the weight-resident conv kernel in the backward
+    long long dual_stream;      // weight gradients on a second stream
+    int side_sync_lo = 0, side_sync_hi = 0;     // MONOCON_HIP_SIDE_SYNC=lo:hi (debugging): the caller's stream waits for side steps lo <= k < hi
+    bool plan_debug = false;    // MONOCON_HIP_PLAN_DEBUG (set at all): the build prints its decisions to stderr, one "[plan]" line each
 };
+const struct { const char *name; long long PlanSwitches::*field; long long def; } SWITCH_TABLE[] = {
+    {"MONOCON_HIP_LAZY_Z", &PlanSwitches::lazy_z, 3},
+    {"MONOCON_HIP_LAZY_MIN", &PlanSwitches::lazy_min, 900000},
+    {"MONOCON_HIP_LAZY_FEAT", &PlanSwitches::lazy_feat, 0},
+    {"MONOCON_HIP_ZBITS", &PlanSwitches::zbits, 1},
+    {"MONOCON_HIP_GRAD_POOL", &PlanSwitches::grad_pool, 1},
+    {"MONOCON_HIP_GRAD_POOL_COOL", &PlanSwitches::grad_pool_cool, 2},
+    {"MONOCON_HIP_HEAD_DX_FUSE", &PlanSwitches::head_dx_fuse, 1},
+    {"MONOCON_HIP_DGRAD_S2_THIN", &PlanSwitches::dgrad_s2_thin, 1},
+    {"MONOCON_HIP_STEM_FUSE", &PlanSwitches::stem_fuse, 1},
+    {"MONOCON_HIP_BM_EPILOGUE", &PlanSwitches::bm_epilogue, 1},
+    {"MONOCON_HIP_WRES_BWD", &PlanSwitches::wres_bwd, 0},
+    {"MONOCON_HIP_DUAL_STREAM", &PlanSwitches::dual_stream, 1},
+};
+PlanSwitches read_switches() {
+    PlanSwitches sw{};
+    std::string changed;
+    for (const auto &d : SWITCH_TABLE) {
+        const char *e = std::getenv(d.name);
+        sw.*d.field = e ? std::atoll(e) : d.def;
+        if (sw.*d.field != d.def) changed += std::string(" ") + d.name + "=" + std::to_string(sw.*d.field);
+    }
+    if (const char *e = std::getenv("MONOCON_HIP_SIDE_SYNC")) {
+        if (std::sscanf(e, "%d:%d", &sw.side_sync_lo, &sw.side_sync_hi) != 2) sw.side_sync_lo = sw.side_sync_hi = 0;
+        if (sw.side_sync_lo < sw.side_sync_hi) changed += std::string(" MONOCON_HIP_SIDE_SYNC=") + e;
+    }
+    sw.plan_debug = std::getenv("MONOCON_HIP_PLAN_DEBUG") != nullptr;
+    if (sw.plan_debug && !changed.empty()) fprintf(stderr, "[plan] switches off their defaults:%s\n", changed.c_str());
+    return sw;
+}
 
 struct PoolBwdArgs {       // a max-pool backward launch (stable address: bn_backward may still attach `stats`)
     const float *x, *dout, *la, *lb;
     float *dx, *stats;
     int B, H, W, C, acc;
+};
+
+// The launch that wrote a gradient map LAST, when it is of a kind that sees the COMPLETE gradient and can take over the
+// reductions of the BatchNorm backward (TB::bn_backward); NONE for every other writer.  Set by TB::wrote() only.
+struct LastWriter {
+    enum Kind { NONE, DGRAD_CONV, POOL_BWD, DECONV_BWD } kind = NONE;
+    union {
+        ConvArgs *conv;           // a generic stride-1 data-gradient conv: its epilogue masks the gradient and leaves the partials
+        PoolBwdArgs *pool;        // a max-pool backward that accumulated into the map (launch_maxpool2_bwd's stats_partial)
+        float **deconv_stats;     // the fused depthwise-deconv backward of the map's only consumer: where to attach `stats`
+    };
+    LastWriter() : conv(nullptr) {}
+    LastWriter(ConvArgs *c) : kind(c ? DGRAD_CONV : NONE), conv(c) {}
+    LastWriter(PoolBwdArgs *p) : kind(p ? POOL_BWD : NONE), pool(p) {}
+    LastWriter(float **s) : kind(s ? DECONV_BWD : NONE), deconv_stats(s) {}
+};
+
+struct TNode {
+    Tensor t;
+    float *g = nullptr;
+    bool ginit = false, needs_grad = true;
+    LastWriter last;
+    // LAZY activation (precision mode 3): the post-BatchNorm map z = act(la[c] * y + lb[c]) is never written --
+    // t.p is the producing layer's raw conv output y, and every consumer forms z while it loads its operand (ConvSrc::la
+    // in conv_mfma.h; act = ReLU when lrelu).  null: t.p holds the values.  TB::materialise() turns a lazy node into a
+    // stored one (an affine_act pass appended to the forward) for a consumer that cannot form it.
+    const float *la = nullptr, *lb = nullptr;
+    bool lrelu = true;
 };
 
 struct PackJob {           // dgrad panel refreshed from the master weights before every forward
@@ -68,33 +128,41 @@ struct Rec {
     std::string bn;
 };
 
+// One step of the backward pass, in the order the steps are enqueued (TB::push_bwd is the only way one is appended).
+enum BwdStream { ON_MAIN, ON_SIDE };
+struct BwdStep {
+    Fn fn;
+    // ON_SIDE: the step only produces weight gradients (nothing downstream in the backward reads them) and runs on the
+    // plan's second stream: MFMA-bound wgrad overlaps the HBM-bound BN passes and the tails of the dgrad chain
+    BwdStream stream = ON_MAIN;
+    // gradient-map pool (TB::g_acquire): this step is the first writer of a recycled buffer whose previous content was
+    // read by side step `wait` (index in TrainState::bwd; -1: nothing to wait for)
+    int wait = -1;
+    // data parallelism: the gradient bucket (mc_internal.h) that is complete once this step has been enqueued, or -1
+    int bucket = -1;
+    bool feat_dgrad = false;         // head-only plan: the data gradient into the external feat node (TrainState::skip_feat_dgrad)
+    hipEvent_t ready = nullptr;      // side step: everything it reads is complete at this point of the caller's stream
+    hipEvent_t fin = nullptr;        // side step some later step waits for: it has finished
+};
+
 }  // namespace
 
 struct TrainState {
     int B = 0, H = 0, W = 0;
     unsigned long long bind_gen = 0;
+    PlanSwitches sw{};
     PlanMem mem;
     std::vector<TNode> nodes;
     std::vector<Rec> recs;
-    std::vector<Fn> fwd, bwd;
+    std::vector<Fn> fwd;
+    std::vector<BwdStep> bwd;
     std::deque<ConvArgs> dgrads;     // data-gradient launches (stable addresses: bn_backward may still patch them)
     std::deque<PoolBwdArgs> pool_bwds;
     std::deque<float *> deconv_stats;      // per fused deconv backward: its statistics buffer (null until bn_backward attaches one)
-    // backward closures that only produce weight gradients (nothing downstream in the step reads them) run
-    // on a second stream: MFMA-bound wgrad overlaps the HBM-bound BN passes and the tails of the dgrad chain
-    std::vector<char> bwd_side;
-    // data parallelism: gradient bucket b (mc_internal.h) is complete once backward closure bucket_after[b] has been
-    // enqueued (-1: no closure writes into it)
-    int bucket_after[MC_NUM_GRAD_BUCKETS] = {-1, -1, -1, -1};
-    hipStream_t side = nullptr;
-    std::vector<hipEvent_t> side_ev;
+    hipStream_t side = nullptr;      // the weight-gradient stream
     hipEvent_t side_done = nullptr;
-    // gradient-map pool (see TB::g_acquire): before main-stream closure `first` writes into a recycled buffer it waits for
-    // side-stream closure number `second` (the weight gradient that read the buffer's previous content)
+    bool dual = true;                // side steps run on `side` (false: MONOCON_HIP_DUAL_STREAM=0, or the stream / an event could not be created)
     unsigned *img_amax = nullptr;      // mode 3: max |image| slot (written by the forward stem, read by its weight gradient)
-    std::map<int, int> wait_side;
-    std::vector<hipEvent_t> side_fin;
-    bool dual = true;
     std::vector<PackJob> packs;
     mc::PackBatch pack_batch;        // the data-gradient panels of `packs`, one grid per forward
     std::vector<Fn> pack_fns;
@@ -113,7 +181,6 @@ struct TrainState {
     const float *feat_ext = nullptr;
     float *gfeat_ext = nullptr;
     bool skip_feat_dgrad = false;    // head-only plan, mc_head_backward(grad_feat = NULL)
-    int feat_dgrad_closure = -1;     // index in `bwd` of the data gradient into the external feat node
     // plan-owned
     mc_targets targets{};
     float *dpred[10] = {nullptr};
@@ -126,9 +193,10 @@ static std::atomic<unsigned long long> g_train_generation{0};
 
 static void train_free(TrainState *t) {
     if (!t) return;
-    for (hipEvent_t e : t->side_ev) (void)hipEventDestroy(e);
-    for (hipEvent_t e : t->side_fin)
-        if (e) (void)hipEventDestroy(e);
+    for (const BwdStep &s : t->bwd) {
+        if (s.ready) (void)hipEventDestroy(s.ready);
+        if (s.fin) (void)hipEventDestroy(s.fin);
+    }
     if (t->side_done) (void)hipEventDestroy(t->side_done);
     if (t->side) (void)hipStreamDestroy(t->side);
     t->mem.release();
@@ -141,12 +209,10 @@ struct TB {   // train plan builder
     mc_handle *h;
     TrainState *ts;
     PlanAlloc mem{h, ts->mem, ts->ok, 1, 1024};
+    const PlanSwitches &sw = ts->sw;
+    const int B = ts->B, H = ts->H, W = ts->W, fh = H / 4, fw = W / 4, HW = fh * fw;
     void *last_panel16 = nullptr;   // bf16 twin of the panel the last pack_job() made
 
-    // bn_backward(): the caller consumes (d, y, coef) itself -- no element-wise dY pass (the stem, whose dY is read by its
-    // weight gradient only); honoured on the backward-statistics-epilogue path, reported back in did_skip_affine
-    bool want_skip_affine = false, did_skip_affine = false;
-    float *skip_coef = nullptr;
     float *alloc(size_t n) { return mem.alloc(n); }
     unsigned *slot() { return mem.slot(); }
     unsigned *w_slot(const float *w_master) {
@@ -155,75 +221,60 @@ struct TB {   // train plan builder
         if (it == h->w_amax_of.end()) { ts->ok = false; h->err = "train plan: no max-|w| slot for a master weight"; return nullptr; }
         return it->second;
     }
-    // activation / gradient maps the autotuner times kernels on: optionally ReLU-shaped noise instead of zeros (see
-    // launch_noise_fill).  MEASURED (round 4, one session, B=32): 56.52 / 56.56 ms per step tuned on zeros, 56.51 / 56.62
-    // tuned on noise -- the ranking of the shapes does not depend on it; off by default (MONOCON_HIP_TUNE_NOISE=1).
-    bool tune_noise = [] { const char *e = std::getenv("MONOCON_HIP_TUNE_NOISE"); return e && std::atoi(e) != 0; }();
-    int wres_bwd = [] { const char *e = std::getenv("MONOCON_HIP_WRES_BWD"); return e ? std::atoi(e) : 0; }();
-    float *alloc_map(size_t n) {
-        float *p = alloc(n);
-        if (p && !h->dry_alloc && h->autotune && tune_noise && n >= 4096)
-            (void)launch_noise_fill(p, n, (unsigned)ts->mem.bufs.size() * 7919u, nullptr);
-        return p;
+
+    // ---- backward steps
+    int cur_bucket = 0;       // gradient bucket of the layer group whose steps are being pushed (build_train keeps the last of each)
+    int pending_wait = -1;    // g_acquire() handed out a recycled buffer: the next step pushed is its first writer
+    int push_bwd(Fn fn, BwdStream stream = ON_MAIN) {
+        BwdStep s;
+        s.fn = std::move(fn); s.stream = stream; s.bucket = cur_bucket; s.wait = pending_wait;
+        pending_wait = -1;
+        ts->bwd.push_back(std::move(s));
+        return (int)ts->bwd.size() - 1;
     }
-    // ---- gradient maps.  The backward closures are BUILT in the order they run, so the life of a map's gradient is known
+
+    // ---- gradient maps.  The backward steps are BUILT in the order they run, so the life of a map's gradient is known
     // while building: it starts at its first writer (a data-gradient conv, a pooling / deconv backward, the residual
     // share of an affine pass) and ends with the layer that produced the map (whose affine pass turns dZ into dY in
     // place; dY is then read by that layer's data- and weight-gradient launches).  Buffers are handed out at the first
     // write and returned after the producing layer, oldest first; a buffer whose last reader ran on the weight-gradient
-    // stream carries that closure's number, and its next first writer waits for it (TrainState::wait_side).
+    // stream carries that step's index, and its next first writer waits for it (BwdStep::wait).
     // MONOCON_HIP_GRAD_POOL=0: one private buffer per map.  Measured at B=32 (one session, scratch/ab/pool_ab.sh):
     // 37.7 GB / 59.77 ms without the pool, 32.9 GB / 60.09 ms recycling immediately, 33.8 GB / 59.89 ms with two buffers
     // of head start (the default).
-    struct PoolBuf { float *p; int side_k; };
+    struct PoolBuf { float *p; int side_step; };
     std::map<size_t, std::deque<PoolBuf>> gpool;
-    bool pool_on = [] { const char *e = std::getenv("MONOCON_HIP_GRAD_POOL"); return !e || std::atoi(e) != 0; }();
-    // a returned buffer is handed out again only once `pool_cool` younger ones of its size wait behind it: the weight
-    // gradient that still reads it has then had that many layers of head start, and the wait is a formality
-    int pool_cool = [] { const char *e = std::getenv("MONOCON_HIP_GRAD_POOL_COOL"); return e ? std::atoi(e) : 2; }();
     float *g_acquire(int node) {
         TNode &n = ts->nodes[node];
         if (n.g) return n.g;
         const size_t ne = n.t.numel();
         auto &q = gpool[ne];
-        if (pool_on && (int)q.size() > pool_cool) {
+        // a returned buffer is handed out again only once MONOCON_HIP_GRAD_POOL_COOL younger ones of its size wait behind it:
+        // the weight gradient that still reads it has then had that many layers of head start, and the wait is a formality
+        if (sw.grad_pool && (long long)q.size() > sw.grad_pool_cool) {
             const PoolBuf b = q.front();
             q.pop_front();
-            if (b.side_k >= 0) {
-                auto it = ts->wait_side.find((int)ts->bwd.size());
-                if (it == ts->wait_side.end()) ts->wait_side[(int)ts->bwd.size()] = b.side_k;
-                else it->second = std::max(it->second, b.side_k);
-            }
+            pending_wait = std::max(pending_wait, b.side_step);
             n.g = b.p;
         } else {
-            n.g = alloc_map(ne);
+            n.g = alloc(ne);
         }
         return n.g;
     }
-    void g_release(int node, int side_k) {
+    // the map's gradient has had its last reader: side step `side_step` (-1: a step on the caller's stream)
+    void g_release(int node, int side_step) {
         TNode &n = ts->nodes[node];
-        if (!pool_on || !n.g) return;
-        gpool[n.t.numel()].push_back({n.g, side_k});
+        if (!sw.grad_pool || !n.g) return;
+        gpool[n.t.numel()].push_back({n.g, side_step});
         n.g = nullptr;
     }
-    int last_side_closure() const {       // number (among the side-stream closures) of the last one pushed, -1 if none
-        int k = 0;
-        for (char c : ts->bwd_side) k += c != 0;
-        return k - 1;
+    // EVERY writer of a gradient map calls this after pushing its step(s): `by` names the launch if it can carry the
+    // BatchNorm-backward reductions of the map (see LastWriter), and is left out by every other writer
+    void wrote(int node, LastWriter by = {}) {
+        ts->nodes[node].ginit = true;
+        ts->nodes[node].last = by;
     }
-    // MONOCON_HIP_LAZY_Z (bit mask, default 3): which post-BatchNorm activations are never stored (TNode::la).  1: the
-    // BatchNorm + ReLU outputs without residual (stem, level0 / level1, BasicBlock conv1, Root, neck proj / node); 2: a
-    // Tree's `project` branch (BatchNorm without ReLU, consumed as the residual of the block beside it); 0: every
-    // activation is stored (rounds 1-5).  Outputs of a residual add are always stored.
-    int lazy_mask = [] { const char *e = std::getenv("MONOCON_HIP_LAZY_Z"); return e ? std::atoi(e) : 3; }();
-    // A lazy map costs its MFMA-kernel consumers one fma + one v_med3 per staged element (measured, B = 32: a 3x3 weight
-    // gradient +0.03 ms, a conv +0.01 ms per launch) and saves one element-wise pass over the map (2 x its bytes at ~5.3
-    // TB/s): worth it for the large maps only.  MONOCON_HIP_LAZY_MIN: elements per image from which a ReLU'd map whose
-    // consumers are convolutions is lazy; maps with element-wise consumers only (neck proj -> deconv, project -> residual)
-    // always are.  The default sits between the 256-channel 24x80 maps (491 520 elements: stored) and the 128-channel maps
-    // of the quarter-resolution level (983 040 at the benchmark's width 1280, 958 464 at KITTI's 1248: lazy): with 983 040
-    // itself a KITTI batch lost those maps and 0.3 ms per step (48.66 -> 48.35 ms at 384x1248, two runs each).
-    long long lazy_min = [] { const char *e = std::getenv("MONOCON_HIP_LAZY_MIN"); return e ? std::atoll(e) : 900000ll; }();
+
     int n_lazy = 0, n_materialised = 0;
     // a consumer that cannot form a lazy activation on load: store it after all (one element-wise pass appended to the
     // forward at this point of the build -- i.e. before the consumer's own launch -- and the node is an ordinary one from
@@ -231,7 +282,7 @@ struct TB {   // train plan builder
     void materialise(int node_i) {
         TNode &n = ts->nodes[node_i];
         if (!n.la) return;
-        float *z = alloc_map(n.t.numel());
+        float *z = alloc(n.t.numel());
         const float *y = n.t.p, *la = n.la, *lb = n.lb;
         const int B = n.t.B, C = n.t.C, rl = n.lrelu ? 1 : 0;
         const size_t rows = (size_t)n.t.H * n.t.W;
@@ -239,7 +290,7 @@ struct TB {   // train plan builder
             HIPCHK(hh, launch_affine_act(y, la, lb, nullptr, B, rows, C, 0, rl, z, st, nullptr));
             return 0;
         });
-        if (std::getenv("MONOCON_HIP_PLAN_DEBUG"))
+        if (sw.plan_debug)
             fprintf(stderr, "[plan] lazy node %d (%d ch %dx%d) materialised for a consumer that cannot form it on load\n", node_i, C, n.t.H, n.t.W);
         n.t.p = z; n.la = n.lb = nullptr;
         ++n_materialised;
@@ -251,10 +302,10 @@ struct TB {   // train plan builder
     int node(int B, int H, int W, int C, bool needs_grad = true, bool storage = true) {
         TNode n;
         n.t.B = B; n.t.H = H; n.t.W = W; n.t.C = C;
-        n.t.p = storage ? alloc_map(n.t.numel()) : nullptr;
+        n.t.p = storage ? alloc(n.t.numel()) : nullptr;
         n.t.amax = slot();
         n.needs_grad = needs_grad;
-        if (needs_grad && !pool_on) n.g = alloc(n.t.numel());
+        if (needs_grad && !sw.grad_pool) n.g = alloc(n.t.numel());
         ts->nodes.push_back(n);
         return (int)ts->nodes.size() - 1;
     }
@@ -294,16 +345,106 @@ struct TB {   // train plan builder
         });
     }
 
-    // the neck's LAST node is `feat` (NetStep::never_lazy): its consumers are the fused 64 -> 576 head conv and that conv's
-    // weight gradient, the two longest launches of the step -- formed on load it cost them 0.15 + 0.22 ms (alone) to save a
-    // 0.095 ms pass: stored (MONOCON_HIP_LAZY_FEAT=1: lazy like the other nodes)
-    bool lazy_feat = [] { const char *e = std::getenv("MONOCON_HIP_LAZY_FEAT"); return e && std::atoi(e) != 0; }();
+    // the max-|x| slots start every forward at zero: their producers only raise them (mode 3; the first step of the forward)
+    void zero_amax_slots() {
+        if (h->prec != 3) return;
+        (void)slot();
+        --ts->mem.amax_used;
+        ts->fwd.push_back([ts = ts](mc_handle *hh, hipStream_t st) {
+            HIPCHK(hh, hipMemsetAsync(ts->mem.amax_arena, 0, (size_t)ts->mem.amax_used * AMAX_WORDS * sizeof(unsigned), st));
+            return 0;
+        });
+    }
+
+    // the heads on their own (MonoConDenseHeads.forward_train, monocon_heads.py:150-157): the neck output is an
+    // external NCHW tensor, copied into the plan's NHWC node; its gradient is copied out after the backward
+    int external_feat() {
+        const int feat = node(B, fh, fw, 64, true);
+        float *fp = ts->nodes[feat].t.p;
+        unsigned *fmax = ts->nodes[feat].t.amax;
+        ts->fwd.push_back([=, ts = ts, B = B, fh = fh, fw = fw](mc_handle *hh, hipStream_t st) {
+            HIPCHK(hh, launch_nchw_to_nhwc(ts->feat_ext, B, 64, fh, fw, fp, st));
+            if (fmax) HIPCHK(hh, launch_absmax(fp, (size_t)B * fh * fw * 64, fmax, st));
+            return 0;
+        });
+        return feat;
+    }
+
+    // BatchNorm of the raw conv output r.y from its statistics partials, then the activation: lazy (never stored: the node
+    // points at y and carries the coefficients; ymax = the slot where the conv left max |y|), or one element-wise pass
+    void bn_act(Rec &r, const float *stats, int nb, int cstride, bool lazy, const unsigned *ymax) {
+        const int B = r.y.B, C = r.y.C, res = r.res, rl = r.relu;
+        float *ca = alloc(C), *cb = alloc(C);
+        r.ca = ca; r.cb = cb;
+        r.mean = alloc(C); r.rstd = alloc(C);
+        bn_train_ops(r.y, stats, nb, cstride, r.bn, 1e-5f, 0.1f, ca, cb, r.mean, r.rstd, ymax, lazy ? ts->nodes[r.z].t.amax : nullptr, rl);
+        if (lazy) {
+            TNode &zn = ts->nodes[r.z];
+            zn.t.p = r.y.p; zn.la = ca; zn.lb = cb; zn.lrelu = r.relu;
+            ++n_lazy;
+        } else if (!r.dead) {
+            const TNode &rn = ts->nodes[res >= 0 ? res : 0];
+            const float *yp = r.y.p, *rp = res >= 0 ? rn.t.p : nullptr;
+            const float *ra = res >= 0 ? rn.la : nullptr, *rb = res >= 0 ? rn.lb : nullptr;     // the residual may be lazy
+            const int rrelu = (res >= 0 && rn.lrelu) ? 1 : 0;
+            float *zp = ts->nodes[r.z].t.p;
+            unsigned *zmax = ts->nodes[r.z].t.amax;
+            const size_t rows = (size_t)r.y.H * r.y.W;
+            // a residual layer's ReLU mask cannot be recomputed from y alone: the forward leaves it bit-packed for the
+            // backward-statistics epilogue of the data gradient that completes this map's gradient (1/32 of the bytes of z;
+            // MONOCON_HIP_ZBITS=0: that epilogue reads z)
+            unsigned *zb = (sw.zbits && res >= 0 && rl && C % 32 == 0) ? reinterpret_cast<unsigned *>(alloc((size_t)B * rows * (C / 32))) : nullptr;
+            r.zbits = zb;
+            ts->fwd.push_back([=](mc_handle *hh, hipStream_t st) {
+                HIPCHK(hh, launch_affine_act(yp, ca, cb, rp, B, rows, C, 0, rl, zp, st, zmax, ra, rb, rrelu, zb));
+                return 0;
+            });
+        }
+    }
+
+    // ---- stem (raw conv -> batch stats -> normalise + ReLU)
+    void stem() {
+        Rec stem;
+        stem.kind = REC_STEM; stem.bn = "backbone.base_layer.1"; stem.relu = true;
+        stem.y.B = B; stem.y.H = H; stem.y.W = W; stem.y.C = 16;
+        stem.y.p = alloc(stem.y.numel());
+        // (mode 3 with the fp16-pipe stem, which leaves max |y|: the stem's activation is lazy like conv_bn's, TNode::la)
+        const bool stem_lazy = h->prec == 3 && stem_f16_enabled() && (sw.lazy_z & 1);
+        stem.z = node(B, H, W, 16, true, !stem_lazy);
+        float *ones16 = alloc(16), *zeros16 = alloc(16);
+        std::vector<float> one(16, 1.f);
+        if (!h->dry_alloc && hipMemcpy(ones16, one.data(), 64, hipMemcpyHostToDevice) != hipSuccess) ts->ok = false;
+        // mode 3: the fp16-pipe stem leaves the (sum, sum of squares) partials per output row itself; the other modes reduce
+        // the raw map in a second pass
+        const bool fused_stats = h->prec == 3 && stem_f16_enabled();
+        const int nb = fused_stats ? B * H : chan_reduce_blocks(B, H * W);
+        float *partial = alloc((size_t)nb * 16 * 2), *yp = stem.y.p, *rm = P(stem.bn + ".running_mean", 16);
+        unsigned *imax = fused_stats ? slot() : nullptr;     // max |image|, left by the forward stem for its weight gradient
+        ts->img_amax = imax;
+        unsigned *ymax = fused_stats ? slot() : nullptr;     // max |raw stem output|: operand-scale bound of the fused weight gradient
+        stem.y.amax = ymax;
+        const float *sw_ = h->stem_w;
+        ts->fwd.push_back([=, ts = ts, B = B, H = H, W = W](mc_handle *hh, hipStream_t st) {
+            if (fused_stats) {
+                HIPCHK(hh, launch_stem_f16(ts->img, B, H, W, sw_, ones16, zeros16, yp, st, 0, ymax, partial, rm, imax));
+            } else {
+                HIPCHK(hh, launch_stem(ts->img, B, H, W, sw_, ones16, zeros16, yp, st, 0, hh->prec));
+                HIPCHK(hh, launch_chan_reduce(yp, nullptr, nullptr, rm, B, H * W, 16, 0, 0, partial, 16, st));
+            }
+            return 0;
+        });
+        bn_act(stem, partial, nb, 16, stem_lazy, stem_lazy ? ymax : nullptr);
+        ts->recs.push_back(stem);
+    }
 
     int conv_bn(const NetStep &s) {
         ConvLayer &Lr = L(s.name);
         const std::vector<int> &srcs = s.srcs;
         const int res = s.res;
-        const bool relu = s.relu, dead = s.dead, never_lazy = s.never_lazy && !lazy_feat;
+        // the neck's LAST node is `feat` (NetStep::never_lazy): its consumers are the fused 64 -> 576 head conv and that conv's
+        // weight gradient, the two longest launches of the step -- formed on load it cost them 0.15 + 0.22 ms (alone) to save a
+        // 0.095 ms pass: stored (MONOCON_HIP_LAZY_FEAT=1: lazy like the other nodes)
+        const bool relu = s.relu, dead = s.dead, never_lazy = s.never_lazy && !sw.lazy_feat;
         const Tensor s0 = ts->nodes[srcs[0]].t;   // by value: node() below may reallocate ts->nodes
         const int B = s0.B;
         const int Ho = (s0.H + 2 * (Lr.ks / 2) - Lr.ks) / Lr.stride + 1, Wo = (s0.W + 2 * (Lr.ks / 2) - Lr.ks) / Lr.stride + 1;
@@ -311,9 +452,19 @@ struct TB {   // train plan builder
         r.kind = REC_CONV; r.L = &Lr; r.srcs = srcs; r.res = res; r.relu = relu; r.dead = dead; r.bn = Lr.bn;
         r.y.B = B; r.y.H = Ho; r.y.W = Wo; r.y.C = Lr.cout;
         r.y.p = alloc(r.y.numel());
-        // lazy output: BatchNorm (+ ReLU) without residual in mode 3 (the convs of every kernel family leave max |y|)
-        const bool lazy = !dead && !never_lazy && res < 0 && h->prec == 3 && (lazy_mask & (relu ? 1 : 2)) != 0 &&
-                          (!relu || s.elementwise_consumers || (long long)Ho * Wo * Lr.cout >= lazy_min);
+        // lazy output: BatchNorm (+ ReLU) without residual in mode 3 (the convs of every kernel family leave max |y|).
+        // MONOCON_HIP_LAZY_Z (bit mask, default 3): 1: the BatchNorm + ReLU outputs without residual (stem, level0 / level1,
+        // BasicBlock conv1, Root, neck proj / node); 2: a Tree's `project` branch (BatchNorm without ReLU, consumed as the
+        // residual of the block beside it); 0: every activation is stored.  Outputs of a residual add are always stored.
+        // A lazy map costs its MFMA-kernel consumers one fma + one v_med3 per staged element (measured, B = 32: a 3x3 weight
+        // gradient +0.03 ms, a conv +0.01 ms per launch) and saves one element-wise pass over the map (2 x its bytes at ~5.3
+        // TB/s): worth it for the large maps only.  MONOCON_HIP_LAZY_MIN: elements per image from which a ReLU'd map whose
+        // consumers are convolutions is lazy; maps with element-wise consumers only (neck proj -> deconv, project -> residual)
+        // always are.  The default sits between the 256-channel 24x80 maps (491 520 elements: stored) and the 128-channel maps
+        // of the quarter-resolution level (983 040 at the benchmark's width 1280, 958 464 at KITTI's 1248: lazy): with 983 040
+        // itself a KITTI batch lost those maps and 0.3 ms per step (48.66 -> 48.35 ms at 384x1248, two runs each).
+        const bool lazy = !dead && !never_lazy && res < 0 && h->prec == 3 && (sw.lazy_z & (relu ? 1 : 2)) != 0 &&
+                          (!relu || s.elementwise_consumers || (long long)Ho * Wo * Lr.cout >= sw.lazy_min);
         r.z = dead ? -1 : node(B, Ho, Wo, Lr.cout, true, !lazy);
         ConvArgs a{};
         a.nsrc = (int)srcs.size();
@@ -347,35 +498,7 @@ struct TB {   // train plan builder
         a.stat_shift = P(Lr.bn + ".running_mean", Lr.cout);
         const int ks = Lr.ks, stride = Lr.stride;
         ts->fwd.push_back([=](mc_handle *hh, hipStream_t st) { HIPCHK(hh, launch_conv(a, ks, stride, st)); return 0; });
-        float *ca = alloc(Lr.cout), *cb = alloc(Lr.cout);
-        r.ca = ca; r.cb = cb;
-        r.mean = alloc(Lr.cout); r.rstd = alloc(Lr.cout);
-        bn_train_ops(r.y, stats, B * chunks, Lr.coutp, Lr.bn, 1e-5f, 0.1f, ca, cb, r.mean, r.rstd, yslot,
-                     lazy ? ts->nodes[r.z].t.amax : nullptr, relu ? 1 : 0);
-        if (lazy) {
-            TNode &zn = ts->nodes[r.z];
-            zn.t.p = r.y.p; zn.la = ca; zn.lb = cb; zn.lrelu = relu;
-            ++n_lazy;
-        } else if (!dead) {
-            const TNode &rn = ts->nodes[res >= 0 ? res : 0];
-            const float *yp = r.y.p, *rp = res >= 0 ? rn.t.p : nullptr;
-            const float *ra = res >= 0 ? rn.la : nullptr, *rb = res >= 0 ? rn.lb : nullptr;     // the residual may be lazy
-            const int rrelu = (res >= 0 && rn.lrelu) ? 1 : 0;
-            float *zp = ts->nodes[r.z].t.p;
-            unsigned *zmax = ts->nodes[r.z].t.amax;
-            const size_t rows = (size_t)Ho * Wo;
-            const int C = Lr.cout, rl = relu;
-            // a residual layer's ReLU mask cannot be recomputed from y alone: the forward leaves it bit-packed for the
-            // backward-statistics epilogue of the data gradient that completes this map's gradient (1/32 of the bytes of z;
-            // MONOCON_HIP_ZBITS=0: that epilogue reads z as in rounds 1-5)
-            const bool zbits_on = [] { const char *e = std::getenv("MONOCON_HIP_ZBITS"); return !e || std::atoi(e) != 0; }();      // (per plan build)
-            unsigned *zb = (zbits_on && res >= 0 && relu && C % 32 == 0) ? reinterpret_cast<unsigned *>(alloc((size_t)B * rows * (C / 32))) : nullptr;
-            r.zbits = zb;
-            ts->fwd.push_back([=](mc_handle *hh, hipStream_t st) {
-                HIPCHK(hh, launch_affine_act(yp, ca, cb, rp, B, rows, C, 0, rl, zp, st, zmax, ra, rb, rrelu, zb));
-                return 0;
-            });
-        }
+        bn_act(r, stats, B * chunks, Lr.coutp, lazy, yslot);
         ts->recs.push_back(r);
         return r.z;
     }
@@ -439,38 +562,41 @@ struct TB {   // train plan builder
         TNode &sn = ts->nodes[srcnode];
         if (!sn.needs_grad) return;
         g_acquire(srcnode);
+        // a stride-1 conv over dY with the panel of one output-parity class (-1: the whole flipped kernel)
+        auto dgrad_conv = [&](int cls) {
+            float *panel;
+            int csp;
+            pack_job(w_master, Cout_fwd, CinTotal, ks, c_off, sn.t.C, CoutPad, &panel, &csp, cls);
+            ConvArgs d{};
+            d.nsrc = 1;
+            d.src[0].p = dy.p; d.src[0].C = dy.C;
+            d.B = dy.B; d.Hin = dy.H; d.Win = dy.W; d.Hout = dy.H; d.Wout = dy.W;
+            d.Cin = dy.C; d.Cout = sn.t.C; d.CoutP = csp; d.wpk = panel;
+            d.wpk16 = last_panel16; d.prec = last_panel16 ? h->prec : 0;
+            d.amax_in[0] = dy.amax; d.amax_w = w_slot(w_master);
+            return d;
+        };
         if (stride == 2 && ks == 3) {
             // four output-parity classes, each a small stride-1 window conv over dY that scatters to every
             // second pixel of g_src (no zero-dilated copy of dY, 9 instead of 36 tap-MACs per output quad)
             if (2 * dy.H != sn.t.H || 2 * dy.W != sn.t.W) { ts->ok = false; h->err = "train plan: stride-2 dgrad shape mismatch"; }
             // the 32 -> 16 layer at full resolution (level1): all four classes in one pass of its own kernel (conv_thin.hip;
             // MONOCON_HIP_DGRAD_S2_THIN=0: the four launches below)
-            const bool s2_thin = [] { const char *e = std::getenv("MONOCON_HIP_DGRAD_S2_THIN"); return !e || std::atoi(e) != 0; }();
-            if (s2_thin && ts->ok && dgrad_s2_thin_ok(h->prec, ks, stride, dy.C, sn.t.C, CinTotal, c_off, dy.amax, w_slot(w_master), dy.H, dy.W)) {
+            if (sw.dgrad_s2_thin && ts->ok && dgrad_s2_thin_ok(h->prec, ks, stride, dy.C, sn.t.C, CinTotal, c_off, dy.amax, w_slot(w_master), dy.H, dy.W)) {
                 const float *dyp = dy.p;
                 float *gp = sn.g;
                 const int B = dy.B, Hd = dy.H, Wd = dy.W, Cd = dy.C, acc = sn.ginit ? 1 : 0;
                 const unsigned *dmax = dy.amax, *wmax = w_slot(w_master);
-                ts->bwd.push_back([=](mc_handle *hh, hipStream_t st) {
+                push_bwd([=](mc_handle *hh, hipStream_t st) {
                     HIPCHK(hh, launch_dgrad_s2_thin(dyp, B, Hd, Wd, Cd, w_master, CinTotal, c_off, gp, acc, dmax, wmax, st));
                     return 0;
                 });
-                sn.ginit = true;
-                sn.last_conv = nullptr; sn.last_pool = nullptr;
+                wrote(srcnode);
                 return;
             }
             for (int cls = 0; cls < 4; ++cls) {
                 const int py = cls >> 1, px = cls & 1;
-                float *panel;
-                int csp;
-                pack_job(w_master, Cout_fwd, CinTotal, ks, c_off, sn.t.C, CoutPad, &panel, &csp, cls);
-                ConvArgs d{};
-                d.nsrc = 1;
-                d.src[0].p = dy.p; d.src[0].C = dy.C;
-                d.B = dy.B; d.Hin = dy.H; d.Win = dy.W; d.Hout = dy.H; d.Wout = dy.W;
-                d.Cin = dy.C; d.Cout = sn.t.C; d.CoutP = csp; d.wpk = panel;
-                d.wpk16 = last_panel16; d.prec = last_panel16 ? h->prec : 0;
-                d.amax_in[0] = dy.amax; d.amax_w = w_slot(w_master);
+                ConvArgs d = dgrad_conv(cls);
                 const int ld = sn.t.C;
                 d.out = sn.g + ((size_t)py * sn.t.W + px) * ld; d.out_ld = ld;
                 d.o_px = 2 * ld; d.o_row = 2 * sn.t.W * ld; d.o_img = sn.t.H * sn.t.W * ld;
@@ -478,47 +604,34 @@ struct TB {   // train plan builder
                 const int kcode = (1 + py) * 10 + (1 + px);
                 const int kk = kcode == 11 ? 1 : kcode;
                 d.cfg = ts->ok ? mc_choose_conv_cfg(h, d, kk, 1) : CFG_128x32;
-                ts->bwd.push_back([=](mc_handle *hh, hipStream_t st) { HIPCHK(hh, launch_conv(d, kk, 1, st)); return 0; });
+                push_bwd([=](mc_handle *hh, hipStream_t st) { HIPCHK(hh, launch_conv(d, kk, 1, st)); return 0; });
             }
-            sn.ginit = true;
-            sn.last_conv = nullptr; sn.last_pool = nullptr;
+            wrote(srcnode);
             return;
         }
-        float *panel;
-        int csp;
-        pack_job(w_master, Cout_fwd, CinTotal, ks, c_off, sn.t.C, CoutPad, &panel, &csp);
-        const float *dyp = dy.p;
-        int Hd = dy.H, Wd = dy.W;
-        ConvArgs d{};
-        d.nsrc = 1;
-        d.src[0].p = dyp; d.src[0].C = dy.C;
-        d.B = dy.B; d.Hin = Hd; d.Win = Wd; d.Hout = Hd; d.Wout = Wd;
-        d.Cin = dy.C; d.Cout = sn.t.C; d.CoutP = csp; d.wpk = panel;
-        d.wpk16 = last_panel16; d.prec = last_panel16 ? h->prec : 0;
-        d.amax_in[0] = dy.amax; d.amax_w = w_slot(w_master);
+        ConvArgs d = dgrad_conv(-1);
         d.out = sn.g; d.out_ld = sn.t.C;
         if (sn.ginit) { d.res = sn.g; d.res_ld = sn.t.C; }
-        if (Hd != sn.t.H || Wd != sn.t.W) { ts->ok = false; h->err = "train plan: dgrad shape mismatch"; }
+        if (dy.H != sn.t.H || dy.W != sn.t.W) { ts->ok = false; h->err = "train plan: dgrad shape mismatch"; }
         d.cfg = ts->ok ? mc_choose_conv_cfg(h, d, ks, 1) : CFG_128x32;
         // The weight-resident kernel (conv_wres.hip) owns its CU -- four waves with the whole register file -- so beside the
         // weight-gradient stream it cannot share one the way the tiled kernels do and the two streams take
-        // turns: measured in the step (rocprofv3, round 5) a plain 64 -> 64 data gradient takes ~595 us on it against 389 us
+        // turns: measured in the step (rocprofv3) a plain 64 -> 64 data gradient takes ~595 us on it against 389 us
         // on conv_bf16_kernel, although it is the faster kernel alone (244 vs 284 us); its backward-statistics twins take
         // 546 us in the step (303 alone).  One-session A/B of the whole step: 52.61 ms without it in the backward, 53.24 ms
         // with the twins on it.  Backward launches therefore keep the tiled kernels.
         // MONOCON_HIP_WRES_BWD: 0 (default) = never in the backward, 1 = the twins (bn_backward sets the flag), 2 = wherever
         // the autotuner chose it
-        if (wres_bwd < 2) d.cfg &= ~CFG_WRES;
+        if (sw.wres_bwd < 2) d.cfg &= ~CFG_WRES;
         ts->dgrads.push_back(d);
         ConvArgs *dp = &ts->dgrads.back();
-        ts->bwd.push_back([=](mc_handle *hh, hipStream_t st) { HIPCHK(hh, launch_conv(*dp, ks, 1, st)); return 0; });
-        sn.ginit = true;
+        push_bwd([=](mc_handle *hh, hipStream_t st) { HIPCHK(hh, launch_conv(*dp, ks, 1, st)); return 0; });
         // (the fp32 row kernel has no backward-statistics epilogue; its fp16-pipe replacement for 16 -> 16 layers has)
-        sn.last_conv = (d.cfg == CFG_SMALL && !conv_thin_ok(d, ks, 1)) ? nullptr : dp;
-        sn.last_pool = nullptr;
+        wrote(srcnode, (d.cfg == CFG_SMALL && !conv_thin_ok(d, ks, 1)) ? nullptr : dp);
     }
 
-    void emit_wgrad(const std::vector<int> &srcs, const Tensor &dy, int dy_ld, int Cout, int ks, int stride, float *dw) {
+    // the weight gradient of a conv, on the weight-gradient stream: dy is not written again in this step.  Returns its step.
+    int emit_wgrad(const std::vector<int> &srcs, const Tensor &dy, int dy_ld, int Cout, int ks, int stride, float *dw) {
         WgradArgs a{};
         a.nsrc = (int)srcs.size();
         auto fill = [&] {
@@ -546,11 +659,14 @@ struct TB {   // train plan builder
             fill();
         }
         a.partial = alloc(wgrad_partial_floats(a, ks));
-        ts->bwd.push_back([=](mc_handle *hh, hipStream_t st) { HIPCHK(hh, launch_wgrad(a, ks, stride, dw, st)); return 0; });
+        return push_bwd([=](mc_handle *hh, hipStream_t st) { HIPCHK(hh, launch_wgrad(a, ks, stride, dw, st)); return 0; }, ON_SIDE);
     }
 
-    // BN(+ReLU)(+residual) backward: returns dy (gradient wrt the raw conv output)
-    Tensor bn_backward(const Rec &r, const std::string &bn) {
+    // BN(+ReLU)(+residual) backward, ONE step.  dy: the gradient wrt the raw conv output.  caller_forms_dy: the caller
+    // consumes (d, y, coef) itself (the stem, whose dY is read by its weight gradient only) -- honoured on the
+    // backward-statistics-epilogue path, where affine_skipped reports it: dy.p is then the masked gradient d, dy.amax max |d|
+    struct BnBwd { Tensor dy; float *coef; bool affine_skipped; };
+    BnBwd bn_backward(const Rec &r, const std::string &bn, bool caller_forms_dy = false) {
         TNode &zn = ts->nodes[r.z];
         Tensor dy = r.y;
         // dY (the gradient wrt the raw conv output) is written IN PLACE over dZ: the affine pass is elementwise and the
@@ -570,19 +686,18 @@ struct TB {   // train plan builder
         if (r.res >= 0 && ts->nodes[r.res].needs_grad) {
             gres = g_acquire(r.res);
             gmode = ts->nodes[r.res].ginit ? 2 : 1;
-            ts->nodes[r.res].ginit = true;
-            ts->nodes[r.res].last_conv = nullptr; ts->nodes[r.res].last_pool = nullptr;
+            wrote(r.res);
         }
         const double n = (double)B * rows;
-        // every branch below only decides where the (sum d, sum d*y) partials come from; this pushes the ONE closure of the
+        // every branch below only decides where the (sum d, sum d*y) partials come from; this pushes the ONE step of the
         // BatchNorm backward: the reduction pass (reduce: no launch of the step left them), bn_bwd_finalize, and the
         // affine pass (dZ -> dY in place, the residual's share; it applies the ReLU mask only after the reduction pass --
         // a launch that leaves the partials has masked the gradient already)
-        auto closure = [&](float *partial, int nbp, int cstride, bool reduce, bool affine) {
+        auto step = [&](float *partial, int nbp, int cstride, bool reduce, bool affine) {
             double *fold = fold_scratch(nbp, C);  // (61 440 partial rows at full resolution: 16 workgroups walking them took 87 us)
             const int arelu = reduce ? relu : 0;
             const float *aa = reduce ? fa : nullptr, *ab = reduce ? fb : nullptr;
-            ts->bwd.push_back([=](mc_handle *hh, hipStream_t st) {
+            push_bwd([=](mc_handle *hh, hipStream_t st) {
                 if (reduce) HIPCHK(hh, launch_chan_reduce(yp, gz, zp, nullptr, B, rows, C, 1, relu, partial, C, st, fa, fb));
                 HIPCHK(hh, launch_bn_bwd_finalize(partial, nbp, cstride, n, C, gamma, mean, rstd, dg, db, coef, st, fold));
                 if (affine)
@@ -590,16 +705,14 @@ struct TB {   // train plan builder
                                                  nullptr, dymax));
                 return 0;
             });
-            return dy;
+            return BnBwd{dy, coef, !affine};
         };
-        ConvArgs *lc = zn.last_conv;
+        const LastWriter last = zn.last;
+        ConvArgs *lc = last.kind == LastWriter::DGRAD_CONV ? last.conv : nullptr;
         // MONOCON_HIP_BM_EPILOGUE: 0 = never take over the reductions in the data gradient's epilogue (always the reduction
         // pass), N > 1 = only for maps of at most N pixels per image
-        {
-            static const int bm_mode = [] { const char *e = std::getenv("MONOCON_HIP_BM_EPILOGUE"); return e ? std::atoi(e) : 1; }();
-            if (bm_mode == 0 || (bm_mode > 1 && r.y.H * r.y.W > bm_mode)) lc = nullptr;
-        }
-        if (std::getenv("MONOCON_HIP_PLAN_DEBUG"))
+        if (sw.bm_epilogue == 0 || (sw.bm_epilogue > 1 && r.y.H * r.y.W > sw.bm_epilogue)) lc = nullptr;
+        if (sw.plan_debug)
             fprintf(stderr, "[plan] bn_backward %-40s %4d ch %4dx%-4d relu %d res %d last-writer-conv %d\n", bn.c_str(), C, r.y.H,
                     r.y.W, relu, r.res >= 0, lc != nullptr);
         if (lc && lc->out == zn.g && lc->Cout == C && lc->out_ld == C && lc->Hout == r.y.H && lc->Wout == r.y.W && !lc->stats) {
@@ -610,200 +723,102 @@ struct TB {   // train plan builder
             lc->stats = partial;
             lc->bm_y = yp; lc->bm_z = zp; lc->bm_a = fa; lc->bm_b = fb; lc->bm_relu = relu;
             lc->bm_zbits = relu == 1 ? r.zbits : nullptr;
-            if (wres_bwd >= 1 && !(lc->cfg & (CFG_SMALL | CFG_WS)) && conv_wres_ok(*lc, 3, 1)) lc->cfg |= CFG_WRES;      // (see emit_dgrad)
-            if (std::getenv("MONOCON_HIP_PLAN_DEBUG"))
+            if (sw.wres_bwd >= 1 && !(lc->cfg & (CFG_SMALL | CFG_WS)) && conv_wres_ok(*lc, 3, 1)) lc->cfg |= CFG_WRES;      // (see emit_dgrad)
+            if (sw.plan_debug)
                 fprintf(stderr, "[plan]   twin of %-36s cfg %3d  K %4d  Cout %3d  %dx%d  res %d  nsrc %d srcC %d wres %d\n", bn.c_str(), lc->cfg,
                         lc->Cin, lc->Cout, lc->Hout, lc->Wout, lc->res != nullptr, lc->nsrc, lc->src[0].C, (lc->cfg & CFG_WRES) != 0);
-            const bool skip_affine = want_skip_affine && !gres;
-            if (skip_affine) {
-                // the epilogue also leaves max |d| (for the consumer's operand scale); only the coefficients are computed here:
-                // dy.p = the masked gradient d, dy.amax = max |d|
-                lc->amax_out = dymax;
-                did_skip_affine = true;
-                skip_coef = coef;
-            }
-            return closure(partial, nbp, cstride, false, !skip_affine);
+            const bool skip_affine = caller_forms_dy && !gres;
+            // the epilogue then also leaves max |d| (for the consumer's operand scale); only the coefficients are computed here
+            if (skip_affine) lc->amax_out = dymax;
+            return step(partial, nbp, cstride, false, !skip_affine);
         }
         // the gradient of this map was completed by a max-pool backward over a LAZY map (it holds y, forms z for its window
-        // comparison anyway): that launch masks the total and leaves the partials -- no reduction pass (MONOCON_HIP_POOL_STATS=0: off)
-        {
-            const bool pool_stats = [] { const char *e = std::getenv("MONOCON_HIP_POOL_STATS"); return !e || std::atoi(e) != 0; }();
-            PoolBwdArgs *pl = zn.last_pool;
-            if (pool_stats && pl && relu == 2 && pl->la == fa && pl->lb == fb && pl->x == yp && pl->acc && pl->dx == zn.g && pl->C == C &&
-                pl->H * pl->W == rows && !pl->stats && !want_skip_affine && C % 4 == 0 && 256 % (C / 4) == 0) {
-                const int nbp = maxpool2_bwd_blocks(B, pl->H, pl->W, C);
-                float *partial = alloc((size_t)nbp * C * 2);
-                pl->stats = partial;
-                if (std::getenv("MONOCON_HIP_PLAN_DEBUG"))
-                    fprintf(stderr, "[plan]   statistics of %-36s left by the max-pool backward (%d partial rows)\n", bn.c_str(), nbp);
-                return closure(partial, nbp, C, false, true);
-            }
+        // comparison anyway): that launch masks the total and leaves the partials -- no reduction pass
+        PoolBwdArgs *pl = last.kind == LastWriter::POOL_BWD ? last.pool : nullptr;
+        if (pl && relu == 2 && pl->la == fa && pl->lb == fb && pl->x == yp && pl->acc && pl->dx == zn.g && pl->C == C &&
+            pl->H * pl->W == rows && !pl->stats && !caller_forms_dy && C % 4 == 0 && 256 % (C / 4) == 0) {
+            const int nbp = maxpool2_bwd_blocks(B, pl->H, pl->W, C);
+            float *partial = alloc((size_t)nbp * C * 2);
+            pl->stats = partial;
+            if (sw.plan_debug)
+                fprintf(stderr, "[plan]   statistics of %-36s left by the max-pool backward (%d partial rows)\n", bn.c_str(), nbp);
+            return step(partial, nbp, C, false, true);
         }
         // ... or by the fused backward of the depthwise deconv that is its only consumer (neck proj -> up): same contract
-        if (float **ds = zn.last_deconv_stats) {
-            const bool dc_stats = [] { const char *e = std::getenv("MONOCON_HIP_DECONV_STATS"); return !e || std::atoi(e) != 0; }();
-            if (dc_stats && relu == 2 && zn.la == fa && zn.lb == fb && !*ds && !want_skip_affine && !gres) {
-                const int nbp = B * r.y.H;            // one workgroup per (image, row) of the deconv's input
-                float *partial = alloc((size_t)nbp * C * 2);
-                *ds = partial;
-                if (std::getenv("MONOCON_HIP_PLAN_DEBUG"))
-                    fprintf(stderr, "[plan]   statistics of %-36s left by the deconv backward (%d partial rows)\n", bn.c_str(), nbp);
-                return closure(partial, nbp, C, false, true);       // (gres is null here)
-            }
+        float **ds = last.kind == LastWriter::DECONV_BWD ? last.deconv_stats : nullptr;
+        if (ds && relu == 2 && zn.la == fa && zn.lb == fb && !*ds && !caller_forms_dy && !gres) {
+            const int nbp = B * r.y.H;            // one workgroup per (image, row) of the deconv's input
+            float *partial = alloc((size_t)nbp * C * 2);
+            *ds = partial;
+            if (sw.plan_debug)
+                fprintf(stderr, "[plan]   statistics of %-36s left by the deconv backward (%d partial rows)\n", bn.c_str(), nbp);
+            return step(partial, nbp, C, false, true);       // (gres is null here)
         }
         const int nb = chan_reduce_blocks(B, rows);
-        return closure(alloc((size_t)nb * C * 2), nb, C, true, true);
+        return step(alloc((size_t)nb * C * 2), nb, C, true, true);
     }
-};
 
-}  // namespace
-
-// ------------------------------------------------------------------------------------ build
-static TrainState *build_train(mc_handle *h, int B, int H, int W, bool head_only = false) {
-    std::unique_ptr<TrainState, void (*)(TrainState *)> tsp(new TrainState(), train_free);
-    TrainState *ts = tsp.get();
-    ts->B = B; ts->H = H; ts->W = W; ts->bind_gen = h->bind_gen; ts->head_only = head_only;
-    TB b{h, ts};
-    const int fh = H / 4, fw = W / 4, HW = fh * fw;
-    int feat = -1;
-    if (h->prec == 3) {      // the max-|x| slots start every forward at zero: their producers only raise them
-        (void)b.slot();
-        --ts->mem.amax_used;
-        ts->fwd.push_back([=](mc_handle *hh, hipStream_t st) {
-            HIPCHK(hh, hipMemsetAsync(ts->mem.amax_arena, 0, (size_t)ts->mem.amax_used * AMAX_WORDS * sizeof(unsigned), st));
-            return 0;
-        });
-    }
-    if (head_only) {
-        // the heads on their own (MonoConDenseHeads.forward_train, monocon_heads.py:150-157): the neck output is an
-        // external NCHW tensor, copied into the plan's NHWC node; its gradient is copied out after the backward
-        feat = b.node(B, fh, fw, 64, true);
-        float *fp = ts->nodes[feat].t.p;
-        unsigned *fmax = ts->nodes[feat].t.amax;
-        ts->fwd.push_back([=](mc_handle *hh, hipStream_t st) {
-            HIPCHK(hh, launch_nchw_to_nhwc(ts->feat_ext, B, 64, fh, fw, fp, st));
-            if (fmax) HIPCHK(hh, launch_absmax(fp, (size_t)B * fh * fw * 64, fmax, st));
-            return 0;
-        });
-    } else {
-
-    // ---- stem (raw conv -> batch stats -> normalise + ReLU)
-    Rec stem;
-    stem.kind = REC_STEM; stem.bn = "backbone.base_layer.1"; stem.relu = true;
-    stem.y.B = B; stem.y.H = H; stem.y.W = W; stem.y.C = 16;
-    stem.y.p = b.alloc(stem.y.numel());
-    // (mode 3 with the fp16-pipe stem, which leaves max |y|: the stem's activation is lazy like conv_bn's, TNode::la)
-    const bool stem_lazy = h->prec == 3 && stem_f16_enabled() && (b.lazy_mask & 1);
-    stem.z = b.node(B, H, W, 16, true, !stem_lazy);
-    float *ones16 = b.alloc(16), *zeros16 = b.alloc(16);
-    {
-        std::vector<float> one(16, 1.f);
-        if (!h->dry_alloc && hipMemcpy(ones16, one.data(), 64, hipMemcpyHostToDevice) != hipSuccess) ts->ok = false;
-        // mode 3: the fp16-pipe stem leaves the (sum, sum of squares) partials per output row itself; the other modes reduce
-        // the raw map in a second pass
-        const bool fused_stats = h->prec == 3 && stem_f16_enabled();
-        const int nb = fused_stats ? B * H : chan_reduce_blocks(B, H * W);
-        float *partial = b.alloc((size_t)nb * 16 * 2), *ca = b.alloc(16), *cb = b.alloc(16);
-        stem.mean = b.alloc(16); stem.rstd = b.alloc(16);
-        float *yp = stem.y.p, *zp = ts->nodes[stem.z].t.p, *rm = b.P(stem.bn + ".running_mean", 16);
-        unsigned *zmax = ts->nodes[stem.z].t.amax;
-        unsigned *imax = fused_stats ? b.slot() : nullptr;     // max |image|, left by the forward stem for its weight gradient
-        ts->img_amax = imax;
-        unsigned *ymax = fused_stats ? b.slot() : nullptr;     // max |raw stem output|: operand-scale bound of the fused weight gradient
-        stem.y.amax = ymax;
-        const float *sw = h->stem_w;
-        ts->fwd.push_back([=](mc_handle *hh, hipStream_t st) {
-            if (fused_stats) {
-                HIPCHK(hh, launch_stem_f16(ts->img, B, H, W, sw, ones16, zeros16, yp, st, 0, ymax, partial, rm, imax));
-            } else {
-                HIPCHK(hh, launch_stem(ts->img, B, H, W, sw, ones16, zeros16, yp, st, 0, hh->prec));
-                HIPCHK(hh, launch_chan_reduce(yp, nullptr, nullptr, rm, B, H * W, 16, 0, 0, partial, 16, st));
-            }
-            return 0;
-        });
-        b.bn_train_ops(stem.y, partial, nb, 16, stem.bn, 1e-5f, 0.1f, ca, cb, stem.mean, stem.rstd, stem_lazy ? ymax : nullptr,
-                       stem_lazy ? zmax : nullptr, 1);
-        stem.ca = ca; stem.cb = cb;
-        if (stem_lazy) {
-            TNode &zn = ts->nodes[stem.z];
-            zn.t.p = yp; zn.la = ca; zn.lb = cb; zn.lrelu = true;
-            ++b.n_lazy;
-        } else {
-            ts->fwd.push_back([=](mc_handle *hh, hipStream_t st) {
-                HIPCHK(hh, launch_affine_act(yp, ca, cb, nullptr, B, (size_t)H * W, 16, 0, 1, zp, st, zmax));
-                return 0;
-            });
-        }
-        ts->recs.push_back(stem);
-    }
-    // ---- backbone and neck: the steps of the network graph (the nodes they make are the graph's; node 0 is the stem's)
-    for (const NetStep &s : h->net.steps) {
-        const int o = s.kind == STEP_CONV ? b.conv_bn(s) : s.kind == STEP_POOL ? b.pool(s.srcs[0]) : b.deconv(h->deconvs[s.name], s.srcs[0]);
-        if (o != s.out) { ts->ok = false; h->err = "train plan: node order differs from the network graph"; }
-    }
-    feat = h->net.feat;
-    }   // !head_only
-
-    // ---- heads
-    const int CP = NUM_HEADS * HEAD_CH, LD = 80;
-    Tensor xh; xh.B = B; xh.H = fh; xh.W = fw; xh.C = CP; xh.p = b.alloc(xh.numel());
-    // (round 2: the normalised hidden maps are no longer stored -- head_bwd_kernel recomputes relu(scale*x + shift) from the
-    //  conv output it reads anyway: one 2.3 GB write and one 2.3 GB read per step less)
-
-    Tensor raw; raw.B = B; raw.H = fh; raw.W = fw; raw.C = LD; raw.p = b.alloc(raw.numel());
+    // ---------------------------------------------------------------- heads
+    static constexpr int CP = NUM_HEADS * HEAD_CH, LD = 80;
+    Tensor xh;                 // the hidden maps of the nine heads (output of the fused 64 -> 576 conv); the normalised maps are
+                               // not stored: head_bwd_kernel recomputes relu(scale*x + shift) from the conv output it reads anyway
     AttnTrainArgs at{};
     AttnGradPtrs gp{};
-    for (int hd = 0; hd < NUM_HEADS; ++hd) {
-        const std::string an = std::string("head.") + HEAD_NAMES[hd] + ".1";
-        const int A = NUM_AFFINE, AC = NUM_AFFINE * HEAD_CH;
-        at.rm[hd] = b.P(an + ".running_mean", HEAD_CH); at.rv[hd] = b.P(an + ".running_var", HEAD_CH);
-        at.nbt[hd] = b.NBT(an + ".num_batches_tracked");
-        at.att_w[hd] = b.P(an + ".attn_weights.attention.0.weight", AC);
-        at.att_g[hd] = b.P(an + ".attn_weights.attention.1.weight", A);
-        at.att_b[hd] = b.P(an + ".attn_weights.attention.1.bias", A);
-        at.att_rm[hd] = b.P(an + ".attn_weights.attention.1.running_mean", A);
-        at.att_rv[hd] = b.P(an + ".attn_weights.attention.1.running_var", A);
-        at.att_nbt[hd] = b.NBT(an + ".attn_weights.attention.1.num_batches_tracked");
-        at.weight_[hd] = b.P(an + ".weight_", AC); at.bias_[hd] = b.P(an + ".bias_", AC);
-        gp.d_weight_[hd] = b.G(an + ".weight_", AC); gp.d_bias_[hd] = b.G(an + ".bias_", AC);
-        gp.d_att_w[hd] = b.G(an + ".attn_weights.attention.0.weight", AC);
-        gp.d_att_g[hd] = b.G(an + ".attn_weights.attention.1.weight", A);
-        gp.d_att_b[hd] = b.G(an + ".attn_weights.attention.1.bias", A);
-    }
-    ConvArgs c3{};
-    {
+    float *w3dense = nullptr;  // dense OIHW (576,64,3,3) copy of the nine head convs for the dgrad panel
+    size_t raw_numel = 0;
+
+    void heads_forward(int feat) {
+        xh.B = B; xh.H = fh; xh.W = fw; xh.C = CP; xh.p = alloc(xh.numel());
+        Tensor raw; raw.B = B; raw.H = fh; raw.W = fw; raw.C = LD; raw.p = alloc(raw.numel());
+        raw_numel = raw.numel();
+        for (int hd = 0; hd < NUM_HEADS; ++hd) {
+            const std::string an = std::string("head.") + HEAD_NAMES[hd] + ".1";
+            const int A = NUM_AFFINE, AC = NUM_AFFINE * HEAD_CH;
+            at.rm[hd] = P(an + ".running_mean", HEAD_CH); at.rv[hd] = P(an + ".running_var", HEAD_CH);
+            at.nbt[hd] = NBT(an + ".num_batches_tracked");
+            at.att_w[hd] = P(an + ".attn_weights.attention.0.weight", AC);
+            at.att_g[hd] = P(an + ".attn_weights.attention.1.weight", A);
+            at.att_b[hd] = P(an + ".attn_weights.attention.1.bias", A);
+            at.att_rm[hd] = P(an + ".attn_weights.attention.1.running_mean", A);
+            at.att_rv[hd] = P(an + ".attn_weights.attention.1.running_var", A);
+            at.att_nbt[hd] = NBT(an + ".attn_weights.attention.1.num_batches_tracked");
+            at.weight_[hd] = P(an + ".weight_", AC); at.bias_[hd] = P(an + ".bias_", AC);
+            gp.d_weight_[hd] = G(an + ".weight_", AC); gp.d_bias_[hd] = G(an + ".bias_", AC);
+            gp.d_att_w[hd] = G(an + ".attn_weights.attention.0.weight", AC);
+            gp.d_att_g[hd] = G(an + ".attn_weights.attention.1.weight", A);
+            gp.d_att_b[hd] = G(an + ".attn_weights.attention.1.bias", A);
+        }
+        ConvArgs c3{};
         c3.nsrc = 1;
-        b.fill_src(c3.src[0], feat);
+        fill_src(c3.src[0], feat);
         const TNode &fn = ts->nodes[feat];
         c3.B = B; c3.Hin = fh; c3.Win = fw; c3.Hout = fh; c3.Wout = fw; c3.Cin = 64; c3.Cout = CP; c3.CoutP = h->head3.coutp;
         c3.wpk = h->head3.wpk; c3.bias = h->head_bias; c3.out = xh.p; c3.out_ld = CP; c3.cfg = h->head3.cfg;
         c3.wpk16 = h->head3.wpk16; c3.prec = h->prec;
         if (h->prec == 3) { c3.amax_in[0] = fn.t.amax; c3.amax_w = h->head3.w_amax; }
         if (c3.src[0].la && (!fn.lrelu || !conv_lazy_capable(c3, 3, 1))) {
-            b.materialise(feat);
-            b.fill_src(c3.src[0], feat);
+            materialise(feat);
+            fill_src(c3.src[0], feat);
         }
         at.chunks = conv_chunks_per_image(c3.cfg, fh, fw);
         at.stat_ld = h->head3.coutp;
-        float *stats = b.alloc((size_t)B * at.chunks * at.stat_ld * 2);
+        float *stats = alloc((size_t)B * at.chunks * at.stat_ld * 2);
         c3.stats = stats; c3.stat_shift = h->head_rm;
         at.stats = stats; at.B = B; at.HW = HW;
-        at.stats64 = reinterpret_cast<double *>(b.alloc((size_t)B * at.stat_ld * 4));   // [B][stat_ld][2] doubles
-        at.sv_inst = b.alloc((size_t)B * CP * 3); at.mu_r = b.alloc((size_t)CP * 2); at.bn10 = b.alloc(NUM_HEADS * NUM_AFFINE * 2);
-        at.that = b.alloc((size_t)B * NUM_HEADS * NUM_AFFINE); at.yatt = b.alloc((size_t)B * NUM_HEADS * NUM_AFFINE);
-        at.gamma_p = b.alloc((size_t)B * CP); at.scale = b.alloc((size_t)B * CP); at.shift = b.alloc((size_t)B * CP);
-    }
-    float *w3dense = b.alloc((size_t)CP * 64 * 9);
-    // AttnBN apply + ReLU + the nine 1x1 convs + prediction epilogues in ONE pass over the hidden maps
-    // (head_apply_kernel, the inference kernel), which also stores the normalised maps for the backward
-    HeadApplyArgs ha{};
-    {
+        at.stats64 = reinterpret_cast<double *>(alloc((size_t)B * at.stat_ld * 4));   // [B][stat_ld][2] doubles
+        at.sv_inst = alloc((size_t)B * CP * 3); at.mu_r = alloc((size_t)CP * 2); at.bn10 = alloc(NUM_HEADS * NUM_AFFINE * 2);
+        at.that = alloc((size_t)B * NUM_HEADS * NUM_AFFINE); at.yatt = alloc((size_t)B * NUM_HEADS * NUM_AFFINE);
+        at.gamma_p = alloc((size_t)B * CP); at.scale = alloc((size_t)B * CP); at.shift = alloc((size_t)B * CP);
+        w3dense = alloc((size_t)CP * 64 * 9);
+        // AttnBN apply + ReLU + the nine 1x1 convs + prediction epilogues in ONE pass over the hidden maps
+        // (head_apply_kernel, the inference kernel)
+        HeadApplyArgs ha{};
         ha.hidden = xh.p; ha.scale = at.scale; ha.shift = at.shift; ha.w = h->head_w1t; ha.b = h->head_b1;
         ha.B = B; ha.HW = HW; ha.z_out = nullptr;
         for (int i = 0; i < 10; ++i) ha.pred_c[i] = PRED_CH[i];     // the prediction pointers are per call (ts->preds)
         // one closure per kernel family so that mc_profile_train attributes the durations correctly
         ts->fwd.push_back([=](mc_handle *hh, hipStream_t st) { HIPCHK(hh, launch_conv(c3, 3, 1, st)); return 0; });
-        ts->fwd.push_back([=](mc_handle *hh, hipStream_t st) {
+        ts->fwd.push_back([=, ts = ts, at = at](mc_handle *hh, hipStream_t st) {
             HIPCHK(hh, launch_attn_train_fwd(at, st));
             HeadApplyArgs a2 = ha;
             for (int i = 0; i < 10; ++i) a2.pred[i] = ts->preds[i];
@@ -811,8 +826,9 @@ static TrainState *build_train(mc_handle *h, int B, int H, int W, bool head_only
             return 0;
         });
     }
-    // targets + losses
-    {
+
+    // ---- targets + losses
+    void targets_and_losses() {
         mc_targets &T = ts->targets;
         const size_t R = (size_t)B * ts->max_objs;
         // one arena for the targets, one for the regression-gradient maps (single zero fill each)
@@ -821,7 +837,7 @@ static TrainState *build_train(mc_handle *h, int B, int H, int W, bool head_only
                                R * 2, R * 18, R / 4 + 1, R * 18, R * 18};
         size_t ttot = 0;
         for (size_t n : tn) ttot += up(n);
-        float *ta = b.alloc(ttot);
+        float *ta = alloc(ttot);
         float *tp[15];
         { size_t o = 0; for (int i = 0; i < 15; ++i) { tp[i] = ta ? ta + o : nullptr; o += up(tn[i]); } }
         T.center_heatmap_target = tp[0]; T.kpt_heatmap_target = tp[1];
@@ -832,27 +848,26 @@ static TrainState *build_train(mc_handle *h, int B, int H, int W, bool head_only
         T.mask_target = reinterpret_cast<uint8_t *>(tp[12]);
         T.mask_center2kpt_offset = tp[13]; T.mask_kpt_heatmap_offset = tp[14];
         h->tgt_arena = ta; h->tgt_arena_bytes = ttot * sizeof(float);
-        ts->dpred[0] = b.alloc((size_t)B * PRED_CH[0] * HW);
-        ts->dpred[1] = b.alloc((size_t)B * PRED_CH[1] * HW);
+        ts->dpred[0] = alloc((size_t)B * PRED_CH[0] * HW);
+        ts->dpred[1] = alloc((size_t)B * PRED_CH[1] * HW);
         size_t dtot = 0;
         for (int i = 2; i < 10; ++i) dtot += up((size_t)B * PRED_CH[i] * HW);
-        float *da = b.alloc(dtot);
+        float *da = alloc(dtot);
         { size_t o = 0; for (int i = 2; i < 10; ++i) { ts->dpred[i] = da ? da + o : nullptr; o += up((size_t)B * PRED_CH[i] * HW); } }
         h->dp_arena = da; h->dp_arena_bytes = dtot * sizeof(float);
-        ts->fwd.push_back([=](mc_handle *hh, hipStream_t st) {
+        ts->fwd.push_back([ts = ts, B = B, fh = fh, fw = fw](mc_handle *hh, hipStream_t st) {
             if (mc_make_targets(hh, &ts->labels, B, ts->max_objs, ts->pad_h, ts->pad_w, fh, fw, &ts->targets, st)) return -1;
             if (mc_losses(hh, ts->preds, &ts->targets, B, ts->max_objs, fh, fw, ts->losses, st)) return -1;
             return 0;
         });
     }
 
-    // ===================================================================== backward
-    // ---- losses -> raw gradients -> heads
-    {
-        float *draw = b.alloc(raw.numel());
-        float *cs1 = b.alloc(colsum_partial_floats((size_t)B * HW, LD));
-        float *db1 = b.alloc(NUM_OUT_ROWS), *dw1 = b.alloc((size_t)NUM_OUT_ROWS * HEAD_CH);
-        ts->bwd.push_back([=](mc_handle *hh, hipStream_t st) {
+    // ---- losses -> raw gradients -> heads -> the gradient of feat
+    void heads_backward(int feat) {
+        float *draw = alloc(raw_numel);
+        float *cs1 = alloc(colsum_partial_floats((size_t)B * HW, LD));
+        float *db1 = alloc(NUM_OUT_ROWS), *dw1 = alloc((size_t)NUM_OUT_ROWS * HEAD_CH);
+        push_bwd([=, ts = ts, B = B, fh = fh, fw = fw, HW = HW](mc_handle *hh, hipStream_t st) {
             if (mc_losses_backward(hh, ts->preds, &ts->targets, B, ts->max_objs, fh, fw, ts->grad_losses, ts->dpred, st)) return -1;
             // a caller's gradients wrt the maps enter here, in the same pass: everything downstream starts from draw
             bool user = false;
@@ -867,216 +882,209 @@ static TrainState *build_train(mc_handle *h, int B, int H, int W, bool head_only
         // the nine 1x1 convs backwards in one pass (head_bwd_kernel): weight-gradient partials, the ReLU-masked
         // data gradient d, and the (sum d, sum d*x) partials of the AttnBN backward
         const int nbr = chan_reduce_blocks(B, HW), rb_per_img = nbr / B;
-        // MONOCON_HIP_HEAD_DX_FUSE=0: round 4's passes (head_bwd_kernel stores the masked gradient d, affine_bwd_kernel reads it
-        // back).  Default: d is never stored -- the AttnBN backward forms it again from the 65 raw-gradient rows
+        // MONOCON_HIP_HEAD_DX_FUSE=0: head_bwd_kernel stores the masked gradient d, affine_bwd_kernel reads it back.
+        // Default: d is never stored -- the AttnBN backward forms it again from the 65 raw-gradient rows
         // (launch_head_dx; 7 fma per element on average against 4.3 GB less traffic per step at B = 32)
-        const bool dx_fuse = [] { const char *e = std::getenv("MONOCON_HIP_HEAD_DX_FUSE"); return !e || std::atoi(e) != 0; }();
-        float *dh = b.alloc(xh.numel());
-        float *dw1p = b.alloc((size_t)nbr * NUM_OUT_ROWS * HEAD_CH);
-        float *partial = b.alloc((size_t)nbr * CP * 2), *coef = b.alloc((size_t)B * CP * 4);
+        const bool dx_fuse = sw.head_dx_fuse != 0;
+        float *dh = alloc(xh.numel());
+        float *dw1p = alloc((size_t)nbr * NUM_OUT_ROWS * HEAD_CH);
+        float *partial = alloc((size_t)nbr * CP * 2), *coef = alloc((size_t)B * CP * 4);
         float *dx = dh;        // the AttnBN backward (an elementwise affine pass) runs in place on the masked gradient
         // scatter dw1 / db1 rows to the parameter gradient tensors (rows are in concatenation order)
         const int *rb = head_row_begin();
-        struct Seg { float *dst_w, *dst_b; int r0, nr; };
-        std::vector<Seg> segs;
-        for (int hd = 0; hd < 8; ++hd) {
-            const int nr = rb[hd + 1] - rb[hd];
-            segs.push_back(Seg{b.G(std::string("head.") + HEAD_NAMES[hd] + ".3.weight", nr * HEAD_CH),
-                               b.G(std::string("head.") + HEAD_NAMES[hd] + ".3.bias", nr), rb[hd], nr});
-        }
-        segs.push_back(Seg{b.G("head.dir_cls.0.weight", 12 * HEAD_CH), b.G("head.dir_cls.0.bias", 12), rb[8], 12});
-        segs.push_back(Seg{b.G("head.dir_reg.0.weight", 12 * HEAD_CH), b.G("head.dir_reg.0.bias", 12), rb[8] + 12, 12});
         CopyBatch segcb;
-        for (const Seg &s : segs) {
-            if (!segcb.add(dw1 + (size_t)s.r0 * HEAD_CH, s.dst_w, (size_t)s.nr * HEAD_CH) || !segcb.add(db1 + s.r0, s.dst_b, s.nr))
+        auto seg = [&](const std::string &layer, int r0, int nr) {
+            if (!segcb.add(dw1 + (size_t)r0 * HEAD_CH, G(layer + ".weight", nr * HEAD_CH), (size_t)nr * HEAD_CH) ||
+                !segcb.add(db1 + r0, G(layer + ".bias", nr), nr))
                 ts->ok = false;
-        }
-        {
-            const float *xp = xh.p, *w1 = h->head_w1, *zsc = at.scale, *zsh = at.shift;
-            ts->bwd.push_back([=](mc_handle *hh, hipStream_t st) {
-                HIPCHK(hh, launch_head_bwd(draw, LD, nullptr, xp, w1, B, HW, nbr, dx_fuse ? nullptr : dh, dw1p, partial, st, zsc, zsh));
-                HIPCHK(hh, launch_splitk_reduce(dw1p, nbr, 1, NUM_OUT_ROWS, HEAD_CH, dw1, st));
-                HIPCHK(hh, launch_copy_batch(segcb, st));
-                return 0;
-            });
-        }
-        float *db3 = b.alloc(CP), *dw3 = b.alloc((size_t)CP * 64 * 9);
-        float *cs3 = b.alloc((size_t)std::max(affine_bwd_blocks(B, (size_t)HW, CP), nbr) * CP * 2);
-        Tensor dxT = xh; dxT.p = dx; dxT.amax = b.slot();
+        };
+        for (int hd = 0; hd < 8; ++hd) seg(std::string("head.") + HEAD_NAMES[hd] + ".3", rb[hd], rb[hd + 1] - rb[hd]);
+        seg("head.dir_cls.0", rb[8], 12);
+        seg("head.dir_reg.0", rb[8] + 12, 12);
+        const float *xp = xh.p, *w1 = h->head_w1, *zsc = at.scale, *zsh = at.shift;
+        push_bwd([=, B = B, HW = HW](mc_handle *hh, hipStream_t st) {
+            HIPCHK(hh, launch_head_bwd(draw, LD, nullptr, xp, w1, B, HW, nbr, dx_fuse ? nullptr : dh, dw1p, partial, st, zsc, zsh));
+            HIPCHK(hh, launch_splitk_reduce(dw1p, nbr, 1, NUM_OUT_ROWS, HEAD_CH, dw1, st));
+            HIPCHK(hh, launch_copy_batch(segcb, st));
+            return 0;
+        });
+        float *db3 = alloc(CP), *dw3 = alloc((size_t)CP * 64 * 9);
+        float *cs3 = alloc((size_t)std::max(affine_bwd_blocks(B, (size_t)HW, CP), nbr) * CP * 2);
+        Tensor dxT = xh; dxT.p = dx; dxT.amax = slot();
         unsigned *dxmax = dxT.amax;
-        {
-            const float *xp = xh.p, *w1h = h->head_w1, *zsc2 = at.scale, *zsh2 = at.shift;
-            ts->bwd.push_back([=](mc_handle *hh, hipStream_t st) {
-                // d is already masked: the AttnBN backward is the plain per-(image, channel) affine map; the same pass
-                // leaves the column sums of dx (the 3x3 convs' bias gradients) instead of a second read of dx
-                HIPCHK(hh, launch_attn_train_bwd(at, partial, rb_per_img, gp, coef, st));
-                if (dx_fuse)
-                    HIPCHK(hh, launch_head_dx(draw, LD, xp, w1h, coef, B, HW, nbr, dx, cs3, db3, dxmax, st, zsc2, zsh2));
-                else
-                    HIPCHK(hh, launch_affine_bwd(dh, nullptr, xp, coef, B, (size_t)HW, CP, 1, 0, dx, nullptr, 0, st, nullptr, nullptr, cs3, db3,
-                                                 dxmax));
-                return 0;
-            });
-        }
+        push_bwd([=, at = at, gp = gp, B = B, HW = HW](mc_handle *hh, hipStream_t st) {
+            // d is already masked: the AttnBN backward is the plain per-(image, channel) affine map; the same pass
+            // leaves the column sums of dx (the 3x3 convs' bias gradients) instead of a second read of dx
+            HIPCHK(hh, launch_attn_train_bwd(at, partial, rb_per_img, gp, coef, st));
+            if (dx_fuse)
+                HIPCHK(hh, launch_head_dx(draw, LD, xp, w1, coef, B, HW, nbr, dx, cs3, db3, dxmax, st, zsc, zsh));
+            else
+                HIPCHK(hh, launch_affine_bwd(dh, nullptr, xp, coef, B, (size_t)HW, CP, 1, 0, dx, nullptr, 0, st, nullptr, nullptr, cs3, db3,
+                                             dxmax));
+            return 0;
+        });
         // the fused 64 -> 576 weight gradient (2 ms at B = 32, the longest launch of the backward) and the scatter of its
         // result go to the weight-gradient stream like every other layer's: dx is a private buffer, nothing writes it again
-        // in this step (round 4: it used to run on the caller's stream, in front of the whole neck / backbone backward)
-        ts->bwd_side.resize(ts->bwd.size(), 0);
-        b.emit_wgrad({feat}, dxT, CP, CP, 3, 1, dw3);
-        const size_t head_wgrad_first = ts->bwd_side.size();
-        std::vector<float *> g3w, g3b;
-        for (int hd = 0; hd < NUM_HEADS; ++hd) {
-            g3w.push_back(b.G(std::string("head.") + HEAD_NAMES[hd] + ".0.weight", 9 * HEAD_CH * HEAD_CH));
-            g3b.push_back(b.G(std::string("head.") + HEAD_NAMES[hd] + ".0.bias", HEAD_CH));
-        }
+        // in this step
+        emit_wgrad({feat}, dxT, CP, CP, 3, 1, dw3);
         CopyBatch g3cb;
         for (int hd = 0; hd < NUM_HEADS; ++hd) {
-            if (!g3cb.add(dw3 + (size_t)hd * 64 * 64 * 9, g3w[hd], (size_t)64 * 64 * 9) || !g3cb.add(db3 + hd * 64, g3b[hd], 64))
+            const std::string layer = std::string("head.") + HEAD_NAMES[hd] + ".0";
+            if (!g3cb.add(dw3 + (size_t)hd * 64 * 64 * 9, G(layer + ".weight", 9 * HEAD_CH * HEAD_CH), (size_t)64 * 64 * 9) ||
+                !g3cb.add(db3 + hd * 64, G(layer + ".bias", HEAD_CH), 64))
                 ts->ok = false;
         }
-        ts->bwd.push_back([=](mc_handle *hh, hipStream_t st) { HIPCHK(hh, launch_copy_batch(g3cb, st)); return 0; });
-        (void)head_wgrad_first;
-        ts->bwd_side.resize(ts->bwd.size(), 1);
-        // dense OIHW (576,64,3,3) copy of the nine head convs for the dgrad panel
-        std::vector<const float *> w3;
-        for (int hd = 0; hd < NUM_HEADS; ++hd) w3.push_back(b.P(std::string("head.") + HEAD_NAMES[hd] + ".0.weight", 9 * HEAD_CH * HEAD_CH));
+        push_bwd([=](mc_handle *hh, hipStream_t st) { HIPCHK(hh, launch_copy_batch(g3cb, st)); return 0; }, ON_SIDE);
         CopyBatch w3cb;
         for (int hd = 0; hd < NUM_HEADS; ++hd)
-            if (!w3cb.add(w3[hd], w3dense + (size_t)hd * 64 * 64 * 9, (size_t)64 * 64 * 9)) ts->ok = false;
+            if (!w3cb.add(P(std::string("head.") + HEAD_NAMES[hd] + ".0.weight", 9 * HEAD_CH * HEAD_CH), w3dense + (size_t)hd * 64 * 64 * 9,
+                          (size_t)64 * 64 * 9))
+                ts->ok = false;
         ts->pack_fns.push_back([=](mc_handle *hh, hipStream_t st) { HIPCHK(hh, launch_copy_batch(w3cb, st)); return 0; });
         if (h->prec == 3) h->w_amax_of[w3dense] = h->head3.w_amax;     // the dense copy shares the fused head panel's maximum
-        b.emit_dgrad(w3dense, dxT, CP, 64, 3, 1, 0, feat, CP);
-        if (head_only) ts->feat_dgrad_closure = (int)ts->bwd.size() - 1;
+        emit_dgrad(w3dense, dxT, CP, 64, 3, 1, 0, feat, CP);
+        if (ts->head_only) ts->bwd.back().feat_dgrad = true;
     }
-    // everything enqueued so far writes head gradients (bucket 0)
-    ts->bucket_after[0] = (int)ts->bwd.size() - 1;
-    // ---- neck + backbone in reverse forward order
-    for (int ri = (int)ts->recs.size() - 1; ri >= 0; --ri) {
-        const Rec r = ts->recs[ri];
-        struct Mark {      // closures pushed while this record is processed complete gradients of its layer group
-            TrainState *t; int b; size_t n0;
-            ~Mark() { if (t->bwd.size() > n0) t->bucket_after[b] = std::max(t->bucket_after[b], (int)t->bwd.size() - 1); }
-        } mark{ts, mc_grad_bucket_of(r.kind == REC_DECONV ? r.D->name : (r.kind == REC_POOL ? std::string("backbone.") : r.bn)),
-               ts->bwd.size()};
-        if (r.kind == REC_POOL) {
-            TNode &in = ts->nodes[r.in];
-            const TNode &o = ts->nodes[r.z];
-            if (!o.ginit || !in.needs_grad) continue;
-            float *gi = b.g_acquire(r.in);
-            PoolBwdArgs pa{in.t.p, o.g, in.la, in.lb, gi, nullptr, in.t.B, in.t.H, in.t.W, in.t.C, in.ginit ? 1 : 0};     // (lazy x: its ReLU'd values are compared)
-            ts->pool_bwds.push_back(pa);
-            PoolBwdArgs *pp = &ts->pool_bwds.back();
-            ts->bwd.push_back([=](mc_handle *hh, hipStream_t st) {
-                HIPCHK(hh, launch_maxpool2_bwd(pp->x, pp->dout, pp->B, pp->H, pp->W, pp->C, pp->dx, pp->acc, st, pp->la, pp->lb, pp->stats));
-                return 0;
-            });
-            in.last_pool = pp;
-            in.ginit = true;
-            in.last_conv = nullptr;
-            b.g_release(r.z, -1);
-        } else if (r.kind == REC_DECONV) {
-            TNode &in = ts->nodes[r.in];
-            const TNode &o = ts->nodes[r.z];
-            if (!o.ginit) continue;
-            if (in.ginit) { ts->ok = false; h->err = "train plan: deconv input has more than one consumer"; }
-            const float *xp = in.t.p, *go = o.g, *wp = r.D->wpk, *xla = in.la, *xlb = in.lb;
-            float *gi = b.g_acquire(r.in), *dw = b.G(r.D->name + ".weight", (int64_t)r.D->C * 16);
-            const int Bq = in.t.B, Hq = in.t.H, Wq = in.t.W, Cq = in.t.C;
-            float *part = b.alloc(deconv4_bwd_w_partial_floats(Bq, Hq, Cq));
-            // MONOCON_HIP_DECONV_FUSE=0: the data gradient and the weight gradient of the depthwise deconv as two passes (rounds 1-5)
-            const bool dc_fuse = [] { const char *e = std::getenv("MONOCON_HIP_DECONV_FUSE"); return !e || std::atoi(e) != 0; }();
-            ts->deconv_stats.push_back(nullptr);
-            float **dstats = &ts->deconv_stats.back();
-            ts->bwd.push_back([=](mc_handle *hh, hipStream_t st) {
-                if (dc_fuse) {
-                    HIPCHK(hh, launch_deconv4_bwd_w(xp, go, Bq, Hq, Wq, Cq, part, dw, st, xla, xlb, wp, gi, *dstats));
-                } else {
-                    HIPCHK(hh, launch_deconv4_bwd_data(go, Bq, Hq, Wq, Cq, wp, gi, st));
-                    HIPCHK(hh, launch_deconv4_bwd_w(xp, go, Bq, Hq, Wq, Cq, part, dw, st, xla, xlb));
-                }
-                return 0;
-            });
-            in.ginit = true;
-            in.last_conv = nullptr; in.last_pool = nullptr;
-            in.last_deconv_stats = (dc_fuse && xla && xlb) ? dstats : nullptr;
-            b.g_release(r.z, -1);
-        } else if (r.kind == REC_CONV) {
-            if (r.dead || !ts->nodes[r.z].ginit) continue;
-            Tensor dy = b.bn_backward(r, r.bn);
-            ts->bwd_side.resize(ts->bwd.size(), 0);
-            const int64_t wn = (int64_t)r.L->cout * r.L->cin * r.L->ks * r.L->ks;
-            b.emit_wgrad(r.srcs, dy, r.L->cout, r.L->cout, r.L->ks, r.L->stride, b.G(r.L->conv + ".weight", wn));
-            ts->bwd_side.resize(ts->bwd.size(), 1);   // the closure(s) emit_wgrad just added
-            const float *wm = b.P(r.L->conv + ".weight", wn);
-            int c_off = 0;
-            for (int s : r.srcs) {
-                b.emit_dgrad(wm, dy, r.L->cout, r.L->cin, r.L->ks, r.L->stride, c_off, s, r.L->cout);
-                c_off += ts->nodes[s].t.C;
-            }
-            b.g_release(r.z, b.last_side_closure());     // dZ / dY of this layer: last read by its weight gradient
-        } else if (r.kind == REC_STEM) {
-            if (!ts->nodes[r.z].ginit) continue;
-            // mode 3: the stem's dY has ONE reader, its weight gradient -- which forms it on the fly from (d, y, coefficients)
-            // instead of reading what an element-wise pass wrote (MONOCON_HIP_STEM_FUSE=0: the separate pass)
-            static const bool stem_fuse = [] { const char *e = std::getenv("MONOCON_HIP_STEM_FUSE"); return !e || std::atoi(e) != 0; }();
-            b.want_skip_affine = stem_fuse && h->prec == 3 && ts->img_amax && r.y.amax && W % 4 == 0 && W >= 16;
-            b.did_skip_affine = false;
-            Tensor dy = b.bn_backward(r, r.bn);
-            b.want_skip_affine = false;
-            const bool fused = b.did_skip_affine;
-            float *part = b.alloc((size_t)stem_wgrad_blocks(B, H, W) * 147 * 16), *dw = b.G("backbone.base_layer.0.weight", 16 * 147);
-            const float *dyp = dy.p, *yfp = fused ? r.y.p : nullptr, *cfp = fused ? b.skip_coef : nullptr;
-            const unsigned *imax = ts->img_amax, *dymax = dy.amax, *yfmax = fused ? r.y.amax : nullptr;
-            ts->bwd_side.resize(ts->bwd.size(), 0);
-            ts->bwd.push_back([=](mc_handle *hh, hipStream_t st) {
-                HIPCHK(hh, launch_stem_wgrad(ts->img, dyp, B, H, W, part, dw, st, imax, imax ? dymax : nullptr, yfp, cfp, yfmax));
-                return 0;
-            });
-            // MONOCON_HIP_STEM_WGRAD_MAIN=1 (measured, round 6; default off): the stem's weight gradient on the caller's stream.
-            // When it can start (after level0's data gradient and the BatchNorm-backward coefficients) the caller's stream has
-            // nothing left to do while the weight-gradient stream is busy with level0's weight gradient for another 0.8 ms
-            // (rocprofv3: main idle from 46.27 ms of the step, side busy until 47.87) -- yet run side by side the two
-            // front-end weight gradients finish no earlier: 48.77 / 48.82 ms per step (three runs each, one session).  Also
-            // measured neutral in the same round: the data-gradient panels packed on the weight-gradient stream at the head of
-            // the backward instead of on the caller's stream in front of the forward (49.64 / 49.69 ms).
-            static const bool stem_main = [] { const char *e = std::getenv("MONOCON_HIP_STEM_WGRAD_MAIN"); return e && std::atoi(e) != 0; }();
-            ts->bwd_side.resize(ts->bwd.size(), stem_main ? 0 : 1);
-            b.g_release(r.z, stem_main ? -1 : b.last_side_closure());
+
+    // ---------------------------------------------------------------- neck + backbone backwards: one method per record kind
+    void pool_backward(const Rec &r) {
+        TNode &in = ts->nodes[r.in];
+        const TNode &o = ts->nodes[r.z];
+        if (!o.ginit || !in.needs_grad) return;
+        float *gi = g_acquire(r.in);
+        PoolBwdArgs pa{in.t.p, o.g, in.la, in.lb, gi, nullptr, in.t.B, in.t.H, in.t.W, in.t.C, in.ginit ? 1 : 0};     // (lazy x: its ReLU'd values are compared)
+        ts->pool_bwds.push_back(pa);
+        PoolBwdArgs *pp = &ts->pool_bwds.back();
+        push_bwd([=](mc_handle *hh, hipStream_t st) {
+            HIPCHK(hh, launch_maxpool2_bwd(pp->x, pp->dout, pp->B, pp->H, pp->W, pp->C, pp->dx, pp->acc, st, pp->la, pp->lb, pp->stats));
+            return 0;
+        });
+        wrote(r.in, pp);
+        g_release(r.z, -1);
+    }
+
+    // the depthwise deconv: data and weight gradient in one pass
+    void deconv_backward(const Rec &r) {
+        TNode &in = ts->nodes[r.in];
+        const TNode &o = ts->nodes[r.z];
+        if (!o.ginit) return;
+        if (in.ginit) { ts->ok = false; h->err = "train plan: deconv input has more than one consumer"; }
+        const float *xp = in.t.p, *go = o.g, *wp = r.D->wpk, *xla = in.la, *xlb = in.lb;
+        float *gi = g_acquire(r.in), *dw = G(r.D->name + ".weight", (int64_t)r.D->C * 16);
+        const int Bq = in.t.B, Hq = in.t.H, Wq = in.t.W, Cq = in.t.C;
+        float *part = alloc(deconv4_bwd_w_partial_floats(Bq, Hq, Cq));
+        ts->deconv_stats.push_back(nullptr);
+        float **dstats = &ts->deconv_stats.back();
+        push_bwd([=](mc_handle *hh, hipStream_t st) {
+            HIPCHK(hh, launch_deconv4_bwd_w(xp, go, Bq, Hq, Wq, Cq, part, dw, st, xla, xlb, wp, gi, *dstats));
+            return 0;
+        });
+        wrote(r.in, (xla && xlb) ? dstats : nullptr);       // (the statistics need the lazy input's y)
+        g_release(r.z, -1);
+    }
+
+    void conv_backward(const Rec &r) {
+        if (r.dead || !ts->nodes[r.z].ginit) return;
+        const Tensor dy = bn_backward(r, r.bn).dy;
+        const int64_t wn = (int64_t)r.L->cout * r.L->cin * r.L->ks * r.L->ks;
+        const int wgrad = emit_wgrad(r.srcs, dy, r.L->cout, r.L->cout, r.L->ks, r.L->stride, G(r.L->conv + ".weight", wn));
+        const float *wm = P(r.L->conv + ".weight", wn);
+        int c_off = 0;
+        for (int s : r.srcs) {
+            emit_dgrad(wm, dy, r.L->cout, r.L->cin, r.L->ks, r.L->stride, c_off, s, r.L->cout);
+            c_off += ts->nodes[s].t.C;
         }
+        g_release(r.z, wgrad);     // dZ / dY of this layer: last read by its weight gradient
     }
-    if (head_only) {
+
+    void stem_backward(const Rec &r) {
+        if (!ts->nodes[r.z].ginit) return;
+        // mode 3: the stem's dY has ONE reader, its weight gradient -- which forms it on the fly from (d, y, coefficients)
+        // instead of reading what an element-wise pass wrote (MONOCON_HIP_STEM_FUSE=0: the separate pass)
+        const bool want_fused = sw.stem_fuse && h->prec == 3 && ts->img_amax && r.y.amax && W % 4 == 0 && W >= 16;
+        const BnBwd bb = bn_backward(r, r.bn, want_fused);
+        const bool fused = bb.affine_skipped;
+        float *part = alloc((size_t)stem_wgrad_blocks(B, H, W) * 147 * 16), *dw = G("backbone.base_layer.0.weight", 16 * 147);
+        const float *dyp = bb.dy.p, *yfp = fused ? r.y.p : nullptr, *cfp = fused ? bb.coef : nullptr;
+        const unsigned *imax = ts->img_amax, *dymax = bb.dy.amax, *yfmax = fused ? r.y.amax : nullptr;
+        const int wgrad = push_bwd([=, ts = ts, B = B, H = H, W = W](mc_handle *hh, hipStream_t st) {
+            HIPCHK(hh, launch_stem_wgrad(ts->img, dyp, B, H, W, part, dw, st, imax, imax ? dymax : nullptr, yfp, cfp, yfmax));
+            return 0;
+        }, ON_SIDE);
+        g_release(r.z, wgrad);
+    }
+
+    // head-only plan: the gradient of the external feat goes out as NCHW
+    void feat_grad_out(int feat) {
         const float *gp = ts->nodes[feat].g;
-        ts->bwd.push_back([=](mc_handle *hh, hipStream_t st) {
+        push_bwd([=, ts = ts, B = B, fh = fh, fw = fw](mc_handle *hh, hipStream_t st) {
             if (ts->gfeat_ext) HIPCHK(hh, launch_nhwc_to_nchw(gp, B, 64, fh, fw, ts->gfeat_ext, st));
             ts->gfeat_ext = nullptr;      // written once, for the call that asked for it: never a stale pointer later
             return 0;
         });
     }
+};
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------ build
+static TrainState *build_train(mc_handle *h, int B, int H, int W, bool head_only = false) {
+    std::unique_ptr<TrainState, void (*)(TrainState *)> tsp(new TrainState(), train_free);
+    TrainState *ts = tsp.get();
+    ts->B = B; ts->H = H; ts->W = W; ts->bind_gen = h->bind_gen; ts->head_only = head_only;
+    ts->sw = read_switches();
+    TB b{h, ts};
+    // ---- forward
+    b.zero_amax_slots();
+    int feat;
+    if (head_only) {
+        feat = b.external_feat();
+    } else {
+        b.stem();
+        // backbone and neck: the steps of the network graph (the nodes they make are the graph's; node 0 is the stem's)
+        for (const NetStep &s : h->net.steps) {
+            const int o = s.kind == STEP_CONV ? b.conv_bn(s) : s.kind == STEP_POOL ? b.pool(s.srcs[0]) : b.deconv(h->deconvs[s.name], s.srcs[0]);
+            if (o != s.out) { ts->ok = false; h->err = "train plan: node order differs from the network graph"; }
+        }
+        feat = h->net.feat;
+    }
+    b.heads_forward(feat);
+    b.targets_and_losses();
+    // ---- backward: the heads (gradient bucket 0), then neck + backbone in reverse forward order
+    b.cur_bucket = 0;
+    b.heads_backward(feat);
+    for (int ri = (int)ts->recs.size() - 1; ri >= 0; --ri) {
+        const Rec r = ts->recs[ri];
+        b.cur_bucket = mc_grad_bucket_of(r.kind == REC_DECONV ? r.D->name : (r.kind == REC_POOL ? std::string("backbone.") : r.bn));
+        if (r.kind == REC_POOL) b.pool_backward(r);
+        else if (r.kind == REC_DECONV) b.deconv_backward(r);
+        else if (r.kind == REC_CONV) b.conv_backward(r);
+        else if (r.kind == REC_STEM) b.stem_backward(r);
+    }
+    if (head_only) b.feat_grad_out(feat);
+    // a gradient bucket is complete once the LAST step pushed for its layer groups has been enqueued
+    {
+        bool seen[MC_NUM_GRAD_BUCKETS] = {};
+        for (auto s = ts->bwd.rbegin(); s != ts->bwd.rend(); ++s) {
+            if (seen[s->bucket]) s->bucket = -1;
+            else seen[s->bucket] = true;
+        }
+    }
     if (!ts->ok) return nullptr;
-    if (std::getenv("MONOCON_HIP_PLAN_DEBUG"))
+    if (ts->sw.plan_debug)
         fprintf(stderr, "[plan] lazy activations: %d never stored, %d stored after all (lazy mask %d), %.2f GB\n", b.n_lazy - b.n_materialised,
-                b.n_materialised, b.lazy_mask, ts->mem.bytes * 1e-9);
+                b.n_materialised, (int)ts->sw.lazy_z, ts->mem.bytes * 1e-9);
     if (h->dry_alloc) return tsp.release();   // mc_query_workspace: sizes only
-    ts->bwd_side.resize(ts->bwd.size(), 0);
-    if (const char *e = std::getenv("MONOCON_HIP_DUAL_STREAM")) ts->dual = std::atoi(e) != 0;
-    if (ts->dual) {
-        size_t nside = 0;
-        for (char c : ts->bwd_side) nside += c != 0;
-        // MONOCON_HIP_SIDE_PRIORITY = low / high: the weight-gradient stream below / above the caller's stream in the
-        // hardware queues' priority order (default: the same)
-        int prio = 0, lo = 0, hi = 0;
-        (void)hipDeviceGetStreamPriorityRange(&lo, &hi);      // lo = numerically greatest = least urgent
-        if (const char *pe = std::getenv("MONOCON_HIP_SIDE_PRIORITY")) prio = pe[0] == 'l' ? lo : (pe[0] == 'h' ? hi : 0);
-        if (hipStreamCreateWithPriority(&ts->side, hipStreamNonBlocking, prio) != hipSuccess ||
-            hipEventCreateWithFlags(&ts->side_done, hipEventDisableTiming) != hipSuccess) ts->dual = false;
-        ts->side_ev.resize(ts->dual ? nside : 0);
-        for (auto &ev : ts->side_ev)
-            if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) { ts->dual = false; break; }
-        // one "finished" event per side closure that a recycled gradient buffer waits for
-        ts->side_fin.assign(ts->dual ? nside : 0, nullptr);
-        for (const auto &w : ts->wait_side)
-            if (ts->dual && w.second >= 0 && w.second < (int)nside && !ts->side_fin[w.second] &&
-                hipEventCreateWithFlags(&ts->side_fin[w.second], hipEventDisableTiming) != hipSuccess) { ts->dual = false; break; }
+    // ---- the weight-gradient stream and its events (any failure: everything on the caller's stream)
+    ts->dual = ts->sw.dual_stream != 0;
+    if (ts->dual && (hipStreamCreateWithFlags(&ts->side, hipStreamNonBlocking) != hipSuccess ||
+                     hipEventCreateWithFlags(&ts->side_done, hipEventDisableTiming) != hipSuccess))
+        ts->dual = false;
+    for (BwdStep &s : ts->bwd) {
+        if (!ts->dual) break;
+        if (s.stream == ON_SIDE && hipEventCreateWithFlags(&s.ready, hipEventDisableTiming) != hipSuccess) ts->dual = false;
+        hipEvent_t *fin = s.wait >= 0 ? &ts->bwd[s.wait].fin : nullptr;
+        if (fin && !*fin && hipEventCreateWithFlags(fin, hipEventDisableTiming) != hipSuccess) ts->dual = false;
     }
     if (hipDeviceSynchronize() != hipSuccess) return nullptr;
     return tsp.release();
@@ -1259,54 +1267,45 @@ static int backward_run(mc_handle *h, TrainState *ts, const float *grad_losses, 
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     ts->grad_losses = grad_losses;
-    size_t k = 0;
+    int k = 0;                // number of the side step (MONOCON_HIP_SIDE_SYNC counts them)
     bool used_side = false;
+    unsigned fired = 0;       // gradient buckets handed to the communicator so far
     // data parallelism with a communicator owned by the handle: every gradient bucket is exchanged (averaged over the
     // ranks) on the communicator's stream as soon as its last writer has been enqueued
     const bool dp = !ts->head_only && mc_comm_overlap_active(h);
     if (dp && mc_comm_prepare(h)) return -1;
-    for (size_t i = 0; i < ts->bwd.size(); ++i) {
-        if (ts->skip_feat_dgrad && (int)i == ts->feat_dgrad_closure) continue;
-        if (ts->dual && ts->bwd_side[i] && k < ts->side_ev.size()) {
-            // everything this closure reads (dY of its layer, forward activations) is ready at this point of
+    for (const BwdStep &s : ts->bwd) {
+        if (s.feat_dgrad && ts->skip_feat_dgrad) continue;
+        if (ts->dual && s.stream == ON_SIDE) {
+            // everything this step reads (dY of its layer, forward activations) is ready at this point of
             // the main stream; its outputs (the weight gradient) are first needed after mc_backward
-            HIPCHK(h, hipEventRecord(ts->side_ev[k], st));
-            HIPCHK(h, hipStreamWaitEvent(ts->side, ts->side_ev[k], 0));
-            if (ts->bwd[i](h, ts->side)) return -1;
-            if (k < ts->side_fin.size() && ts->side_fin[k]) HIPCHK(h, hipEventRecord(ts->side_fin[k], ts->side));
-            {   // debugging aid: MONOCON_HIP_SIDE_SYNC=lo:hi makes the main stream wait for side closures lo <= k < hi
-                static const std::pair<int, int> rng = [] {
-                    const char *e = std::getenv("MONOCON_HIP_SIDE_SYNC");
-                    int lo = 0, hi = 0;
-                    if (e && std::sscanf(e, "%d:%d", &lo, &hi) != 2) lo = hi = 0;
-                    return std::make_pair(lo, hi);
-                }();
-                if ((int)k >= rng.first && (int)k < rng.second) {
-                    HIPCHK(h, hipEventRecord(ts->side_done, ts->side));
-                    HIPCHK(h, hipStreamWaitEvent(st, ts->side_done, 0));
-                }
+            HIPCHK(h, hipEventRecord(s.ready, st));
+            HIPCHK(h, hipStreamWaitEvent(ts->side, s.ready, 0));
+            if (s.fn(h, ts->side)) return -1;
+            if (s.fin) HIPCHK(h, hipEventRecord(s.fin, ts->side));
+            if (k >= ts->sw.side_sync_lo && k < ts->sw.side_sync_hi) {
+                HIPCHK(h, hipEventRecord(ts->side_done, ts->side));
+                HIPCHK(h, hipStreamWaitEvent(st, ts->side_done, 0));
             }
             ++k;
             used_side = true;
         } else {
-            if (used_side) {      // a recycled gradient buffer: its previous content was read on the side stream
-                auto w = ts->wait_side.find((int)i);
-                if (w != ts->wait_side.end() && w->second < (int)ts->side_fin.size() && ts->side_fin[w->second])
-                    HIPCHK(h, hipStreamWaitEvent(st, ts->side_fin[w->second], 0));
-            }
-            if (ts->bwd[i](h, st)) return -1;
+            // a recycled gradient buffer: its previous content was read on the side stream
+            if (used_side && s.wait >= 0 && ts->bwd[s.wait].fin) HIPCHK(h, hipStreamWaitEvent(st, ts->bwd[s.wait].fin, 0));
+            if (s.fn(h, st)) return -1;
         }
-        if (dp)
-            for (int b = 0; b < MC_NUM_GRAD_BUCKETS; ++b)
-                if (ts->bucket_after[b] == (int)i && mc_comm_fire_bucket(h, b, st, used_side ? ts->side : nullptr)) return -1;
+        if (dp && s.bucket >= 0) {
+            if (mc_comm_fire_bucket(h, s.bucket, st, used_side ? ts->side : nullptr)) return -1;
+            fired |= 1u << s.bucket;
+        }
     }
     if (used_side) {
         HIPCHK(h, hipEventRecord(ts->side_done, ts->side));
         HIPCHK(h, hipStreamWaitEvent(st, ts->side_done, 0));
     }
     if (dp) {
-        for (int b = 0; b < MC_NUM_GRAD_BUCKETS; ++b)       // a bucket no closure of this plan writes into still has to be exchanged
-            if (ts->bucket_after[b] < 0 && mc_comm_fire_bucket(h, b, st, nullptr)) return -1;
+        for (int b = 0; b < MC_NUM_GRAD_BUCKETS; ++b)       // a bucket no step of this plan writes into still has to be exchanged
+            if (!(fired >> b & 1) && mc_comm_fire_bucket(h, b, st, nullptr)) return -1;
         if (mc_comm_join(h, st)) return -1;
     }
     return 0;
@@ -1340,7 +1339,10 @@ int mc_profile_train(mc_handle *h, int iters, double ms[3], double flops[3], dou
     if (iters < 1) iters = 1;
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t n = ts->fwd.size() + ts->bwd.size();
+    std::vector<const Fn *> all;      // every closure of the step in launch order, all on the caller's stream
+    for (const Fn &f : ts->fwd) all.push_back(&f);
+    for (const BwdStep &s : ts->bwd) all.push_back(&s.fn);
+    const size_t n = all.size();
     std::vector<hipEvent_t> ev(2 * n);
     for (auto &e : ev) HIPCHK(h, hipEventCreate(&e));
     std::vector<ProfLast> tag(n);
@@ -1348,14 +1350,13 @@ int mc_profile_train(mc_handle *h, int iters, double ms[3], double flops[3], dou
     int rc = 0;
     for (int it = 0; it < iters && !rc; ++it) {
         size_t i = 0;
-        for (auto *list : {&ts->fwd, &ts->bwd})
-            for (auto &f : *list) {
-                prof_last = {0, 0.0, 0.0};
-                (void)hipEventRecord(ev[2 * i], st);
-                if (f(h, st)) { rc = -1; break; }
-                (void)hipEventRecord(ev[2 * i + 1], st);
-                tag[i++] = prof_last;
-            }
+        for (const Fn *f : all) {
+            prof_last = {0, 0.0, 0.0};
+            (void)hipEventRecord(ev[2 * i], st);
+            if ((*f)(h, st)) { rc = -1; break; }
+            (void)hipEventRecord(ev[2 * i + 1], st);
+            tag[i++] = prof_last;
+        }
         if (hipStreamSynchronize(st) != hipSuccess) rc = fail(h, "mc_profile_train: stream error");
         for (size_t j = 0; j < i && !rc; ++j) {
             float t = 0.f;

@@ -135,12 +135,10 @@ hipError_t launch_maxpool2_bwd(const float *x, const float *dout, int B, int H, 
                                hipStream_t st, const float *la = nullptr, const float *lb = nullptr,    // la / lb: lazy x (ConvSrc::la)
                                float *stats_partial = nullptr);   // [maxpool2_bwd_blocks()][C][2]: also mask + BatchNorm-backward partials
 int maxpool2_bwd_blocks(int B, int H, int W, int C);
-hipError_t launch_deconv4_bwd_data(const float *dout, int B, int H, int W, int C, const float *wpk, float *din,
-                                   hipStream_t st);
 size_t deconv4_bwd_w_partial_floats(int B, int H, int C);
 hipError_t launch_deconv4_bwd_w(const float *in, const float *dout, int B, int H, int W, int C, float *partial, float *dw,
-                                hipStream_t st, const float *la = nullptr, const float *lb = nullptr,    // la / lb: lazy in
-                                const float *wpk = nullptr, float *din = nullptr,   // both given: the same pass also writes din (= launch_deconv4_bwd_data)
+                                hipStream_t st, const float *la, const float *lb,    // la / lb: lazy in (or null)
+                                const float *wpk, float *din,   // the same pass also writes din, the gradient wrt the input
                                 float *stats = nullptr);   // [B * H][C][2] (lazy `in` only): din masked by its ReLU + its BatchNorm-backward partials
 
 // ---- head / stem train kernels (kernels_head_train.hip)

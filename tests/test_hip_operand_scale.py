@@ -11,7 +11,6 @@ decision flips).
 """
 import math
 import os
-import subprocess
 import sys
 
 import pytest
@@ -283,32 +282,24 @@ def _stem_step(sd, batch):
     return res
 
 
-def _golden_state():
-    import numpy as np
-    stats = np.load(os.path.join(REPO, "tests", "golden", "bn_calib_seed7.npz"))
-    return synth.make_state_dict(7, bn_stats={k: stats[k] for k in stats.files})
-
-
 def _stem_inputs(golden_sd, H, W):
     return stressed_state_dict(golden_sd), stressed_batch(4200 + W, 2, H, W)
 
 
 @pytest.mark.parametrize("shape", [(128, 224), (96, 1248)], ids=["128x224", "96x1248"])
-def test_fused_stem_weight_gradient_matches_the_unfused_one(golden_sd, shape, monkeypatch, tmp_path):
+def test_fused_stem_weight_gradient_matches_the_unfused_one(golden_sd, shape, monkeypatch):
     """the stem weight gradient with dY formed on the fly from (d, y, BatchNorm coefficients) and scaled by a bound
-    (MONOCON_HIP_STEM_FUSE, the default) against the separate element-wise pass (STEM_FUSE=0, read once per process: a
-    child process), both against fp64 conv2d_weight(img, dY) with dY the fp64 BatchNorm backward of the stem node's
-    gradient (the GPU's own ReLU mask: no decision flips).  Everything upstream of the stem is the same computation."""
+    (MONOCON_HIP_STEM_FUSE, the default) against the separate element-wise pass (STEM_FUSE=0, read when the train plan
+    is built: a second model in this process), both against fp64 conv2d_weight(img, dY) with dY the fp64 BatchNorm
+    backward of the stem node's gradient (the GPU's own ReLU mask: no decision flips).  Everything upstream of the stem
+    is the same computation."""
     H, W = shape
     monkeypatch.setenv("MONOCON_HIP_GRAD_POOL", "0")                 # private gradient buffers: readable after the step
-    out = tmp_path / "unfused.pt"
-    env = dict(os.environ, MONOCON_HIP_STEM_FUSE="0", MONOCON_HIP_GRAD_POOL="0")
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--stem-child", str(H), str(W), str(out)], env=env,
-                       cwd=REPO, timeout=600, capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    unf = torch.load(str(out))
+    monkeypatch.delenv("MONOCON_HIP_STEM_FUSE", raising=False)
     sd, batch = _stem_inputs(golden_sd, H, W)
     fus = _stem_step(sd, batch)
+    monkeypatch.setenv("MONOCON_HIP_STEM_FUSE", "0")
+    unf = _stem_step(sd, batch)
     assert torch.equal(fus["g1"], unf["g1"])          # level0's gradient: upstream of the stem's weight gradient, bit-equal
     assert torch.equal(fus["z0"], unf["z0"])
     # the stem node's gradient buffer: dZ in the fused run; the separate pass overwrites it with dY in place
@@ -355,8 +346,3 @@ def test_stored_f16x2_layers_keep_22_bits_of_the_operand_maximum(golden_sd, shap
     over = ["%s: %.3g of the bound" % (n, v[1]) for n, v in f16.items() if v[1] > 1.0]
     assert not over, "\n".join(over)
 
-
-if __name__ == "__main__" and len(sys.argv) == 5 and sys.argv[1] == "--stem-child":
-    H, W = int(sys.argv[2]), int(sys.argv[3])
-    sd, batch = _stem_inputs(_golden_state(), H, W)
-    torch.save(_stem_step(sd, batch), sys.argv[4])
