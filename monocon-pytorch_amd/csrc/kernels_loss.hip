@@ -17,8 +17,12 @@ namespace mc {
 __device__ __forceinline__ float py_sqrt_f32(float v) { return (float)sqrt((double)v); }  // math.sqrt(tensor) -> fp32 operand
 
 // reference utils/tensor_ops.py:77-99 evaluated exactly as torch evaluates it on 0-dim fp32 tensors
-// with python scalars (scalars are rounded to fp32; math.sqrt runs in double on the fp32 value)
+// with python scalars (scalars are rounded to fp32; math.sqrt runs in double on the fp32 value).
+// Every product is rounded before the add that takes it, as a tensor operation rounds it: the compiler's default
+// (contract `a * b - c` into one fma) moves r2 across an integer on boxes whose radius sits next to one -- 3 of the 7
+// such boxes of tests/golden/targets_edge.npz came out one smaller, with the whole splat.
 __device__ float gaussian_radius_ref(float height, float width) {
+#pragma clang fp contract(off)
     const float mo = 0.3f;
     (void)mo;
     const float b1 = height + width;
@@ -61,6 +65,7 @@ __device__ __forceinline__ float py_fmod_pos(float a, float m) {   // python/tor
 }
 
 __global__ __launch_bounds__(256) void make_targets_kernel(const TargetArgs a) {
+#pragma clang fp contract(off)      // the reference's op sequence, one rounding per operation (keypoint * ratio - centre, bin * width + half)
     const int b = blockIdx.x / a.max_objs, slot = blockIdx.x % a.max_objs;
     const int tid = threadIdx.x;
     const float *mask = a.mask + (size_t)b * a.max_objs;

@@ -9,6 +9,7 @@ views are the ``.grad`` tensors -- are summed across ranks with a single RCCL al
 and divided by the world size.  Gradient clipping and AdamW then run identically on every rank.
 """
 import os
+import weakref
 
 import torch
 
@@ -84,17 +85,26 @@ def state_checksum(module):
     return tot
 
 
-_HOST_GROUP = None          # (default process group it belongs to, gloo group or False)
+_HOST_GROUP = None          # (token of the default process group it belongs to, gloo group or False)
 _HOST_GROUP_WARNED = False
+_GROUP_TOKENS = weakref.WeakKeyDictionary()     # default process group -> its token
+
+
+class _GroupToken:
+    pass
 
 
 def _default_group_token():
-    """identity of the CURRENT default process group: a cached subgroup of a destroyed / re-created default group is stale"""
+    """identity of the CURRENT default process group: a cached subgroup of a destroyed / re-created default group is stale.
+    A token object per group, looked up weakly -- NOT the group itself: the cache below outlives destroy_process_group(), and
+    a reference from it kept the destroyed group's backend and its worker threads alive until the interpreter shut down,
+    where a gloo worker that released its last tensor aborted the process (about one run in twenty on a loaded host)."""
     import torch.distributed as dist
     try:
-        return dist.distributed_c10d._get_default_group()
+        pg = dist.distributed_c10d._get_default_group()
     except Exception:           # noqa: BLE001
         return None
+    return _GROUP_TOKENS.setdefault(pg, _GroupToken())
 
 
 def host_group():

@@ -187,19 +187,26 @@ def forward(sd, img, train=False, return_levels=False):
 
 # ------------------------------------------------------------------ targets
 def gaussian_radius(h, w, min_overlap=0.3):
-    """reference utils/tensor_ops.py:77-99 (python-float arithmetic on fp32 inputs)."""
-    h, w = float(h), float(w)
+    """reference utils/tensor_ops.py:77-99.  The reference receives 0-dim fp32 tensors, so every + - * / ** below is
+    an fp32 tensor operation (a python scalar operand is rounded to fp32); only ``math.sqrt`` runs in double, on the
+    fp32 value, and its result is rounded to fp32 again by the tensor operation that takes it.  Evaluating the
+    formula in double instead floors to another integer for about one box in a million (radius just below an
+    integer in one arithmetic, just above in the other), and the whole splat changes size."""
+    h = torch.as_tensor(h, dtype=torch.float32)
+    w = torch.as_tensor(w, dtype=torch.float32)
+    a1 = 1
     b1 = h + w
     c1 = w * h * (1 - min_overlap) / (1 + min_overlap)
-    r1 = (b1 - math.sqrt(b1 * b1 - 4 * c1)) / 2
+    r1 = (b1 - math.sqrt((b1 ** 2) - 4 * a1 * c1)) / (2 * a1)
+    a2 = 4
     b2 = 2 * (h + w)
     c2 = (1 - min_overlap) * w * h
-    r2 = (b2 - math.sqrt(b2 * b2 - 16 * c2)) / 8
+    r2 = (b2 - math.sqrt((b2 ** 2) - 4 * a2 * c2)) / (2 * a2)
     a3 = 4 * min_overlap
     b3 = -2 * min_overlap * (h + w)
     c3 = (min_overlap - 1) * w * h
-    r3 = (b3 + math.sqrt(b3 * b3 - 4 * a3 * c3)) / (2 * a3)
-    return min(r1, r2, r3)
+    r3 = (b3 + math.sqrt((b3 ** 2) - 4 * a3 * c3)) / (2 * a3)
+    return float(min(r1, r2, r3))
 
 
 def _splat(canvas, cx_, cy_, radius):
