@@ -228,7 +228,9 @@ int mc_allreduce_grads(mc_handle *h, void *stream);
  * stay bit-identical, step times do not).  So rank 0 builds its plan first -- mc_build_train_plan builds and tunes the
  * train plan of a shape without running a kernel of the step or a collective -- exports the table (mc_tune_export: ints,
  * per entry [key length, key..., shape id]; buf == NULL returns the size in *n_ints), and every other rank imports it
- * (mc_tune_import, returns the number of entries or -1) before it builds its own plan.
+ * (mc_tune_import, returns the number of entries or -1) before it builds its own plan.  A table is adopted as a whole
+ * or not at all: a malformed entry, an unknown shape id or a tiling whose column tile does not divide its entry's padded
+ * column count fails the call and leaves the handle's table unchanged.
  * mc_comm_init runs ncclCommInitRank under a watchdog (MONOCON_HIP_COMM_TIMEOUT_S, default 60): if not every rank
  * arrives, the call fails with a message naming this rank instead of hanging. */
 int mc_build_train_plan(mc_handle *h, int B, int H, int W);

@@ -1187,7 +1187,9 @@ int mc_tune_export(mc_handle *h, int *buf, int cap, int *n_ints) {
 
 int mc_tune_import(mc_handle *h, const int *buf, int n_ints) {
     if (!h || (!buf && n_ints > 0)) return -1;
-    int o = 0, added = 0;
+    // A table is adopted as a whole or not at all: every entry is checked before the first one is stored.
+    std::vector<std::pair<std::vector<int>, int>> entries;
+    int o = 0;
     while (o < n_ints) {
         const int kl = buf[o++];
         if (kl < 10 || kl > 16 || o + kl + 1 > n_ints) return fail(h, "mc_tune_import: malformed table at int %d", o - 1);
@@ -1197,10 +1199,15 @@ int mc_tune_import(mc_handle *h, const int *buf, int n_ints) {
         // (a shape id is CFG_SMALL, or a tiling 1 .. CFG_COUNT - 1 with optional kernel-variant flags: a flag alone is no shape)
         if (cfg != CFG_SMALL && (cfg <= 0 || (cfg & 15) < 1 || (cfg & 15) >= CFG_COUNT || (cfg & ~(15 | CFG_WS | CFG_WRES))))
             return fail(h, "mc_tune_import: unknown shape id %d", cfg);
-        h->tuned[key] = cfg;
-        ++added;
+        // a tiling whose column tile does not divide the signature's padded column count (key[6]) has no launch: every
+        // dispatch refuses it -- but only when the plan RUNS, after the launches in front of it.  Refused here instead.
+        const int bnt = cfg == CFG_SMALL ? 0 : conv_shape(cfg).BNT();
+        if (cfg != CFG_SMALL && (bnt <= 0 || key[6] <= 0 || key[6] % bnt))
+            return fail(h, "mc_tune_import: the %d-column tile of shape id %d does not divide CoutP = %d of its entry", bnt, cfg, key[6]);
+        entries.emplace_back(std::move(key), cfg);
     }
-    return added;
+    for (auto &e : entries) h->tuned[e.first] = e.second;
+    return (int)entries.size();
 }
 
 int mc_set_local_maximum_kernel(mc_handle *h, int kernel) {

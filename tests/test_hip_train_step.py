@@ -207,20 +207,30 @@ def test_train_forward_shape_sweep_vs_oracle(golden_sd, shape, precision):
     """odd batches / other resolutions through the train plan (autotuned conv shapes, 16-channel row kernels
     where the width allows, parity-class stride-2 data gradients): losses vs the CPU oracle's train forward,
     gradients finite and of the oracle's total norm."""
-    from model import MonoConDetector
-    from oracle import monocon_oracle as O
     B, H, W = shape
     batch = synth.make_batch(2000 + B + H + W, B, H, W)
+    L64, ref_norm = oracle_step_reference(golden_sd, batch)
+    m = build(golden_sd, precision)
+    _, loss = m(to_cuda(batch))
+    sum(loss.values()).backward()
+    check_step_vs_oracle(m, loss, L64, ref_norm)
+
+
+def oracle_step_reference(sd, batch):
+    """the yard-sticks of a train step at an arbitrary shape: the oracle's losses in fp64, and the total norm of its
+    (fp32) gradients"""
+    from oracle import monocon_oracle as O
     live = {k: (v.clone().requires_grad_(True) if v.dtype == torch.float32 and "running" not in k else v.clone())
-            for k, v in golden_sd.items()}
+            for k, v in sd.items()}
     _, _, L, _ = O.train_forward(live, batch)
     sum(L.values()).backward()
     ref_norm = float(torch.sqrt(sum((p.grad.double() ** 2).sum() for p in live.values()
                                     if getattr(p, "grad", None) is not None)))
-    L64 = oracle_losses_fp64(golden_sd, batch)
-    m = build(golden_sd, precision)
-    _, loss = m(to_cuda(batch))
-    sum(loss.values()).backward()
+    return oracle_losses_fp64(sd, batch), ref_norm
+
+
+def check_step_vs_oracle(m, loss, L64, ref_norm):
+    """a finished forward + backward of model `m` against oracle_step_reference()"""
     for k, v in loss.items():       # measured: <= 5.7e-5 (the oracle's own fp32 run sits up to 6.3e-5 from its fp64 run)
         assert abs(float(v.detach()) - L64[k]) <= LOSS_TOL * abs(L64[k]) + 1e-7, (k, float(v.detach()), L64[k])
     g = torch.cat([p.grad.flatten() for p in m.parameters() if p.grad is not None])
