@@ -307,7 +307,26 @@ int mc_preprocess(mc_handle *h, const void *img_hwc, int dtype, int H, int W, co
  * 2 brightness, 4 contrast before, 8 saturation, 16 hue, 32 contrast after, 64 permutation, 128 shift, 256 flip, 512 window.
  * frames_hwc: (B, src_h, src_w, 3) uint8; params: (B, 24) float32; out_bchw: (B, 3, pad_h, pad_w) float32, all on the device.
  * Every value is bit-identical to the host pipeline's (float32 operation by operation, then the float64 normalisation of
- * mc_preprocess); with flags 0 it is mc_preprocess of a uint8 frame. */
+ * mc_preprocess); with flags 0 it is mc_preprocess of a uint8 frame.
+ *
+ * Resize3D (transforms/default_transforms.py:15-49) in the same launch: flag 1024.  The stages then run in the reference's list
+ * order with Resize3D first -- resize, colour, shift, flip, window, Normalize, Pad.  With the bit set, parameters 0, 1 are the
+ * RESIZED size (the H, W every later stage works in) and 17 = the decoded frame's height, 18 = its width inside the
+ * (src_h, src_w) canvas; src_h/src_w and pad_h/pad_w may differ.  Slots 19-23 are zero.  A pixel of the resized frame is the
+ * bilinear sample below rounded to uint8 (rintf: half to even, clamped to 0..255) -- the uint8 frame the host pipeline holds
+ * after Resize3D -- and goes on through the colour stage and the float64 normalisation.  The resample, every operation float32
+ * and rounded on its own (no fma contraction, the division correctly rounded); per axis, with n_in source and n_out target
+ * samples and d the target index:
+ *     scale = (float)n_in / (float)n_out          r  = max(scale * ((float)d + 0.5f) - 0.5f, 0.f)
+ *     i0    = min((int)r, n_in - 1)               i1 = min(i0 + 1, n_in - 1)
+ *     l1    = r - (float)i0                       l0 = 1.f - l1
+ *     v     = ly0 * (lx0 * a + lx1 * b) + ly1 * (lx0 * c + lx1 * d)      a, b: the taps x0, x1 on row y0; c, d: on row y1
+ * (half-pixel-centre bilinear without antialiasing: the geometry of cv2.resize's default).  Taps clamp to the frame
+ * (parameters 17, 18), not to the canvas: the canvas padding is never sampled.  transforms.resize_bilinear_u8 is the same
+ * arithmetic in numpy; the output is bit-identical to the host pipeline behind Resize3D(interpolation='exact').
+ * Without the bit nothing changes.  With or without it the kernel clamps a row's sizes to the canvas and to the padded
+ * output, and a permutation index outside 0..2 selects channel 2: no parameter row makes it read outside frames_hwc or write
+ * outside out_bchw. */
 int mc_preprocess_augmented(mc_handle *h, const unsigned char *frames_hwc, const float *params, int B, int src_h, int src_w,
                             const double mean[3], const double std[3], int pad_h, int pad_w, float *out_bchw, void *stream);
 

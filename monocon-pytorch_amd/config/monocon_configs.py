@@ -16,6 +16,9 @@ _DEFAULTS = {
         "NUM_WORKERS": 4,
         "TRAIN_SPLIT": "train",
         "TEST_SPLIT": "val",
+        # [H, W]: run the network at this resolution (Resize3D first in both transform lists, resampled on the device with the
+        # frames' other image work); [] = the frames keep their size
+        "RESIZE_HW": [],
         "FILTER": {"MIN_HEIGHT": 25, "MIN_DEPTH": 2, "MAX_DEPTH": 65, "MAX_TRUNCATION": 0.5, "MAX_OCCLUSION": 2},
     },
     "MODEL": {

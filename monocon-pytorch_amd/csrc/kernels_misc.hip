@@ -633,6 +633,25 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const T *__restrict__ i
 // stage, 5 saturation, 6 hue delta, 7 contrast after it, 8-10 channel permutation (on BGR), 11 sx, 12 sy, 13-16 window
 // x0 y0 x1 y1.  flags: 1 colour stage present, 2 brightness, 4 contrast before, 8 saturation, 16 hue, 32 contrast after,
 // 64 permutation, 128 shift, 256 flip, 512 window.
+//
+// Resize3D in the same launch (flag 1024; the reference's transforms/default_transforms.py:15-49, FIRST in the list: resize ->
+// colour -> shift -> flip -> window -> Normalize -> Pad).  With the bit set prm 0, 1 are the RESIZED size -- the H, W every
+// stage above works in -- and prm 17, 18 the decoded frame's own size inside the (Hs, Ws) canvas; the canvas and the padded
+// output may then differ in size.  The geometry is the index map above on the resized frame's coordinates; where it lands on a
+// live pixel (ys, xs), that pixel is the bilinear sample below, rounded to uint8 (rintf: half to even; clamped to 0..255) where
+// the host pipeline holds a uint8 frame, and goes on through the colour chain and the normalisation.
+// The resample, every operation float32 and rounded on its own (no fma contraction; the division correctly rounded); per axis,
+// with n_in source and n_out target samples and d the target index:
+//     scale = (float)n_in / (float)n_out          r  = max(scale * ((float)d + 0.5f) - 0.5f, 0.f)
+//     i0    = min((int)r, n_in - 1)               i1 = min(i0 + 1, n_in - 1)
+//     l1    = r - (float)i0                       l0 = 1.f - l1
+//     v     = ly0 * (lx0 * a + lx1 * b) + ly1 * (lx0 * c + lx1 * d)       a, b: the taps (x0, x1) on row y0; c, d: on row y1
+// i.e. half-pixel-centre bilinear without antialiasing (the geometry of cv2.resize's default).  The taps clamp to the FRAME
+// (prm 17, 18), never to the canvas: its padding is not sampled.  Four 3-byte taps in, 12 bytes out per pixel.
+//
+// A row is not trusted to be consistent: the frame's size is clamped to the canvas and the output size to the padded output,
+// so no row makes the kernel read outside frames_hwc or write outside out (rows written by DeferredImage are unaffected).  The
+// permutation is a chain of selects, not an indexed access: an index outside 0..2 reads channel 2.
 namespace {
 // float32 division through float64: the float64 quotient of two floats rounds to what a correctly rounded float32 division
 // gives (53 >= 2 * 24 + 2 bits) -- independent of how the compiler is told to divide floats.
@@ -688,15 +707,36 @@ __device__ __forceinline__ void aug_colour(float &c0, float &c1, float &c2, cons
     }
     c0 = r; c1 = g; c2 = b;                                         // BGR -> RGB
 }
+// one axis of the resample: the two taps (clamped to the frame) and their weights for target index d
+__device__ __forceinline__ void resize_axis(int d, int n_in, int n_out, int &i0, int &i1, float &l0, float &l1) {
+#pragma clang fp contract(off)
+    const float scale = div_rn((float)n_in, (float)n_out);
+    const float t0 = (float)d + 0.5f;
+    const float t1 = scale * t0;
+    const float r = fmaxf(t1 - 0.5f, 0.f);
+    i0 = min((int)r, n_in - 1);
+    i1 = min(i0 + 1, n_in - 1);
+    l1 = r - (float)i0;
+    l0 = 1.f - l1;
+}
+__device__ __forceinline__ float resize_sample(float a, float b, float c, float d, float lx0, float lx1, float ly0, float ly1) {
+#pragma clang fp contract(off)
+    const float ta = lx0 * a, tb = lx1 * b, tc = lx0 * c, td = lx1 * d;
+    const float top = ta + tb, bot = tc + td;
+    const float wt = ly0 * top, wb = ly1 * bot;
+    const float v = wt + wb;
+    return fminf(fmaxf(rintf(v), 0.f), 255.f);                      // the host pipeline's uint8 frame
+}
 }  // namespace
 
-__global__ __launch_bounds__(256) void preprocess_aug_kernel(const unsigned char *__restrict__ in, const float *__restrict__ prm_all,
-                                                             int Hs, int Ws, double m0, double m1, double m2, double s0, double s1,
-                                                             double s2, int Hp, int Wp, float *__restrict__ out) {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, img = blockIdx.z;
-    if (x >= Wp) return;
-    const float *prm = prm_all + (size_t)img * 24;
-    const int H = (int)prm[0], W = (int)prm[1], flags = (int)prm[2];
+// One output pixel.  RESIZE is the row's flag 1024: uniform per blockIdx.z, so the kernel branches on it once per wave and
+// the rows without the bit run the code they always ran (plus the two clamps, on the scalar unit).
+template <bool RESIZE>
+__device__ __forceinline__ void preprocess_aug_pixel(const unsigned char *__restrict__ in, const float *__restrict__ prm, int rowH,
+                                                     int rowW, int flags, int x, int y, int img, int Hs, int Ws, double m0, double m1, double m2,
+                                                     double s0, double s1, double s2, int Hp, int Wp, float *__restrict__ out) {
+    // the frame the stages work in: the decoded one inside the canvas, or (RESIZE) the resampled one inside the output
+    const int H = min(rowH, RESIZE ? Hp : min(Hs, Hp)), W = min(rowW, RESIZE ? Wp : min(Ws, Wp));
     float v0 = 0.f, v1 = 0.f, v2 = 0.f;
     if (y < H && x < W) {
         bool live = true;
@@ -706,8 +746,21 @@ __global__ __launch_bounds__(256) void preprocess_aug_kernel(const unsigned char
         live = live && xs >= 0 && xs < W && ys >= 0 && ys < H;
         float c0 = 0.f, c1 = 0.f, c2 = 0.f;
         if (live) {
-            const unsigned char *p = in + (((size_t)img * Hs + ys) * Ws + xs) * 3;
-            c0 = (float)p[0]; c1 = (float)p[1]; c2 = (float)p[2];
+            if (RESIZE) {
+                const int Hin = max(min((int)prm[17], Hs), 1), Win = max(min((int)prm[18], Ws), 1);
+                int y0, y1, x0, x1;
+                float ly0, ly1, lx0, lx1;
+                resize_axis(ys, Hin, H, y0, y1, ly0, ly1);
+                resize_axis(xs, Win, W, x0, x1, lx0, lx1);
+                const unsigned char *r0 = in + ((size_t)img * Hs + y0) * Ws * 3, *r1 = in + ((size_t)img * Hs + y1) * Ws * 3;
+                const unsigned char *pa = r0 + (size_t)x0 * 3, *pb = r0 + (size_t)x1 * 3, *pc = r1 + (size_t)x0 * 3, *pd = r1 + (size_t)x1 * 3;
+                c0 = resize_sample((float)pa[0], (float)pb[0], (float)pc[0], (float)pd[0], lx0, lx1, ly0, ly1);
+                c1 = resize_sample((float)pa[1], (float)pb[1], (float)pc[1], (float)pd[1], lx0, lx1, ly0, ly1);
+                c2 = resize_sample((float)pa[2], (float)pb[2], (float)pc[2], (float)pd[2], lx0, lx1, ly0, ly1);
+            } else {
+                const unsigned char *p = in + (((size_t)img * Hs + ys) * Ws + xs) * 3;
+                c0 = (float)p[0]; c1 = (float)p[1]; c2 = (float)p[2];
+            }
             if (flags & 1) aug_colour(c0, c1, c2, prm, flags);
         }
         v0 = (float)(((double)c0 - m0) / s0);
@@ -718,6 +771,20 @@ __global__ __launch_bounds__(256) void preprocess_aug_kernel(const unsigned char
     out[o] = v0;
     out[plane + o] = v1;
     out[2 * plane + o] = v2;
+}
+__global__ __launch_bounds__(256) void preprocess_aug_kernel(const unsigned char *__restrict__ in, const float *__restrict__ prm_all,
+                                                             int Hs, int Ws, double m0, double m1, double m2, double s0, double s1,
+                                                             double s2, int Hp, int Wp, float *__restrict__ out) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, img = blockIdx.z;
+    if (x >= Wp) return;
+    const float *prm = prm_all + (size_t)img * 24;
+    // (size, size and flags in one go: the branch below must not put a second dependent load in front of the first pixel)
+    const int rowH = __builtin_amdgcn_readfirstlane((int)prm[0]), rowW = __builtin_amdgcn_readfirstlane((int)prm[1]);
+    const int flags = __builtin_amdgcn_readfirstlane((int)prm[2]);
+    if (__builtin_expect((flags & 1024) != 0, 0))
+        preprocess_aug_pixel<true>(in, prm, rowH, rowW, flags, x, y, img, Hs, Ws, m0, m1, m2, s0, s1, s2, Hp, Wp, out);
+    else
+        preprocess_aug_pixel<false>(in, prm, rowH, rowW, flags, x, y, img, Hs, Ws, m0, m1, m2, s0, s1, s2, Hp, Wp, out);
 }
 hipError_t launch_preprocess_aug(const unsigned char *frames, const float *prm, int B, int Hs, int Ws, const double mean[3],
                                  const double std[3], int Hp, int Wp, float *out, hipStream_t st) {

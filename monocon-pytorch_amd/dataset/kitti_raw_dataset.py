@@ -19,13 +19,13 @@ from typing import Any, Dict, List
 import numpy as np
 from torch.utils.data import Dataset
 
-from dataset.monocon_dataset import IMG_MEAN, IMG_STD, MonoConDataset
+from dataset.monocon_dataset import IMG_MEAN, IMG_STD, MonoConDataset, _resize
 from transforms import Compose, Convert_3D_to_4D, DeferImage, DeferredImage, Normalize, Pad, ToTensor
 from utils.engine_utils import tprint
 
 
-def default_raw_transforms():
-    return [Normalize(mean=IMG_MEAN, std=IMG_STD, keep_origin=True), Pad(size_divisor=32), ToTensor(), Convert_3D_to_4D()]
+def default_raw_transforms(resize_hw=None):
+    return _resize(resize_hw) + [Normalize(mean=IMG_MEAN, std=IMG_STD, keep_origin=True), Pad(size_divisor=32), ToTensor(), Convert_3D_to_4D()]
 
 
 class SimpleCalib:
@@ -34,10 +34,22 @@ class SimpleCalib:
     def __init__(self, calib_dict: Dict[str, Any]):
         self.P2 = calib_dict['P_rect_02']
 
+    def rescale(self, scale_x: float = None, scale_y: float = None) -> None:
+        """the projection of the frame resized by these factors (KITTICalibration.rescale on P2; Resize3D calls it)"""
+        self.P2[0, [0, 2, 3]] *= 1.0 if scale_x is None else scale_x
+        self.P2[1, [1, 2, 3]] *= 1.0 if scale_y is None else scale_y
+
 
 class KITTIRawDataset(Dataset):
-    def __init__(self, image_dir: str, calib_file: str, img_extension: str = 'png', device_image: bool = False):
+    # what ``resize_hw=None`` means: None = the frames keep their size.  A front end that builds its dataset elsewhere sets it
+    # before that (infer_raw.py runs test_raw.py's main at a chosen resolution this way)
+    default_resize_hw = None
+
+    def __init__(self, image_dir: str, calib_file: str, img_extension: str = 'png', device_image: bool = False,
+                 resize_hw=None):
         super().__init__()
+        if resize_hw is None:
+            resize_hw = type(self).default_resize_hw
         assert os.path.isdir(image_dir), "image_dir %r is not a directory" % (image_dir,)
         assert os.path.isfile(calib_file), "calib_file %r is not a file (calib_cam_to_cam.txt)" % (calib_file,)
         img_extension = img_extension.replace('.', '')
@@ -45,7 +57,10 @@ class KITTIRawDataset(Dataset):
         self.image_files = sorted(glob.glob(os.path.join(self.image_dir, '*.%s' % img_extension)))
         self.calib = SimpleCalib(self._parse_calib(calib_file))
         self.device_image = device_image
-        self.transforms = Compose([DeferImage(), DeferredImage(size_divisor=32)] if device_image else default_raw_transforms())
+        self.resized = len(_resize(resize_hw)) > 0
+        # resize_hw (H, W): the network's resolution (Resize3D(interpolation='exact') first: on the device in batched mode)
+        self.transforms = Compose([DeferImage()] + _resize(resize_hw) + [DeferredImage(size_divisor=32)] if device_image else
+                                  default_raw_transforms(resize_hw))
         tprint("Found %d images in '%s'." % (len(self.image_files), image_dir))
 
     def __len__(self) -> int:
@@ -62,7 +77,9 @@ class KITTIRawDataset(Dataset):
             metas = {'idx': idx, 'sample_idx': idx, 'image_path': self.image_files[idx], 'ori_shape': img.shape[:2]}
         else:
             metas = {'idx': idx, 'image_path': self.image_files[idx], 'ori_shape': img.shape}
-        return self.transforms({'img': img, 'img_metas': metas, 'calib': self.calib})
+        # (Resize3D rescales the sample's calibration in place: it gets its own copy of the drive's)
+        calib = SimpleCalib({'P_rect_02': self.calib.P2.copy()}) if self.resized else self.calib
+        return self.transforms({'img': img, 'img_metas': metas, 'calib': calib})
 
     @staticmethod
     def collate_fn(batched: List[Dict[str, Any]]) -> Dict[str, Any]:

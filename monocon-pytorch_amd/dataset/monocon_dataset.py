@@ -24,7 +24,7 @@ import torch
 from torch.utils.data import Dataset
 
 from transforms import (Compose, DeferImage, DeferredImage, Normalize, Pad, PhotometricDistortion, RandomCrop3D, RandomHorizontalFlip, RandomShift,
-                        ToTensor)
+                        Resize3D, ToTensor)
 from utils.data_classes import KITTICalibration, KITTIMultiObjects
 from utils.kitti_convert_utils import kitti_result_lines
 
@@ -32,25 +32,39 @@ DEFAULT_FILTER_CONFIG = {'min_height': 25, 'min_depth': 2, 'max_depth': 65, 'max
 IMG_MEAN, IMG_STD = [123.675, 116.28, 103.53], [58.395, 57.12, 57.375]
 
 
-def default_transforms(device_image: bool = False):
+def _resize(resize_hw):
+    """[] or [Resize3D] for the front of a list: ``resize_hw`` None (or empty) = the frames keep their size"""
+    if resize_hw is None or len(resize_hw) == 0:
+        return []
+    return [Resize3D((int(resize_hw[0]), int(resize_hw[1])), interpolation='exact')]
+
+
+def default_transforms(device_image: bool = False, resize_hw=None):
     """the test / validation list (dataset/monocon_dataset.py:38-42).  ``device_image``: the image work is left to the device
-    (transforms.DeferredImage: the sample carries the raw uint8 frame + 24 parameters for ``mc_preprocess_augmented``)"""
+    (transforms.DeferredImage: the sample carries the raw uint8 frame + 24 parameters for ``mc_preprocess_augmented``).
+    ``resize_hw`` (H, W): the network's resolution -- Resize3D(interpolation='exact') first, whose resample is the same
+    arithmetic on the host and (deferred) on the device"""
     if device_image:
-        return [DeferImage(), DeferredImage(size_divisor=32)]
-    return [Normalize(mean=IMG_MEAN, std=IMG_STD), Pad(size_divisor=32), ToTensor()]
+        return [DeferImage()] + _resize(resize_hw) + [DeferredImage(size_divisor=32)]
+    return _resize(resize_hw) + [Normalize(mean=IMG_MEAN, std=IMG_STD), Pad(size_divisor=32), ToTensor()]
 
 
-def default_train_transforms(rng=None, device_image: bool = False):
+def default_train_transforms(rng=None, device_image: bool = False, resize_hw=None):
     """the reference's training list (dataset/monocon_dataset.py:22-35).  ``rng``: one np.random.Generator for all the random
     decisions (seed it per rank / worker / epoch); None = numpy's global state.  ``device_image``: the same random decisions,
-    labels and calibration, the pixels left to the device (the float32 colour round trip alone costs a worker ~80 ms per frame)"""
+    labels and calibration, the pixels left to the device (the float32 colour round trip alone costs a worker ~80 ms per frame).
+    ``resize_hw`` (H, W): Resize3D(interpolation='exact') first; RandomCrop3D's window then keeps the reference's proportion of
+    the nominal 375 x 1242 KITTI frame (320 x 960) instead of asserting on a smaller target"""
+    crop_size = (320, 960)
+    if _resize(resize_hw):
+        crop_size = (int(resize_hw[0]) * 320 // 375, int(resize_hw[1]) * 960 // 1242)
     aug = [PhotometricDistortion(brightness_delta=32, contrast_range=(0.5, 1.5), saturation_range=(0.5, 1.5), hue_delta=18, rng=rng),
            RandomShift(prob=0.5, shift_range=(-32, 32), hide_kpts_in_shift_area=True, rng=rng),
            RandomHorizontalFlip(prob=0.5, rng=rng),
-           RandomCrop3D(prob=0.5, crop_size=(320, 960), hide_kpts_in_crop_area=True, rng=rng)]
+           RandomCrop3D(prob=0.5, crop_size=crop_size, hide_kpts_in_crop_area=True, rng=rng)]
     if device_image:
-        return [DeferImage()] + aug + [DeferredImage(size_divisor=32)]
-    return aug + default_transforms()
+        return [DeferImage()] + _resize(resize_hw) + aug + [DeferredImage(size_divisor=32)]
+    return _resize(resize_hw) + aug + default_transforms()
 
 
 def _find_imageset(base_root: str, split: str, imageset_dir: Optional[str]) -> Optional[str]:
@@ -105,11 +119,12 @@ class BaseKITTIMono3DDataset(Dataset):
 
 class MonoConDataset(BaseKITTIMono3DDataset):
     def __init__(self, base_root: str, split: str, max_objs: int = 30, transforms=None, filter_configs: Dict[str, Any] = None,
-                 aug_rng=None, device_image: bool = False, **kwargs):
+                 aug_rng=None, device_image: bool = False, resize_hw=None, **kwargs):
         super().__init__(base_root=base_root, split=split, **kwargs)
         self.max_objs = max_objs
         if transforms is None:          # as the reference: augmentations for 'train' only (monocon_dataset.py:58-63)
-            transforms = default_train_transforms(aug_rng, device_image) if split == 'train' else default_transforms(device_image)
+            transforms = (default_train_transforms(aug_rng, device_image, resize_hw) if split == 'train' else
+                          default_transforms(device_image, resize_hw))
         self.transforms = Compose(transforms)
         # One Generator serves every random transform.  A DataLoader with num_workers > 0 COPIES it into each forked
         # worker, which would then all draw the same augmentation sequence (the engine's worker_init_fn only
@@ -182,6 +197,13 @@ class MonoConDataset(BaseKITTIMono3DDataset):
 
     @staticmethod
     def collate_fn(batched: List[Dict[str, Any]]) -> Dict[str, Any]:
+        shapes = {tuple(d['img'].shape) for d in batched}
+        if len(shapes) > 1 and 'img_aug' in batched[0]:
+            # a deferred Resize3D leaves every frame on the canvas of ITS size (the device resamples it): the host lists resize
+            # first and would stack such a batch
+            raise ValueError("deferred samples with canvases of different sizes %s cannot share a batch: the decoded frames must "
+                             "pad to one (H, W) -- all KITTI frame sizes do; resize such frames on the host (device_image=False)"
+                             % sorted(shapes))
         out = {'img': torch.stack([d['img'] for d in batched]),
                'img_metas': {k: [d['img_metas'][k] for d in batched] for k in batched[0]['img_metas']},
                'calib': [d['calib'] for d in batched]}

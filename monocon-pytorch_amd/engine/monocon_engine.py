@@ -80,7 +80,8 @@ class MonoconEngine(BaseEngine):
                                      split=self.cfg.DATA.TRAIN_SPLIT if is_train else self.cfg.DATA.TEST_SPLIT,
                                      max_objs=self.cfg.MODEL.HEAD.MAX_OBJS,
                                      filter_configs={k.lower(): v for k, v in dict(self.cfg.DATA.FILTER).items()},
-                                     device_image=torch.cuda.is_available() and bool(self.cfg.DATA.get('DEVICE_AUGMENT', True)))
+                                     device_image=torch.cuda.is_available() and bool(self.cfg.DATA.get('DEVICE_AUGMENT', True)),
+                                     resize_hw=list(self.cfg.DATA.get('RESIZE_HW', [])) or None)
         sampler = None
         if self.world > 1 and is_train:
             sampler = DistributedSampler(dataset, num_replicas=self.world, rank=self.rank, shuffle=True, drop_last=True)

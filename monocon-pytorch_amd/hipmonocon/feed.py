@@ -75,6 +75,9 @@ class DevicePrefetcher:
         if self.detector is not None and "label" in batch and isinstance(batch.get("img"), torch.Tensor):
             img = batch["img"]              # (B, 3, Hp, Wp) float32, or transforms.DeferredImage's raw (B, Hp, Wp, 3) uint8 frames
             pad_hw = tuple(img.shape[1:3]) if "img_aug" in batch else tuple(img.shape[-2:])
+            pads = batch.get("img_metas", {}).get("pad_shape") if "img_aug" in batch else None
+            if pads:                        # a deferred Resize3D: the canvas is the decoded frame's, the labels live in the target's
+                pad_hw = tuple(int(v) for v in (pads[0] if isinstance(pads, list) else pads))
             ok = _train.labels_ok_on_host(batch["label"], pad_hw, self.num_classes)
         with torch.cuda.stream(self.copy_stream):
             dev = _upload(batch, self.device)

@@ -45,12 +45,23 @@ class MonoConDetector(nn.Module):
     def finish_batch(self, data_dict: Dict[str, Any]) -> Dict[str, Any]:
         """a collated batch of transforms.DeferredImage samples -- raw uint8 frames (B, Hp, Wp, 3) + ``img_aug`` (B, 24) -- gets
         its float32 (B, 3, Hp, Wp) frames here, in one launch (mc_preprocess_augmented: the train augmentations' image work +
-        Normalize + Pad + ToTensor, bit-identical to the host transforms).  Any other batch passes through."""
+        Normalize + Pad + ToTensor, bit-identical to the host transforms), at the size ``img_metas['pad_shape']`` names: the
+        canvas's, or that of a deferred Resize3D's target.  Any other batch passes through."""
         if 'img_aug' in data_dict:
             eng = self._rt.engine if self._rt.engine is not None else self._engine()
             from dataset.monocon_dataset import IMG_MEAN, IMG_STD
+            from hipmonocon.lib import MonoconHipError
+            # the output's size: what Pad made of the frame the network sees -- the canvas's own size unless a deferred
+            # Resize3D resamples the frames on the way
+            out_hw = None
+            pads = data_dict.get('img_metas', {}).get('pad_shape')
+            if pads is not None:
+                pads = {(int(p[0]), int(p[1])) for p in (pads if isinstance(pads, list) else [pads])}
+                if len(pads) != 1:
+                    raise MonoconHipError("finish_batch: the batch disagrees on pad_shape: %s" % sorted(pads))
+                out_hw = pads.pop()
             data_dict['img'] = eng.preprocess_augmented(data_dict['img'].contiguous(), data_dict.pop('img_aug').contiguous(),
-                                                        IMG_MEAN, IMG_STD)
+                                                        IMG_MEAN, IMG_STD, out_hw=out_hw)
         return data_dict
 
     def forward(self, data_dict: Dict[str, Any], return_loss: bool = True) -> Tuple[Dict[str, torch.Tensor]]:

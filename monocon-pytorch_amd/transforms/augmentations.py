@@ -6,7 +6,8 @@ bookkeeping; host-side numpy, no cv2:
 
   * the BGR <-> HSV conversions of PhotometricDistortion are written out in numpy after OpenCV's float32 formulas
     (hue in degrees, saturation and value unscaled);
-  * Resize3D resamples with torch's bilinear interpolation (half-pixel centres, like cv2.INTER_LINEAR on floats);
+  * Resize3D resamples with torch's bilinear interpolation (half-pixel centres, like cv2.INTER_LINEAR on floats) or, with
+    ``interpolation='exact'``, with ``resize_bilinear_u8``: the float32 arithmetic the device kernel shares, bit for bit;
   * every transform draws from ONE source: an ``np.random.Generator`` handed in as ``rng=`` (what a data-parallel
     loader wants: seed it per (rank, worker, epoch)) or, by default, numpy's global state -- the reference mixes
     numpy's and python's global generators.  The ORDER and kind of the random decisions follow the reference.
@@ -153,6 +154,14 @@ class PhotometricDistortion(BaseTransform):
 
 
 # ------------------------------------------------------------------------------------------------------ geometry
+def _frame_width(data_dict: Dict[str, Any]) -> int:
+    """the width of the frame a transform works in: the image's, or the target of a resize left to the device"""
+    for name, val in data_dict.get('img_ops', ()):
+        if name == 'resize':
+            return int(val[1])
+    return data_dict['img'].shape[1]
+
+
 class RandomShift(BaseTransform):
     """integer translation of image, principal point and 2D labels; objects whose clipped box collapses are dropped.
     (``hide_kpts_in_shift_area`` is accepted and, as in the reference, has no effect: its filter is never invoked.)"""
@@ -225,7 +234,7 @@ class RandomHorizontalFlip(BaseTransform):
             metas['is_flipped'] = False
             return data_dict
         img = data_dict['img']
-        w = img.shape[1]
+        w = _frame_width(data_dict)
         if 'img_ops' in data_dict:
             data_dict['img_ops'].append(('flip', True))
         else:
@@ -356,23 +365,67 @@ class RandomRangeCrop3D(_CropBase):
 
 
 # ------------------------------------------------------------------------------------------------------ misc
+def _resize_axis(n_in: int, n_out: int):
+    """taps and weights of one axis of ``resize_bilinear_u8``: float32 operation by operation"""
+    f32 = np.float32
+    scale = f32(n_in) / f32(n_out)
+    r = np.maximum(scale * (np.arange(n_out, dtype=np.float32) + f32(0.5)) - f32(0.5), f32(0.0))
+    i0 = np.minimum(r.astype(np.int64), n_in - 1)
+    i1 = np.minimum(i0 + 1, n_in - 1)
+    l1 = r - i0.astype(np.float32)
+    l0 = f32(1.0) - l1
+    return i0, i1, l0, l1
+
+
+def resize_bilinear_u8(img: np.ndarray, target_hw: Tuple[int, int]) -> np.ndarray:
+    """uint8 (H, W, C) -> uint8 (th, tw, C): THE resample of this package, the same arithmetic on the host and in
+    ``mc_preprocess_augmented`` (flag 1024; the specification stands in include/monocon_hip.h).  Half-pixel-centre bilinear
+    without antialiasing; every operation float32 and rounded on its own.  Per axis, with n_in source and n_out target samples:
+    scale = n_in / n_out; r = max(scale * (d + 0.5) - 0.5, 0); i0 = min(int(r), n_in - 1); i1 = min(i0 + 1, n_in - 1);
+    l1 = r - i0; l0 = 1 - l1.  v = ly0 * (lx0 * a + lx1 * b) + ly1 * (lx0 * c + lx1 * d), rounded half to even."""
+    if img.dtype != np.uint8 or img.ndim != 3:
+        raise TypeError("resize_bilinear_u8 needs a uint8 (H, W, C) frame, got %s %s" % (img.dtype, img.shape))
+    th, tw = int(target_hw[0]), int(target_hw[1])
+    y0, y1, ly0, ly1 = _resize_axis(img.shape[0], th)
+    x0, x1, lx0, lx1 = _resize_axis(img.shape[1], tw)
+    lx0, lx1 = lx0[None, :, None], lx1[None, :, None]
+    ly0, ly1 = ly0[:, None, None], ly1[:, None, None]
+    f = img.astype(np.float32)
+    top, bot = f[y0], f[y1]
+    v = ly0 * (lx0 * top[:, x0] + lx1 * top[:, x1]) + ly1 * (lx0 * bot[:, x0] + lx1 * bot[:, x1])
+    return np.clip(np.rint(v), 0, 255).astype(np.uint8)
+
+
 class Resize3D(BaseTransform):
-    def __init__(self, target_hw: Union[int, Tuple[int, int]] = None):
+    """``interpolation='torch'`` (default): torch's bilinear interpolation on the host, whose float results depend on the
+    vector path torch takes on the host CPU.  ``'exact'``: ``resize_bilinear_u8``, the arithmetic the device kernel shares --
+    and behind DeferImage the frame is left alone: the device resamples it (``('resize', (th, tw))`` in ``img_ops``)."""
+
+    def __init__(self, target_hw: Union[int, Tuple[int, int]] = None, interpolation: str = 'torch'):
         super().__init__(True, True, True, True)
+        if interpolation not in ('torch', 'exact'):
+            raise ValueError("interpolation must be 'torch' or 'exact', got %r" % (interpolation,))
         self.target_hw = (target_hw, target_hw) if isinstance(target_hw, int) else target_hw
+        self.interpolation = interpolation
 
     def __call__(self, data_dict: Dict[str, Any]) -> Dict[str, Any]:
         if self.target_hw is None:
             return data_dict
         if data_dict.get('img_ops'):
             raise NotImplementedError("Resize3D behind a deferred image operation: the device kernel maps whole pixels only")
-        import torch
-        import torch.nn.functional as F
         img = data_dict['img']
         ori_hw = img.shape[:2]
-        t = torch.from_numpy(np.array(img, copy=True)).permute(2, 0, 1)[None].float()
-        out = F.interpolate(t, size=tuple(self.target_hw), mode='bilinear', align_corners=False)[0].permute(1, 2, 0).numpy()
-        data_dict['img'] = np.clip(np.rint(out), 0, 255).astype(np.uint8) if img.dtype == np.uint8 else out.astype(img.dtype)
+        if self.interpolation == 'exact':
+            if 'img_ops' in data_dict:                                        # DeferImage: the device does the pixels
+                data_dict['img_ops'].append(('resize', (int(self.target_hw[0]), int(self.target_hw[1]))))
+            else:
+                data_dict['img'] = resize_bilinear_u8(img, self.target_hw)
+        else:
+            import torch
+            import torch.nn.functional as F
+            t = torch.from_numpy(np.array(img, copy=True)).permute(2, 0, 1)[None].float()
+            out = F.interpolate(t, size=tuple(self.target_hw), mode='bilinear', align_corners=False)[0].permute(1, 2, 0).numpy()
+            data_dict['img'] = np.clip(np.rint(out), 0, 255).astype(np.uint8) if img.dtype == np.uint8 else out.astype(img.dtype)
         scale_hw = np.array(self.target_hw) / np.array(ori_hw)
         data_dict['img_metas']['scale_hw'] = scale_hw
         data_dict['img_metas']['ori_shape'] = tuple(self.target_hw)

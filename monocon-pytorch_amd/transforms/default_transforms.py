@@ -83,8 +83,9 @@ class GpuNormalizePad(BaseTransform):
 # ---------------------------------------------------------------------------------------------- image work on the device
 AUG_PARAMS = 24
 AUG_COLOUR, AUG_BRIGHTNESS, AUG_CONTRAST_BEFORE, AUG_SATURATION, AUG_HUE, AUG_CONTRAST_AFTER, AUG_PERMUTATION = 1, 2, 4, 8, 16, 32, 64
-AUG_SHIFT, AUG_FLIP, AUG_WINDOW = 128, 256, 512
-_AUG_ORDER = ('colour', 'shift', 'flip', 'window')       # the order the kernel composes them in = the reference's train list
+AUG_SHIFT, AUG_FLIP, AUG_WINDOW, AUG_RESIZE = 128, 256, 512, 1024
+# the order the kernel composes them in = the reference's train list, with Resize3D in front of it
+_AUG_ORDER = ('resize', 'colour', 'shift', 'flip', 'window')
 
 
 class DeferImage(BaseTransform):
@@ -106,7 +107,11 @@ class DeferredImage(BaseTransform):
     zero-padded to the padded size as (Hp, Wp, 3), and ``img_aug`` the float32 parameters the device kernel needs to produce
     -- bit for bit -- the float32 CHW frame those three (and the augmentations in front of them) would have
     (``Engine.preprocess_augmented``; hipmonocon.feed.DevicePrefetcher calls it on the uploaded batch).  Labels become tensors
-    as under ToTensor."""
+    as under ToTensor.
+
+    Behind a deferred ``Resize3D(interpolation='exact')`` the frame is still the decoded one, zero-padded to a multiple of
+    ``size_divisor`` of ITS size; parameters 0, 1 carry the resized size (the frame every later stage works in), 17, 18 the
+    decoded frame's own, and ``pad_shape`` is what Pad makes of the resized size: the device's output, not the canvas."""
 
     def __init__(self, size_divisor: int = 32):
         super().__init__(True, True, False, True)
@@ -122,12 +127,15 @@ class DeferredImage(BaseTransform):
         if len(set(names)) != len(names) or names != [n for n in _AUG_ORDER if n in names]:
             raise NotImplementedError("deferred image operations %s: the device kernel composes at most one each of %s, in "
                                       "that order" % (names, list(_AUG_ORDER)))
-        h, w = img.shape[:2]
+        h, w = src_h, src_w = img.shape[:2]
         prm = np.zeros(AUG_PARAMS, np.float32)
-        prm[0], prm[1] = h, w
         flags = 0
         for name, val in ops:
-            if name == 'colour':
+            if name == 'resize':
+                flags |= AUG_RESIZE
+                h, w = val
+                prm[17], prm[18] = src_h, src_w
+            elif name == 'colour':
                 flags |= AUG_COLOUR
                 for key, bit, at in (('brightness', AUG_BRIGHTNESS, 3), ('contrast_before', AUG_CONTRAST_BEFORE, 4),
                                      ('saturation', AUG_SATURATION, 5), ('hue', AUG_HUE, 6), ('contrast_after', AUG_CONTRAST_AFTER, 7)):
@@ -145,11 +153,11 @@ class DeferredImage(BaseTransform):
             else:
                 flags |= AUG_WINDOW
                 prm[13:17] = val
-        prm[2] = flags
+        prm[0], prm[1], prm[2] = h, w, flags
         d = self.size_divisor
         ph, pw = -(-h // d) * d, -(-w // d) * d
-        canvas = np.zeros((ph, pw, 3), np.uint8)
-        canvas[:h, :w] = img
+        canvas = np.zeros((-(-src_h // d) * d, -(-src_w // d) * d, 3), np.uint8)
+        canvas[:src_h, :src_w] = img
         data_dict['img'] = torch.from_numpy(canvas)
         data_dict['img_aug'] = torch.from_numpy(prm)
         data_dict['img_metas']['pad_shape'] = (ph, pw)

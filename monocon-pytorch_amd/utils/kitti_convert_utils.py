@@ -20,8 +20,18 @@ def _empty_anno():
             'rotation_y': np.array([]), 'score': np.array([])}
 
 
-def _inv_scale(img_metas):
-    s = img_metas['scale_hw'][0] if img_metas.get('scale_hw') else (1., 1.)
+def _inv_scale(img_metas, i=0):
+    """1 / the resize factors of image ``i`` as (x, y, x, y).  DEPARTS FROM THE REFERENCE, which takes the batch's first
+    ``scale_hw`` for every image: frames of different sizes resized to one target (KITTI's 375x1242 and 370x1224 in one batch)
+    each have their own factors, so image i reads entry i -- the same numbers wherever the batch agrees on them."""
+    s = img_metas.get('scale_hw')
+    if not s:
+        s = (1., 1.)
+    else:
+        n = len(img_metas['ori_shape'])
+        if len(s) != n:
+            raise ValueError("img_metas['scale_hw'] has %d entries for a batch of %d images" % (len(s), n))
+        s = s[i]
     return np.reciprocal(np.array([s[1], s[0], s[1], s[0]], dtype=np.float64))
 
 
@@ -46,9 +56,9 @@ def project_boxes_3d(boxes: np.ndarray, P2: np.ndarray) -> np.ndarray:
 
 
 def convert_to_kitti_3d(results_3d: List[Dict[str, torch.Tensor]], img_metas: Dict[str, Any], calibs) -> List[Dict[str, Any]]:
-    inv = _inv_scale(img_metas)
     out = []
     for i, r in enumerate(results_3d):
+        inv = _inv_scale(img_metas, i)
         boxes, scores, labels = _np(r['boxes_3d']), _np(r['scores_3d']), _np(r['labels_3d'])
         h, w = img_metas['ori_shape'][i]
         anno = _empty_anno()
@@ -70,9 +80,9 @@ def convert_to_kitti_3d(results_3d: List[Dict[str, torch.Tensor]], img_metas: Di
 
 def convert_to_kitti_2d(results_2d: List[List[np.ndarray]], img_metas: Dict[str, Any]) -> List[Dict[str, Any]]:
     assert len(results_2d[0]) == len(CLASSES)
-    inv = _inv_scale(img_metas)
     out = []
     for i, per_class in enumerate(results_2d):
+        inv = _inv_scale(img_metas, i)
         n = sum(b.shape[0] for b in per_class)
         anno = _empty_anno()
         if n:
@@ -89,10 +99,10 @@ def convert_to_kitti_2d(results_2d: List[List[np.ndarray]], img_metas: Dict[str,
 # ------------------------------------------------------------------------------ packed rows of mc_kitti_format
 def img_hw_scale(img_metas: Dict[str, Any], batch: int) -> np.ndarray:
     """(B,4) float32 rows ori_h, ori_w, inv_sx, inv_sy: mc_kitti_format's view of the metas (the inverse resize factors of
-    _inv_scale, which like the conversion above takes the batch's first ``scale_hw``)"""
-    inv = _inv_scale(img_metas)
+    _inv_scale, each image's own as in the conversion above)"""
     out = np.empty((batch, 4), np.float32)
     for i in range(batch):
+        inv = _inv_scale(img_metas, i)
         h, w = tuple(img_metas['ori_shape'][i])[:2]
         out[i] = (h, w, inv[0], inv[1])
     return out
