@@ -197,7 +197,11 @@ int mc_head_backward(mc_handle *h, const float *grad_losses, float *grad_feat, v
  * (B, PRED_CH[k], pad_h/4, pad_w/4)); all of them NULL: exactly mc_head_backward. */
 int mc_head_backward_pred_grads(mc_handle *h, const float *grad_losses, const float *const grad_preds[MC_NUM_PREDS],
                                 float *grad_feat, void *stream);
-/* Debugging aid: activation (which=0) or gradient (which=1) of node `node` of the train plan as NCHW. */
+/* Debugging aid: activation (which=0) or gradient buffer (which=1) of node `node` of the train plan as NCHW.  The
+ * gradient buffer is readable only with MONOCON_HIP_GRAD_POOL=0; after a backward it holds dY (the gradient wrt the raw
+ * conv output) for a conv + BatchNorm node, dZ (the sum of the consumers' data gradients) for a pool or deconv output
+ * node, and for the stem dY -- or, where the f16x2 stem weight gradient forms dY on the fly (MONOCON_HIP_STEM_FUSE=1
+ * with the statistics left by level0's data-gradient epilogue), the masked gradient d = dZ * [z > 0]. */
 int mc_train_debug_node(mc_handle *h, int node, int which, float *out_nchw, int dims[4], void *stream);
 
 /* ---- data parallelism -----------------------------------------------------------

@@ -1205,7 +1205,14 @@ int mc_train_generation(mc_handle *h, unsigned long long *out) {
 }
 
 // debugging aid: copy activation node `node` (train plan order: 0 = stem output, 1 = level0, ...) as NCHW;
-// which = 0 activation, 1 its gradient.  dims[4] receives (B, C, H, W).
+// which = 0 activation (a lazy one is formed for the caller), 1 the node's gradient buffer.  dims[4] receives (B, C, H, W).
+// The gradient buffer is readable only with MONOCON_HIP_GRAD_POOL=0 (pooled buffers are handed on during the backward; a
+// node without a private buffer fails with "no such buffer").  After a backward it holds
+//   - conv + BatchNorm node: dY, the gradient wrt the RAW conv output (the affine pass writes it in place over dZ);
+//   - pool / deconv output node: dZ, the plain sum of its consumers' data gradients;
+//   - the stem (node 0): dY like any conv node, except where its weight gradient forms dY on the fly (mode f16x2,
+//     MONOCON_HIP_STEM_FUSE=1 and the statistics left by level0's data-gradient epilogue): the affine pass is skipped and
+//     the buffer keeps the masked gradient d = dZ * [z > 0].
 int mc_train_debug_node(mc_handle *h, int node, int which, float *out_nchw, int dims[4], void *stream) {
     if (!h || !h->train) return fail(h, "mc_train_debug_node: no train plan");
     TrainState *ts = h->train;

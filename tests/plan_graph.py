@@ -1,0 +1,432 @@
+"""The train plan's graph as the tests see it, the stressed state, and the layer-local backward reference.
+
+A plain module (no fixtures): `test_hip_operand_scale.py` (forward, layer by layer), `test_hip_backward_layers.py` (backward,
+layer by layer) and `test_backward_reference_cpu.py` (the checker checked against autograd) share it.
+
+The graph mirrors mc_api.hip `build_net` / mc_train_plan.hip: node 0 is the stem's output, every live conv + BatchNorm, every
+2x2 max-pool and every depthwise deconv makes one node, in forward order.
+
+The backward reference (`backward_reference`) is pure torch on the CPU in float64.  It never differentiates through more than
+ONE layer: every quantity of a layer is formed from the plan's own buffers around it, so no ReLU or max-pool decision can flip
+and nothing is amplified.  The buffers, as `mc_train_debug_node` hands them out after a backward with MONOCON_HIP_GRAD_POOL=0:
+
+    act[n]   the activation of node n (which = 0)
+    g[n]     conv + BatchNorm node: dY, the gradient wrt the RAW conv output (the affine pass writes it in place over dZ)
+             pool / deconv output node: dZ, the plain sum of its consumers' data gradients
+             the stem (node 0): dY like every conv node -- except where the stem weight gradient forms dY on the fly
+             (f16x2, MONOCON_HIP_STEM_FUSE=1, statistics left by level0's data-gradient epilogue): then the affine pass is
+             skipped and the buffer keeps d = dZ * [z > 0], the masked gradient.  With STEM_FUSE=0, in fp32 / bf16x3, or with
+             MONOCON_HIP_BM_EPILOGUE=0 it holds dY.
+"""
+import os
+import sys
+
+import torch
+import torch.nn.functional as F
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(REPO, "monocon-pytorch_amd")
+for _p in (PKG, REPO):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+STRESS_SEED = 1234
+STEM = "backbone.base_layer.0"
+EPS = 1e-5
+
+
+# ------------------------------------------------------------------------------------------------ the stressed state
+def _bn_of(conv):
+    """BatchNorm behind a train-plan conv (mc_api.hip build_net)"""
+    if conv.endswith(".project.0") or conv.endswith("level0.0") or conv.endswith("level1.0") or conv.endswith("base_layer.0"):
+        return conv[:-1] + "1"
+    if conv.endswith(".root.conv"):
+        return conv[:-len("conv")] + "bn"
+    if conv.endswith(".conv1") or conv.endswith(".conv2"):
+        return conv[:-len("convN")] + "bn" + conv[-1]
+    assert conv.endswith(".conv") and ".ida_" in conv, conv
+    return conv[:-len("conv")] + "bn1"
+
+
+def stressed_state_dict(sd, seed=STRESS_SEED):
+    """The golden state with (a) every conv in front of a train-mode BatchNorm rescaled per output channel, log-uniformly
+    over [1, 10^3] (running statistics rescaled with it: the network's function does not change), and (b) every such
+    BatchNorm's gamma log-uniform over [1e-2, 10] and beta uniform over [-3, 10] -- off-centre channels of both signs."""
+    g = torch.Generator().manual_seed(seed)
+    out = {k: v.clone() for k, v in sd.items()}
+    for conv, _ in _plan_convs():
+        w = out[conv + ".weight"]
+        bn = _bn_of(conv)
+        C = w.shape[0]
+        s = 10.0 ** (3.0 * torch.rand(C, generator=g, dtype=torch.float64))
+        out[conv + ".weight"] = (w.double() * s[:, None, None, None]).float()
+        out[bn + ".running_mean"] = (out[bn + ".running_mean"].double() * s).float()
+        out[bn + ".running_var"] = (out[bn + ".running_var"].double() * s * s).float()
+        out[bn + ".weight"] = (10.0 ** (-2.0 + 3.0 * torch.rand(C, generator=g, dtype=torch.float64))).float()
+        out[bn + ".bias"] = (-3.0 + 13.0 * torch.rand(C, generator=g, dtype=torch.float64)).float()
+    return out
+
+
+def stressed_batch(seed, B, H, W):
+    """(c) frames with a strong DC offset after Normalize: alternately a bright and a dark frame with faint texture"""
+    from hipmonocon import synth
+    batch = synth.make_batch(seed, B, H, W)
+    img = batch["img"]
+    for b in range(B):
+        img[b] = (2.1 if b % 2 == 0 else -1.9) + 0.05 * img[b]
+    return batch
+
+
+# ------------------------------------------------------------------------------------------------ the train plan's graph
+class PlanGraph:
+    """recs: per live conv layer (conv name, source nodes, residual node or -1, relu, output node, kernel size, stride);
+    pools: (input node, output node); deconvs: (parameter name `neck.ida_i.up_t`, input node, output node);
+    steps: all of them in forward order, ("conv", rec) / ("pool", in, out) / ("deconv", name, in, out);
+    node_c / node_down: channels and down-scale of every node (node 0: 16 channels at full resolution);
+    consumers[n]: who reads node n, in the order the BACKWARD writes their shares into n's gradient (records in reverse
+    forward order; within a conv record the residual's share -- written by the BatchNorm backward -- before the data gradients
+    of its sources in source order): ("conv", rec, source index, channel offset) / ("res", rec) / ("pool", out) /
+    ("deconv", name, out)."""
+
+    def __init__(self):
+        self.recs, self.pools, self.deconvs, self.steps = [], [], [], []
+        self.node_c, self.node_down = [16], [1]
+        self.feat = -1
+
+    @property
+    def n_nodes(self):
+        return len(self.node_c)
+
+    def dims(self, B, H, W):
+        return [(B, c, H // d, W // d) for c, d in zip(self.node_c, self.node_down)]
+
+    @property
+    def consumers(self):
+        cons = [[] for _ in range(self.n_nodes)]
+        for st in reversed(self.steps):
+            if st[0] == "conv":
+                rec = st[1]
+                if rec[2] >= 0:
+                    cons[rec[2]].append(("res", rec))
+                off = 0
+                for i, s in enumerate(rec[1]):
+                    cons[s].append(("conv", rec, i, off))
+                    off += self.node_c[s]
+            elif st[0] == "pool":
+                cons[st[1]].append(("pool", st[2]))
+            else:
+                cons[st[2]].append(("deconv", st[1], st[3]))
+        return cons
+
+
+def plan_graph():
+    """The node order of the train plan (mc_train_plan.hip: stem, conv_bn, pool, deconv, tree and the neck loop)"""
+    from hipmonocon import netspec
+    shapes = netspec.state_shapes()
+    G = PlanGraph()
+    pooled = {}
+
+    def node(c, down):
+        G.node_c.append(c)
+        G.node_down.append(down)
+        return G.n_nodes - 1
+
+    def conv_bn(name, ks, stride, srcs, res, relu, dead=False):
+        if dead:
+            return -1
+        cout = shapes[name + ".weight"][0][0]
+        assert shapes[name + ".weight"][0][1] == sum(G.node_c[s] for s in srcs), name
+        o = node(cout, G.node_down[srcs[0]] * stride)
+        rec = (name, list(srcs), res, relu, o, ks, stride)
+        G.recs.append(rec)
+        G.steps.append(("conv", rec))
+        return o
+
+    def pool(x):
+        if x not in pooled:
+            pooled[x] = node(G.node_c[x], G.node_down[x] * 2)
+            G.pools.append((x, pooled[x]))
+            G.steps.append(("pool", x, pooled[x]))
+        return pooled[x]
+
+    def block(n, x, residual, stride):
+        y = conv_bn(n + ".conv1", 3, stride, [x], -1, True)
+        return conv_bn(n + ".conv2", 3, 1, [y], residual if residual >= 0 else x, True)
+
+    def tree(n, levels, cin, cout, stride, level_root, x, children):
+        bottom = pool(x) if stride > 1 else x
+        if level_root:
+            children = children + [bottom]
+        if levels == 1:
+            residual = bottom
+            if cin != cout:
+                residual = conv_bn(n + ".project.0", 1, 1, [bottom], -1, False)
+            x1 = block(n + ".tree1", x, residual, stride)
+            x2 = block(n + ".tree2", x1, -1, 1)
+            return conv_bn(n + ".root.conv", 1, 1, [x2, x1] + children, -1, True)
+        if cin != cout:
+            conv_bn(n + ".project.0", 1, 1, [bottom], -1, False, dead=True)
+        x1 = tree(n + ".tree1", levels - 1, cin, cout, stride, False, x, [])
+        return tree(n + ".tree2", levels - 1, cout, cout, 1, False, x1, children + [x1])
+
+    l0 = conv_bn("backbone.level0.0", 3, 1, [0], -1, True)
+    l1 = conv_bn("backbone.level1.0", 3, 2, [l0], -1, True)
+    l2 = tree("backbone.level2", 1, 32, 64, 2, False, l1, [])
+    l3 = tree("backbone.level3", 2, 64, 128, 2, True, l2, [])
+    l4 = tree("backbone.level4", 2, 128, 256, 2, True, l3, [])
+    l5 = tree("backbone.level5", 1, 256, 512, 2, True, l4, [])
+    layers = [l2, l3, l4, l5]
+    for i in range(3):
+        j = 4 - i - 2
+        for t in range(1, 4 - j):
+            pre = "neck.ida_%d." % i
+            p = conv_bn(pre + "proj_%d.conv" % t, 3, 1, [layers[j + t]], -1, True)
+            u = node(G.node_c[p], G.node_down[p] // 2)           # the depthwise deconv of p
+            G.deconvs.append((pre + "up_%d" % t, p, u))
+            G.steps.append(("deconv", pre + "up_%d" % t, p, u))
+            layers[j + t] = conv_bn(pre + "node_%d.conv" % t, 3, 1, [layers[j + t - 1], u], -1, True)
+    G.feat = layers[3]
+    return G
+
+
+def _plan_graph():
+    """(conv records, number of nodes): see PlanGraph"""
+    G = plan_graph()
+    return G.recs, G.n_nodes
+
+
+def _plan_convs():
+    """(conv, bn) of every conv in front of a train-mode BatchNorm, the stem included (dead `project` convs too: they
+    still tick their statistics)"""
+    names = [STEM] + [r[0] for r in _plan_graph()[0]]
+    from hipmonocon import netspec
+    shapes = netspec.state_shapes()
+    for k in shapes:                                     # the outer `project` of the two-level trees (never consumed)
+        if k.endswith(".project.0.weight") and k[:-len(".weight")] not in names:
+            names.append(k[:-len(".weight")])
+    return [(n, _bn_of(n)) for n in names]
+
+
+def layer_kind(ks, stride):
+    return "stem" if ks == 7 else ("1x1" if ks == 1 else "3x3s%d" % stride)
+
+
+# ------------------------------------------------------------------------------------------------ running a plan
+def _model(sd, precision):
+    from model import MonoConDetector
+    m = MonoConDetector(34, pretrained_backbone=False)
+    m.load_state_dict(sd, strict=True)
+    return m.cuda().train().set_precision(precision)
+
+
+def _node_dims(m, i):
+    import ctypes as C
+    eng = m._engine()
+    dims = (C.c_int * 4)()
+    assert eng.lib.mc_train_debug_node(eng.h, int(i), 0, None, dims, None) == 0
+    return tuple(dims)
+
+
+def _read_node(m, i, which=0):
+    """node i of the model's train plan (NCHW float32); a lazy node is formed without changing the plan"""
+    import ctypes as C
+    eng = m._engine()
+    dims = (C.c_int * 4)()
+    assert eng.lib.mc_train_debug_node(eng.h, int(i), int(which), None, dims, None) == 0
+    out = torch.empty(tuple(dims), dtype=torch.float32, device="cuda")
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    rc = eng.lib.mc_train_debug_node(eng.h, int(i), int(which), C.c_void_p(out.data_ptr()), dims, st)
+    assert rc == 0, rc
+    torch.cuda.synchronize()
+    return out.cpu()
+
+
+# ------------------------------------------------------------------------------------------------ the backward reference
+def _floored(M):
+    """the magnitude sum of a tensor, floored at 2^-10 of its maximum (dead channels do not divide by zero)"""
+    return M.clamp_min(max(float(M.max()), 1e-300) * 2.0 ** -10)
+
+
+def _conv_step(xs, w, gout, ks, stride, dtype, absolute=False):
+    """ONE conv layer differentiated on its own: (y, dW, [data gradient of every source]) for the upstream gradient `gout`;
+    absolute: the same sums over absolute values (the magnitude every rounding error is relative to)"""
+    def cv(t):
+        t = t.detach().to(dtype)          # (detach: a fresh tensor object, the caller's never turns into a leaf)
+        return t.abs() if absolute else t
+    xs = [cv(x).requires_grad_(True) for x in xs]
+    w = cv(w).requires_grad_(True)
+    y = F.conv2d(torch.cat(xs, 1) if len(xs) > 1 else xs[0], w, stride=stride, padding=ks // 2)
+    grads = torch.autograd.grad(y, [w] + xs, cv(gout))
+    return y.detach(), grads[0], list(grads[1:])
+
+
+def _pool_bwd(x, gout, dtype, absolute=False):
+    """max_pool2d(2) backward: a cast keeps ties, and torch routes to the first maximum in scan order, as the kernel does"""
+    x = x.detach().to(dtype).requires_grad_(True)
+    gout = gout.detach().to(dtype)
+    return torch.autograd.grad(F.max_pool2d(x, 2), x, gout.abs() if absolute else gout)[0]
+
+
+def _deconv_step(x, w, gout, dtype, absolute=False):
+    """depthwise ConvTranspose2d(k 4, s 2, p 1, groups C) differentiated on its own: (weight gradient, input gradient)"""
+    def cv(t):
+        t = t.detach().to(dtype)          # (detach: a fresh tensor object, the caller's never turns into a leaf)
+        return t.abs() if absolute else t
+    x, w = cv(x).requires_grad_(True), cv(w).requires_grad_(True)
+    u = F.conv_transpose2d(x, w, stride=2, padding=1, groups=x.shape[1])
+    gw, gx = torch.autograd.grad(u, [w, x], cv(gout))
+    return gw, gx
+
+
+class Triple:
+    """a reference quantity: fp64 value, fp64 magnitude sum, and (yard-stick) the same quantity carried out in float32"""
+    __slots__ = ("ref", "mag", "f32")
+
+    def __init__(self, ref=None, mag=None, f32=None):
+        self.ref, self.mag, self.f32 = ref, mag, f32
+
+    def add(self, ref, mag, f32=None):
+        self.ref = ref if self.ref is None else self.ref + ref
+        self.mag = mag if self.mag is None else self.mag + mag
+        if f32 is not None:
+            self.f32 = f32 if self.f32 is None else self.f32 + f32          # float32, in the order the plan adds its shares
+
+    def floored(self):
+        return _floored(self.mag)
+
+    def err(self, got):
+        """elementwise |got - ref| / M"""
+        return (got.double() - self.ref).abs() / _floored(self.mag)
+
+    def f32_err(self):
+        return float(((self.f32.double() - self.ref).abs() / _floored(self.mag)).max())
+
+
+class BackwardReference:
+    """what `backward_reference` found: per conv name `dW` (Triple) and `bn` (dict: dbeta, dgamma, their |term| sums, n,
+    mean, rstd, a = gamma * rstd); per node `dZ` (Triple: the sum of its consumers' shares), `d` (the masked dZ, conv nodes),
+    `dY` (conv nodes), `y` (the fp64 raw conv output) and `ymag` (sum |x| |w|); per deconv name `dWup` (Triple)."""
+
+    def __init__(self, graph):
+        self.graph = graph
+        self.dW, self.dWup, self.bn = {}, {}, {}
+        self.dZ, self.d, self.dY, self.y, self.ymag, self.tmax = {}, {}, {}, {}, {}, {}
+
+
+def backward_reference(graph, act, g, img, sd, yardstick=True):
+    """The layer-local backward of backbone + neck in float64 from the plan's own buffers (see the module docstring for what
+    `act` and `g` hold).  Covered: every live conv layer (the dead `project` convs are not in the graph); for `feat`, whose
+    dZ comes from the head backward, only the weight-gradient identity.
+
+        dW_L  = conv2d_weight(cat(act[srcs]), g[o])                  (the plan's weight gradient reads this same dY)
+        dZ_o  = sum over o's consumers, in plan order, of
+                  conv consumer C, source slice s:  conv2d_input(g[out(C)], W_C) restricted to the slice
+                  residual consumer R:              d_R (below, recursively)
+                  pool consumer:                    max_pool2d backward of g[pool node] on act[o]
+                  deconv consumer:                  input gradient of the depthwise conv_transpose2d against g[u]
+        d_o   = dZ_o * (act[o] > 0) where the layer has a ReLU: the GPU's own mask
+        y     = conv2d(cat(act[srcs]), W) with its batch statistics;  dbeta = sum d, dgamma = sum d * yhat,
+        dY_o  = gamma * rstd * (d - mean d - yhat * mean(d * yhat))
+        dWup  = depthwise conv_transpose2d weight gradient from act[in] and g[u]
+        stem:   d_0 from level0's share; dW from the image and the fp64 dY_0 (NOT from g[0], whose content depends on the path)
+
+    yardstick: also every conv quantity in float32 from the same float32 buffers, shares added in the plan's order."""
+    R = BackwardReference(graph)
+    D = torch.float64
+    dZ = {n: Triple() for n in range(graph.n_nodes)}
+    R.dZ = dZ
+
+    def bn_backward(name, o, xs, relu, ks, stride):
+        """d, statistics and dY of the conv layer `name` with output node o, from its complete dZ"""
+        w = sd[name + ".weight"].double()
+        bn = _bn_of(name)
+        gamma = sd[bn + ".weight"].double()
+        x = torch.cat([t.double() for t in xs], 1)
+        y = F.conv2d(x, w, stride=stride, padding=ks // 2)
+        R.ymag[o] = F.conv2d(x.abs(), w.abs(), stride=stride, padding=ks // 2)
+        # the f16x2 operand-split scale of the layer: sum over sources of max |x_s| * sum |w_c,s| (test_hip_operand_scale)
+        tm, c0 = torch.zeros_like(gamma), 0
+        for t in xs:
+            tm += float(t.abs().max()) * w[:, c0:c0 + t.shape[1]].abs().sum((1, 2, 3))
+            c0 += t.shape[1]
+        R.tmax[o] = tm
+        mask = (act[o] > 0).double() if relu else torch.ones_like(y)
+        d = dZ[o].ref * mask
+        n = y.numel() // y.shape[1]
+        mean = y.mean((0, 2, 3), keepdim=True)
+        rstd = 1.0 / torch.sqrt(y.var((0, 2, 3), unbiased=False, keepdim=True) + EPS)
+        yhat = (y - mean) * rstd
+        dbeta, dgamma = d.sum((0, 2, 3)), (d * yhat).sum((0, 2, 3))
+        a = gamma[None, :, None, None] * rstd
+        R.d[o], R.y[o] = d, y
+        R.dY[o] = a * (d - dbeta[None, :, None, None] / n - yhat * dgamma[None, :, None, None] / n)
+        R.bn[name] = dict(dbeta=dbeta, dgamma=dgamma, n=n, mean=mean.flatten(), rstd=rstd.flatten(), a=a.flatten(), mask=mask,
+                          abs_d=d.abs().sum((0, 2, 3)), abs_dy=(d * y).abs().sum((0, 2, 3)), yhat=yhat)
+        return d, mask
+
+    for st in reversed(graph.steps):
+        if st[0] == "pool":
+            _, i, o = st
+            dZ[i].add(_pool_bwd(act[i], g[o], D), _pool_bwd(act[i], g[o], D, True),
+                      _pool_bwd(act[i], g[o], torch.float32) if yardstick else None)
+        elif st[0] == "deconv":
+            _, name, i, o = st
+            w = sd[name + ".weight"]
+            gw, gx = _deconv_step(act[i], w, g[o], D)
+            mw, mx = _deconv_step(act[i], w, g[o], D, True)
+            fw, fx = _deconv_step(act[i], w, g[o], torch.float32) if yardstick else (None, None)
+            R.dWup[name] = Triple(gw, mw, fw)
+            dZ[i].add(gx, mx, fx)
+        else:
+            name, srcs, res, relu, o, ks, stride = st[1]
+            xs = [act[s] for s in srcs]
+            if o != graph.feat:
+                d, mask = bn_backward(name, o, xs, relu, ks, stride)
+                if res >= 0:
+                    dZ[res].add(d, dZ[o].mag * mask, (dZ[o].f32 * mask.float()) if yardstick else None)
+            w = sd[name + ".weight"]
+            _, gw, gxs = _conv_step(xs, w, g[o], ks, stride, D)
+            _, mw, mxs = _conv_step(xs, w, g[o], ks, stride, D, True)
+            fw, fxs = None, [None] * len(srcs)
+            if yardstick:
+                _, fw, fxs = _conv_step(xs, w, g[o], ks, stride, torch.float32)
+            R.dW[name] = Triple(gw, mw, fw)
+            for s, gx, mx, fx in zip(srcs, gxs, mxs, fxs):
+                dZ[s].add(gx, mx, fx)
+    # the stem: node 0's dZ is level0's share; its weight gradient from the image and the fp64 dY
+    act_img = {-1: img}
+    bn_backward(STEM, 0, [act_img[-1]], True, 7, 1)
+    wshape = sd[STEM + ".weight"].shape
+    gw = torch.nn.grad.conv2d_weight(img.double(), wshape, R.dY[0], padding=3)
+    mw = torch.nn.grad.conv2d_weight(img.double().abs(), wshape, R.dY[0].abs(), padding=3)
+    fw = torch.nn.grad.conv2d_weight(img.float(), wshape, R.dY[0].float(), padding=3) if yardstick else None
+    R.dW[STEM] = Triple(gw, mw, fw)
+    return R
+
+
+def norm_err(got, ref):
+    """norm-wise error: max |got - ref| / max |ref|"""
+    return float((got.double() - ref).abs().max() / ref.abs().max().clamp_min(1e-300))
+
+
+def compare_normwise(R, g, grads, stem_holds="dY"):
+    """every compared quantity, norm-wise: {(class, layer or node): error}.  grads: parameter name -> gradient."""
+    G = R.graph
+    out = {}
+    for name, t in R.dW.items():
+        out[("dW", name)] = norm_err(grads[name + ".weight"], t.ref)
+    for name, t in R.dWup.items():
+        out[("dWup", name)] = norm_err(grads[name + ".weight"], t.ref)
+    for name, b in R.bn.items():
+        bn = _bn_of(name)
+        out[("dgamma", name)] = norm_err(grads[bn + ".weight"], b["dgamma"])
+        out[("dbeta", name)] = norm_err(grads[bn + ".bias"], b["dbeta"])
+    for name, srcs, res, relu, o, ks, stride in G.recs:
+        if o != G.feat:
+            out[("dY", name)] = norm_err(g[o], R.dY[o])
+    for _, o in G.pools:
+        out[("dZ", "pool node %d" % o)] = norm_err(g[o], R.dZ[o].ref)
+    for name, _, o in G.deconvs:
+        out[("dZ", name)] = norm_err(g[o], R.dZ[o].ref)
+    out[("stem g", STEM)] = norm_err(g[0], R.dY[0] if stem_holds == "dY" else R.d[0])
+    return out

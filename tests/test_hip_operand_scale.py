@@ -23,7 +23,8 @@ for _p in (PKG, REPO):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
-from hipmonocon import synth  # noqa: E402
+from plan_graph import (_bn_of, _model, _plan_graph, _read_node, stressed_batch,  # noqa: E402
+                        stressed_state_dict)
 
 pytestmark = pytest.mark.gpu
 
@@ -33,145 +34,9 @@ ULP = 2.0 ** -23
 FLOOR = 2.0 ** -18
 SHAPES = [(2, 128, 224), (2, 96, 1248)]      # 1248: KITTI's width, the odd-tile paths of the 16-column kernels
 SHAPE_IDS = ["B2_128x224", "B2_96x1248"]
-STRESS_SEED = 1234
-
-
-# ------------------------------------------------------------------------------------------------ the stressed state
-def _bn_of(conv):
-    """BatchNorm behind a train-plan conv (mc_api.hip build_net)"""
-    if conv.endswith(".project.0") or conv.endswith("level0.0") or conv.endswith("level1.0") or conv.endswith("base_layer.0"):
-        return conv[:-1] + "1"
-    if conv.endswith(".root.conv"):
-        return conv[:-len("conv")] + "bn"
-    if conv.endswith(".conv1") or conv.endswith(".conv2"):
-        return conv[:-len("convN")] + "bn" + conv[-1]
-    assert conv.endswith(".conv") and ".ida_" in conv, conv
-    return conv[:-len("conv")] + "bn1"
-
-
-def stressed_state_dict(sd, seed=STRESS_SEED):
-    """The golden state with (a) every conv in front of a train-mode BatchNorm rescaled per output channel, log-uniformly
-    over [1, 10^3] (running statistics rescaled with it: the network's function does not change), and (b) every such
-    BatchNorm's gamma log-uniform over [1e-2, 10] and beta uniform over [-3, 10] -- off-centre channels of both signs."""
-    g = torch.Generator().manual_seed(seed)
-    out = {k: v.clone() for k, v in sd.items()}
-    for conv, _ in _plan_convs():
-        w = out[conv + ".weight"]
-        bn = _bn_of(conv)
-        C = w.shape[0]
-        s = 10.0 ** (3.0 * torch.rand(C, generator=g, dtype=torch.float64))
-        out[conv + ".weight"] = (w.double() * s[:, None, None, None]).float()
-        out[bn + ".running_mean"] = (out[bn + ".running_mean"].double() * s).float()
-        out[bn + ".running_var"] = (out[bn + ".running_var"].double() * s * s).float()
-        out[bn + ".weight"] = (10.0 ** (-2.0 + 3.0 * torch.rand(C, generator=g, dtype=torch.float64))).float()
-        out[bn + ".bias"] = (-3.0 + 13.0 * torch.rand(C, generator=g, dtype=torch.float64)).float()
-    return out
-
-
-def stressed_batch(seed, B, H, W):
-    """(c) frames with a strong DC offset after Normalize: alternately a bright and a dark frame with faint texture"""
-    batch = synth.make_batch(seed, B, H, W)
-    img = batch["img"]
-    for b in range(B):
-        img[b] = (2.1 if b % 2 == 0 else -1.9) + 0.05 * img[b]
-    return batch
-
-
-# ------------------------------------------------------------------------------------------------ the train plan's graph
-def _plan_graph():
-    """The node order of the train plan (mc_train_plan.hip: stem, conv_bn, pool, deconv, tree and the neck loop), and for
-    every conv layer: (conv name, source nodes, residual node or -1, relu, output node, kernel size, stride)."""
-    nodes = [None]                   # node 0: the stem's output
-    recs = []
-    pooled = {}
-
-    def node():
-        nodes.append(None)
-        return len(nodes) - 1
-
-    def conv_bn(name, ks, stride, srcs, res, relu, dead=False):
-        if dead:
-            return -1
-        o = node()
-        recs.append((name, list(srcs), res, relu, o, ks, stride))
-        return o
-
-    def pool(x):
-        if x not in pooled:
-            pooled[x] = node()
-        return pooled[x]
-
-    def block(n, x, residual, stride):
-        y = conv_bn(n + ".conv1", 3, stride, [x], -1, True)
-        return conv_bn(n + ".conv2", 3, 1, [y], residual if residual >= 0 else x, True)
-
-    def tree(n, levels, cin, cout, stride, level_root, x, children):
-        bottom = pool(x) if stride > 1 else x
-        if level_root:
-            children = children + [bottom]
-        if levels == 1:
-            residual = bottom
-            if cin != cout:
-                residual = conv_bn(n + ".project.0", 1, 1, [bottom], -1, False)
-            x1 = block(n + ".tree1", x, residual, stride)
-            x2 = block(n + ".tree2", x1, -1, 1)
-            return conv_bn(n + ".root.conv", 1, 1, [x2, x1] + children, -1, True)
-        if cin != cout:
-            conv_bn(n + ".project.0", 1, 1, [bottom], -1, False, dead=True)
-        x1 = tree(n + ".tree1", levels - 1, cin, cout, stride, False, x, [])
-        return tree(n + ".tree2", levels - 1, cout, cout, 1, False, x1, children + [x1])
-
-    l0 = conv_bn("backbone.level0.0", 3, 1, [0], -1, True)
-    l1 = conv_bn("backbone.level1.0", 3, 2, [l0], -1, True)
-    l2 = tree("backbone.level2", 1, 32, 64, 2, False, l1, [])
-    l3 = tree("backbone.level3", 2, 64, 128, 2, True, l2, [])
-    l4 = tree("backbone.level4", 2, 128, 256, 2, True, l3, [])
-    l5 = tree("backbone.level5", 1, 256, 512, 2, True, l4, [])
-    layers = [l2, l3, l4, l5]
-    for i in range(3):
-        j = 4 - i - 2
-        for t in range(1, 4 - j):
-            pre = "neck.ida_%d." % i
-            p = conv_bn(pre + "proj_%d.conv" % t, 3, 1, [layers[j + t]], -1, True)
-            u = node()                                    # the depthwise deconv of p
-            layers[j + t] = conv_bn(pre + "node_%d.conv" % t, 3, 1, [layers[j + t - 1], u], -1, True)
-    return recs, len(nodes)
-
-
-def _plan_convs():
-    """(conv, bn) of every conv in front of a train-mode BatchNorm, the stem included (dead `project` convs too: they
-    still tick their statistics)"""
-    names = ["backbone.base_layer.0"] + [r[0] for r in _plan_graph()[0]]
-    from hipmonocon import netspec
-    shapes = netspec.state_shapes()
-    for k in shapes:                                     # the outer `project` of the two-level trees (never consumed)
-        if k.endswith(".project.0.weight") and k[:-len(".weight")] not in names:
-            names.append(k[:-len(".weight")])
-    return [(n, _bn_of(n)) for n in names]
 
 
 # ------------------------------------------------------------------------------------------------ running a plan
-def _model(sd, precision):
-    from model import MonoConDetector
-    m = MonoConDetector(34, pretrained_backbone=False)
-    m.load_state_dict(sd, strict=True)
-    return m.cuda().train().set_precision(precision)
-
-
-def _read_node(m, i, which=0):
-    """node i of the model's train plan (NCHW float32); a lazy node is formed without changing the plan"""
-    import ctypes as C
-    eng = m._engine()
-    dims = (C.c_int * 4)()
-    assert eng.lib.mc_train_debug_node(eng.h, int(i), int(which), None, dims, None) == 0
-    out = torch.empty(tuple(dims), dtype=torch.float32, device="cuda")
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    rc = eng.lib.mc_train_debug_node(eng.h, int(i), int(which), C.c_void_p(out.data_ptr()), dims, st)
-    assert rc == 0, rc
-    torch.cuda.synchronize()
-    return out.cpu()
-
-
 def _forward_nodes(sd, batch, precision, env, monkeypatch, backward=False):
     """one train step's forward (and optionally backward) under `env`; every node's value"""
     for k in ("MONOCON_HIP_LAZY_Z", "MONOCON_HIP_LAZY_MIN", "MONOCON_HIP_LAZY_FEAT"):
