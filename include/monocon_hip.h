@@ -177,6 +177,14 @@ int mc_backward(mc_handle *h, const float *grad_losses, void *stream);
  * parameter gradient is written. */
 int mc_backward_pred_grads(mc_handle *h, const float *grad_losses, const float *const grad_preds[MC_NUM_PREDS],
                            void *stream);
+/* mc_backward_pred_grads that also writes d objective / d img as (B,3,H,W) fp32 NCHW into grad_img (caller-owned,
+ * overwritten, valid until `stream` has reached this call's work).  grad_preds may be NULL.  grad_img == NULL: exactly
+ * mc_backward_pred_grads.  Fails on a heads-only plan.  The gradient is the stem's 7x7 data gradient, fp32 operands and
+ * accumulation in every precision mode; it is the caller's (rank's) own and unscaled: data parallelism exchanges nothing
+ * for it.  The plan keeps no pointer to grad_img after returning.  A call that succeeds has written grad_img: a plan in
+ * which no gradient reaches the stem fails instead of leaving it untouched. */
+int mc_backward_image_grad(mc_handle *h, const float *grad_losses, const float *const grad_preds[MC_NUM_PREDS],
+                           float *grad_img, void *stream);
 /* The train plan keeps ONE set of saved activations: mc_backward always differentiates the latest
  * mc_forward_train of the handle.  *generation = id of that forward (0 before the first one; every
  * forward gets a new id).  A caller that may interleave forwards and backwards (gradient accumulation
@@ -272,6 +280,19 @@ int mc_op_conv_wgrad(mc_handle *h, const float *const src[], const int src_chann
 int mc_op_stem(mc_handle *h, const float *img_nchw, int B, int H, int W,
                const float *weight_oihw, const float *scale, const float *bias, float *out,
                void *stream);
+/* op-level: the stem's data gradient on its own (stored form), any H, W >= 1:
+ * dx[b,c,y,x] = sum_{k,r,s} dy[b, y+3-r, x+3-s, k] * weight[k,c,r,s], dy NHWC (B,H,W,16) -> dx NCHW (B,3,H,W); positions
+ * outside the map contribute zero.  fp32 whatever the handle's precision mode.  dy_nhwc must be 16-byte aligned (a misaligned
+ * pointer fails with a message). */
+int mc_op_stem_dgrad(mc_handle *h, const float *dy_nhwc, const float *weight_oihw, int B, int H, int W,
+                     float *dx_nchw, void *stream);
+/* The fused form of the same kernel (what the f16x2 train plan runs, where the stem's dY exists nowhere in memory):
+ * d_nhwc is the masked gradient of the stem's activation, y_nhwc the raw conv output, both NHWC (B,H,W,16), and
+ * dY = P_k d + Q_k y + R_k is formed while a tile is staged, coef[16][4] = (P, Q, R, unused) per channel k: the
+ * BatchNorm-backward coefficients in the layout the train plan keeps them.  d_nhwc, y_nhwc and coef must be 16-byte
+ * aligned (pixels and coefficient rows are read 16 bytes at a time); a misaligned pointer fails with a message. */
+int mc_op_stem_dgrad_fused(mc_handle *h, const float *d_nhwc, const float *y_nhwc, const float *coef,
+                           const float *weight_oihw, int B, int H, int W, float *dx_nchw, void *stream);
 /* 2x2/2 max-pool, NHWC (model/backbone/dla.py:178-179). */
 int mc_op_maxpool2(mc_handle *h, const float *in, int B, int H, int W, int C, float *out,
                    void *stream);

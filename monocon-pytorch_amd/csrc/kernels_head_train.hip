@@ -908,4 +908,126 @@ hipError_t launch_stem_wgrad(const float *img, const float *dy, int B, int H, in
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------ 7x7 stem data gradient (the gradient of the image)
+// dX[b,c,y,x] = sum_{k<16} sum_{r,s<7} dY[b, y+3-r, x+3-s, k] * W[k,c,r,s]: NHWC (B,H,W,16) -> NCHW (B,3,H,W), positions outside
+// the map contribute zero.  2352 MAC per pixel against 64 (128 fused) bytes read: bound by the fp32 vector pipe.  VALU direct
+// form, fp32 operands and fp32 accumulation in every precision mode (one numeric behaviour; the path is optional):
+//   * a 16-row x 64-pixel output tile per workgroup; the (16+6) x (64+6) window of dY goes through LDS channel-planar, eight
+//     channels at a time (two passes: 51 KB, three workgroups per CU, where all sixteen would leave one);
+//   * a thread owns 4 x-adjacent pixels x 3 image channels: per (k, r) it reads its 12-pixel span of the window row (three
+//     ds_read_b128) and issues 7 x 3 x 4 = 84 FMAs, as 42 packed ones: the pixel pairs (0,1), (2,3) of a channel share a
+//     weight, the operand pairs at odd shifts come from a copy of the span displaced by one element;
+//   * the weights are read straight from the OIHW master weight: (k, c, r) is uniform, so they come through the scalar cache.
+// Summation order of one output: k ascending, r ascending, s ascending, one fmaf chain.
+// FUSED: `dy` is the masked gradient d of the stem's activation and dY = P d + Q y + R is formed while the tile is staged (the
+// fma chain of affine_bwd_kernel and of stem_wgrad_f16_kernel<true>, i.e. the same fp32 dY; coef[16][4] = P, Q, R, -).
+constexpr int SD_TH = 16, SD_TW = 64, SD_LW = 72, SD_ROWS = SD_TH + 6, SD_COLS = SD_TW + 6, SD_KH = 8;
+constexpr int SD_PLANE = SD_ROWS * SD_LW + 8;        // + 8: the planes of a thread's two channel quads land 32 banks apart
+typedef float f32x2s __attribute__((ext_vector_type(2)));
+template <bool FUSED>
+__global__ __launch_bounds__(256) void stem_dgrad_kernel(const float *__restrict__ dy, const float *__restrict__ ybn,
+                                                         const float *__restrict__ coef, const float *__restrict__ w, int B, int H,
+                                                         int W, float *__restrict__ dx, int vec_ok) {
+    __shared__ __attribute__((aligned(16))) float win[SD_KH * SD_PLANE];
+    const int tiles_x = (W + SD_TW - 1) / SD_TW, tiles_y = (H + SD_TH - 1) / SD_TH;
+    const int bt = blockIdx.x;
+    const int b = bt / (tiles_x * tiles_y);
+    const int ty0 = ((bt / tiles_x) % tiles_y) * SD_TH, tx0 = (bt % tiles_x) * SD_TW;
+    const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15;
+    f32x2s acc[3][2];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) acc[c][0] = acc[c][1] = f32x2s{0.f, 0.f};
+    for (int kh = 0; kh < 16 / SD_KH; ++kh) {
+        __syncthreads();                             // the previous pass's reads are done
+        // a thread stages one channel quad (q: the same in every iteration) of every 128th window pixel
+        // (a pass reads 32 of a pixel's 64 bytes: every NHWC line is fetched in both passes, the second time from L2 where the
+        // first pass's lines are still resident -- the price of the 51 KB window)
+        const int q = tid & 1, k0 = kh * SD_KH + q * 4;
+        f32x4 cf[4];
+        if constexpr (FUSED) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) cf[j] = reinterpret_cast<const f32x4 *>(coef)[k0 + j];
+        }
+        for (int px = tid >> 1; px < SD_ROWS * SD_COLS; px += 128) {
+            const int ly = px / SD_COLS, lx = px - ly * SD_COLS;
+            const int y = ty0 - 3 + ly, x = tx0 - 3 + lx;
+            f32x4 v = {0.f, 0.f, 0.f, 0.f};
+            if (y >= 0 && y < H && x >= 0 && x < W) {       // (outside the map: zero, not R)
+                const size_t off = (((size_t)b * H + y) * W + x) * 16 + k0;
+                v = *reinterpret_cast<const f32x4 *>(dy + off);
+                if constexpr (FUSED) {
+                    const f32x4 yv = *reinterpret_cast<const f32x4 *>(ybn + off);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) v[j] = fmaf(cf[j][0], v[j], fmaf(cf[j][1], yv[j], cf[j][2]));
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) win[(q * 4 + j) * SD_PLANE + ly * SD_LW + lx] = v[j];
+        }
+        __syncthreads();
+        for (int kk = 0; kk < SD_KH; ++kk) {
+            const float *wk = w + (size_t)(kh * SD_KH + kk) * 147;
+#pragma unroll
+            for (int r = 0; r < 7; ++r) {
+                // window row ty + 6 - r holds map row y + 3 - r; element tx*4 + p + 6 - s of it holds map column x + 3 - s
+                const f32x4 *row = reinterpret_cast<const f32x4 *>(&win[kk * SD_PLANE + (ty + 6 - r) * SD_LW + tx * 4]);
+                // (elements 10 and 11 of the span are columns 70, 71 of the row at tx = 15, which are never staged: they only
+                // reach ev[5] / od[4], which no shift uses)
+                float in[12];
+#pragma unroll
+                for (int q = 0; q < 3; ++q) {
+                    const f32x4 v = row[q];
+                    in[q * 4 + 0] = v[0]; in[q * 4 + 1] = v[1]; in[q * 4 + 2] = v[2]; in[q * 4 + 3] = v[3];
+                }
+                f32x2s ev[6], od[5];                 // ev[i] = in[2i], in[2i+1];  od[i] = in[2i+1], in[2i+2]
+#pragma unroll
+                for (int i = 0; i < 6; ++i) ev[i] = f32x2s{in[2 * i], in[2 * i + 1]};
+#pragma unroll
+                for (int i = 0; i < 5; ++i) od[i] = f32x2s{in[2 * i + 1], in[2 * i + 2]};
+#pragma unroll
+                for (int s = 0; s < 7; ++s) {
+                    const int o = 6 - s;             // pixel p reads in[p + o]
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        const float wv = wk[(c * 7 + r) * 7 + s];
+                        const f32x2s w2 = {wv, wv};
+#pragma unroll
+                        for (int hp = 0; hp < 2; ++hp) {
+                            const f32x2s a = (o & 1) ? od[hp + o / 2] : ev[hp + o / 2];
+                            acc[c][hp] = __builtin_elementwise_fma(a, w2, acc[c][hp]);
+                        }
+                    }
+                }
+            }
+        }
+    }
+    const int y = ty0 + ty, x = tx0 + tx * 4;
+    if (y >= H || x >= W) return;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float *dst = dx + (((size_t)b * 3 + c) * H + y) * W + x;
+        if (vec_ok && x + 3 < W) {
+            *reinterpret_cast<f32x4 *>(dst) = f32x4{acc[c][0][0], acc[c][0][1], acc[c][1][0], acc[c][1][1]};
+        } else {
+#pragma unroll
+            for (int p = 0; p < 4; ++p)
+                if (x + p < W) dst[p] = acc[c][p >> 1][p & 1];
+        }
+    }
+}
+hipError_t launch_stem_dgrad(const float *dy, const float *w_oihw, int B, int H, int W, float *dx, hipStream_t st, const float *y,
+                             const float *coef) {
+    if (!dy || !w_oihw || !dx || B < 1 || H < 1 || W < 1 || (y != nullptr) != (coef != nullptr)) return hipErrorInvalidValue;
+    if (reinterpret_cast<uintptr_t>(dy) % 16 || reinterpret_cast<uintptr_t>(y) % 16 || reinterpret_cast<uintptr_t>(coef) % 16)
+        return hipErrorInvalidValue;                 // pixels and coefficient rows are read 16 bytes at a time
+    const long long nb = (long long)B * ((W + SD_TW - 1) / SD_TW) * ((H + SD_TH - 1) / SD_TH);
+    if (nb > 0x7fffffffLL) return hipErrorInvalidValue;
+    const int vec_ok = (W % 4 == 0 && reinterpret_cast<uintptr_t>(dx) % 16 == 0) ? 1 : 0;      // 16-byte stores of four pixels
+    if (y)
+        hipLaunchKernelGGL(stem_dgrad_kernel<true>, dim3((unsigned)nb), dim3(256), 0, st, dy, y, coef, w_oihw, B, H, W, dx, vec_ok);
+    else
+        hipLaunchKernelGGL(stem_dgrad_kernel<false>, dim3((unsigned)nb), dim3(256), 0, st, dy, nullptr, nullptr, w_oihw, B, H, W, dx, vec_ok);
+    return hipGetLastError();
+}
+
 }  // namespace mc

@@ -945,6 +945,29 @@ int mc_op_stem(mc_handle *h, const float *img, int B, int H, int W, const float 
     return 0;
 }
 
+int mc_op_stem_dgrad(mc_handle *h, const float *dy_nhwc, const float *weight_oihw, int B, int H, int W, float *dx_nchw,
+                     void *stream) {
+    if (!h) return -1;
+    if (!dy_nhwc || !weight_oihw || !dx_nchw) return fail(h, "mc_op_stem_dgrad: null argument");
+    if (B < 1 || H < 1 || W < 1) return fail(h, "mc_op_stem_dgrad: B, H, W must be >= 1 (got %d, %d, %d)", B, H, W);
+    if (reinterpret_cast<uintptr_t>(dy_nhwc) % 16) return fail(h, "mc_op_stem_dgrad: dy_nhwc must be 16-byte aligned");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, launch_stem_dgrad(dy_nhwc, weight_oihw, B, H, W, dx_nchw, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int mc_op_stem_dgrad_fused(mc_handle *h, const float *d_nhwc, const float *y_nhwc, const float *coef, const float *weight_oihw,
+                           int B, int H, int W, float *dx_nchw, void *stream) {
+    if (!h) return -1;
+    if (!d_nhwc || !y_nhwc || !coef || !weight_oihw || !dx_nchw) return fail(h, "mc_op_stem_dgrad_fused: null argument");
+    if (B < 1 || H < 1 || W < 1) return fail(h, "mc_op_stem_dgrad_fused: B, H, W must be >= 1 (got %d, %d, %d)", B, H, W);
+    if (reinterpret_cast<uintptr_t>(d_nhwc) % 16 || reinterpret_cast<uintptr_t>(y_nhwc) % 16 || reinterpret_cast<uintptr_t>(coef) % 16)
+        return fail(h, "mc_op_stem_dgrad_fused: d_nhwc, y_nhwc and coef must be 16-byte aligned");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, launch_stem_dgrad(d_nhwc, weight_oihw, B, H, W, dx_nchw, static_cast<hipStream_t>(stream), y_nhwc, coef));
+    return 0;
+}
+
 int mc_op_maxpool2(mc_handle *h, const float *in, int B, int H, int W, int C, float *out, void *stream) {
     if (!h) return -1;
     if (!in || !out || (C % 4) || (H % 2) || (W % 2)) return fail(h, "mc_op_maxpool2: bad argument");

@@ -141,6 +141,7 @@ struct BwdStep {
     // data parallelism: the gradient bucket (mc_internal.h) that is complete once this step has been enqueued, or -1
     int bucket = -1;
     bool feat_dgrad = false;         // head-only plan: the data gradient into the external feat node (TrainState::skip_feat_dgrad)
+    bool img_dgrad = false;          // the stem's data gradient: runs only in a backward that asked for the image gradient (TrainState::gimg_ext)
     hipEvent_t ready = nullptr;      // side step: everything it reads is complete at this point of the caller's stream
     hipEvent_t fin = nullptr;        // side step some later step waits for: it has finished
 };
@@ -181,6 +182,9 @@ struct TrainState {
     const float *feat_ext = nullptr;
     float *gfeat_ext = nullptr;
     bool skip_feat_dgrad = false;    // head-only plan, mc_head_backward(grad_feat = NULL)
+    // mc_backward_image_grad: where the gradient of the image goes, (B,3,H,W) NCHW.  Caller-owned like gfeat_ext: set by the
+    // entry point for ONE backward and cleared by the step that wrote it
+    float *gimg_ext = nullptr;
     // plan-owned
     mc_targets targets{};
     float *dpred[10] = {nullptr};
@@ -1011,6 +1015,20 @@ struct TB {   // train plan builder
             HIPCHK(hh, launch_stem_wgrad(ts->img, dyp, B, H, W, part, dw, st, imax, imax ? dymax : nullptr, yfp, cfp, yfmax));
             return 0;
         }, ON_SIDE);
+        // the data gradient of the image, for a backward that asked for it (BwdStep::img_dgrad; any other backward launches
+        // exactly what it launched without this step).  It reads the same buffer as the weight gradient, in the same form
+        // (dY, or d with (y, coef)), on the caller's stream while the weight gradient runs on the side stream; it is pushed
+        // before the buffer's release, whose last reader for the pool stays the side step (a later writer on the caller's
+        // stream is ordered behind this step anyway).  fp32 in every mode; no gradient bucket: nothing is exchanged for it,
+        // the image gradient is the rank's own and unscaled.
+        const float *wm = P("backbone.base_layer.0.weight", 16 * 147);
+        const int dgrad = push_bwd([=, ts = ts, B = B, H = H, W = W](mc_handle *hh, hipStream_t st) {
+            if (ts->gimg_ext) HIPCHK(hh, launch_stem_dgrad(dyp, wm, B, H, W, ts->gimg_ext, st, yfp, cfp));
+            ts->gimg_ext = nullptr;       // written once, for the call that asked for it: never a stale pointer later
+            return 0;
+        });
+        ts->bwd[dgrad].img_dgrad = true;
+        ts->bwd[dgrad].bucket = -1;
         g_release(r.z, wgrad);
     }
 
@@ -1066,6 +1084,7 @@ static TrainState *build_train(mc_handle *h, int B, int H, int W, bool head_only
     {
         bool seen[MC_NUM_GRAD_BUCKETS] = {};
         for (auto s = ts->bwd.rbegin(); s != ts->bwd.rend(); ++s) {
+            if (s->bucket < 0) continue;         // (the image's data gradient: in no bucket)
             if (seen[s->bucket]) s->bucket = -1;
             else seen[s->bucket] = true;
         }
@@ -1159,6 +1178,7 @@ static int forward_train_impl(mc_handle *h, const float *img, const mc_labels *l
     HIPCHK(h, ts->pack_batch.launch(st));
     h->train_generation = ++g_train_generation;
     ts->gfeat_ext = nullptr;      // (a previous mc_head_backward's output tensor may be gone by now)
+    ts->gimg_ext = nullptr;
     for (auto &f : ts->fwd)
         if (f(h, st)) return -1;
     return 0;
@@ -1259,6 +1279,22 @@ int mc_backward_pred_grads(mc_handle *h, const float *grad_losses, const float *
     return full_backward(h, "mc_backward_pred_grads", grad_losses, grad_preds, stream);
 }
 
+int mc_backward_image_grad(mc_handle *h, const float *grad_losses, const float *const grad_preds[MC_NUM_PREDS], float *grad_img,
+                           void *stream) {
+    if (!h) return -1;
+    if (h->train && h->train->head_only)
+        return fail(h, "mc_backward_image_grad: the handle holds a heads-only plan (mc_head_forward_train), which has no image: "
+                       "mc_head_backward returns the gradient of feat");
+    if (h->train) h->train->gimg_ext = grad_img;
+    const int rc = full_backward(h, "mc_backward_image_grad", grad_losses, grad_preds, stream);
+    // the step that writes grad_img clears the pointer: still set after a backward that succeeded means the plan has no such
+    // step (no gradient reached the stem) -- an error, never an output left unwritten
+    const bool unwritten = h->train && h->train->gimg_ext != nullptr;
+    if (h->train) h->train->gimg_ext = nullptr;      // (a backward that failed before the step: no stale pointer either)
+    if (!rc && unwritten) return fail(h, "mc_backward_image_grad: the plan has no data-gradient step for the image (no gradient reaches the stem)");
+    return rc;
+}
+
 static int backward_run(mc_handle *h, TrainState *ts, const float *grad_losses, void *stream);
 
 static int backward_impl(mc_handle *h, TrainState *ts, const float *grad_losses, const float *const grad_preds[MC_NUM_PREDS],
@@ -1283,6 +1319,7 @@ static int backward_run(mc_handle *h, TrainState *ts, const float *grad_losses, 
     if (dp && mc_comm_prepare(h)) return -1;
     for (const BwdStep &s : ts->bwd) {
         if (s.feat_dgrad && ts->skip_feat_dgrad) continue;
+        if (s.img_dgrad && !ts->gimg_ext) continue;
         if (ts->dual && s.stream == ON_SIDE) {
             // everything this step reads (dY of its layer, forward activations) is ready at this point of
             // the main stream; its outputs (the weight gradient) are first needed after mc_backward
@@ -1348,7 +1385,8 @@ int mc_profile_train(mc_handle *h, int iters, double ms[3], double flops[3], dou
     hipStream_t st = static_cast<hipStream_t>(stream);
     std::vector<const Fn *> all;      // every closure of the step in launch order, all on the caller's stream
     for (const Fn &f : ts->fwd) all.push_back(&f);
-    for (const BwdStep &s : ts->bwd) all.push_back(&s.fn);
+    for (const BwdStep &s : ts->bwd)
+        if (!s.img_dgrad) all.push_back(&s.fn);      // (the image's data gradient: no replay has an output for it)
     const size_t n = all.size();
     std::vector<hipEvent_t> ev(2 * n);
     for (auto &e : ev) HIPCHK(h, hipEventCreate(&e));

@@ -184,6 +184,12 @@ int stem_wgrad_blocks(int B, int H, int W);
 hipError_t launch_stem_wgrad(const float *img, const float *dy, int B, int H, int W, float *partial, float *dw,
                              hipStream_t st, const unsigned *img_amax = nullptr, const unsigned *dy_amax = nullptr,
                              const float *y = nullptr, const float *coef = nullptr, const unsigned *y_amax = nullptr);
+// the stem's data gradient: dY NHWC (B,H,W,16) x the OIHW master weight (16,3,7,7) -> dX NCHW (B,3,H,W), fp32 operands and
+// accumulation in every precision mode, any H, W >= 1.  Stored form: `dy` is the gradient wrt the raw conv output.  Fused form
+// (y and coef non-null, the convention of launch_stem_wgrad_f16): `dy` is the masked gradient d of the stem's activation and
+// dY = P d + Q y + R is formed while the tile is staged, coef[16][4] = (P, Q, R, -) per channel.
+hipError_t launch_stem_dgrad(const float *dy, const float *w_oihw, int B, int H, int W, float *dx, hipStream_t st,
+                             const float *y = nullptr, const float *coef = nullptr);
 
 // ---- conv weight gradient (wgrad_mfma.hip)
 struct WgradArgs {

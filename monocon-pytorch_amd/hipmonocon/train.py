@@ -9,7 +9,9 @@ loop (``sum(loss_dict.values()).backward()``, ``clip_grad_norm_``, ``optimizer.s
 engine/monocon_engine.py:84-102) runs unchanged on top of it.  The ten prediction maps are
 differentiable outputs of the same Function: an objective that reaches them (an extra term on
 ``pred_dict``, ``head._get_losses`` against other targets) back-propagates through
-``mc_backward_pred_grads``, which adds their gradients to the loss gradients in one pass.
+``mc_backward_pred_grads``, which adds their gradients to the loss gradients in one pass.  The image
+is a differentiable input too: when it requires a gradient the backward goes through
+``mc_backward_image_grad`` and autograd receives d objective / d img (``img.grad`` of a leaf).
 """
 import ctypes as C
 
@@ -137,13 +139,22 @@ class _HipTrainStep(torch.autograd.Function):
                 "accumulation run forward+backward per micro-batch)" % (ctx.generation, gen.value))
         g = grad_losses.contiguous().float()
         gp = _pred_grads(grads[10:])
+        # the image asks for its gradient (a leaf with requires_grad_(), or the output of something that does): the stem's
+        # data gradient runs as one more step of the backward and writes it here; otherwise the calls are the usual ones
+        gimg = torch.empty_like(ctx.keep[0]) if ctx.needs_input_grad[3] else None
         with torch.cuda.device(g.device):
-            if gp is None:
+            if gimg is not None:
+                what = "mc_backward_image_grad"
+                rc = eng.lib.mc_backward_image_grad(eng.h, C.c_void_p(g.data_ptr()), None if gp is None else _ptr_array(gp),
+                                                    C.c_void_p(gimg.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+            elif gp is None:
+                what = "mc_backward"
                 rc = eng.lib.mc_backward(eng.h, C.c_void_p(g.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream))
             else:
+                what = "mc_backward_pred_grads"
                 rc = eng.lib.mc_backward_pred_grads(eng.h, C.c_void_p(g.data_ptr()), _ptr_array(gp),
                                                     C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _lib.check(eng.h, rc, "mc_backward" if gp is None else "mc_backward_pred_grads")
+        _lib.check(eng.h, rc, what)
         # data parallel: with a communicator owned by the handle mc_backward already exchanged the gradients bucket by
         # bucket, overlapped with the backbone's backward (csrc/mc_comm.hip); otherwise one all-reduce of the flat buffer
         if eng.comm_world:
@@ -162,7 +173,7 @@ class _HipTrainStep(torch.autograd.Function):
                 out.append(gb.detach())
             else:
                 out.append(gb.clone())    # caller is accumulating across backward passes: torch adds a copy
-        return (None, None, None, None, None, None, *out)
+        return (None, None, None, gimg, None, None, *out)
 
 
 def _require_objects(detector, label, pad_hw, num_classes=3):
