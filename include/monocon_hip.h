@@ -211,6 +211,13 @@ int mc_head_backward_pred_grads(mc_handle *h, const float *grad_losses, const fl
  * node, and for the stem dY -- or, where the f16x2 stem weight gradient forms dY on the fly (MONOCON_HIP_STEM_FUSE=1
  * with the statistics left by level0's data-gradient epilogue), the masked gradient d = dZ * [z > 0]. */
 int mc_train_debug_node(mc_handle *h, int node, int which, float *out_nchw, int dims[4], void *stream);
+/* Debugging aid: the same for the eval plan of the last mc_forward_infer / stage forward.  which=0: the activation of
+ * graph node `node` (the train plan's node ids); which=1: the raw hidden map of the fused head conv, (B, 576, H/4, W/4),
+ * bias added, before AttnBN; which=2: the per-image AttnBN affine as (B, 2, 9, 64), [b][0] scale and [b][1] shift per
+ * (head, channel); which=3: the AttnBN statistic mean / sqrt(var + 1e-3) as (B, 1, 9, 64), folded on the host from
+ * the head conv's per-patch partials as the kernel folds them (synchronises `stream`).  `node` is ignored for which=1..3.
+ * out_nchw == NULL reports dims only. */
+int mc_infer_debug_node(mc_handle *h, int node, int which, float *out_nchw, int dims[4], void *stream);
 
 /* ---- data parallelism -----------------------------------------------------------
  * The reference is single-GPU (README.MD:11,15: "multi-GPU training is not supported"); these entry points are the

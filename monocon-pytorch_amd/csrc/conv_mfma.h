@@ -89,6 +89,12 @@ struct ConvArgs {
     int relu;
     float *stats;            // optional [B][patches per image][CoutP][2] partial (sum, sumsq) of (v - shift), per 4x8 patch
     const float *stat_shift; // [Cout] or null
+    // 1: the second partial is the patch's CENTRED second moment sum (d - m)^2, d = v - shift, m = (patch sum) / 32, instead of
+    // sum d^2: a consumer combines the patches by Chan's formula (head_attn_kernel), and a map that is flat beside its offset
+    // from `shift` no longer cancels in fp32 ((mean - shift)^2 / var = 1e4 cost 3e-4 of s = mean / sqrt(var), now 1e-6).
+    // Whole 4x8 patches without a residual only: the eval plan's fused head conv.  The order within a patch is fixed by the
+    // MFMA layout as before, so the partials stay independent of the workgroup shape.
+    int stats_centred;
     int ppr, ppi, chunks;    // patches per row / per image, workgroup chunks per image
     int cfg;                 // ConvCfgId workgroup shape (CFG_AUTO = conv_pick_cfg)
     // output / residual pixel mapping in floats (0 = dense NHWC: img = Hout*Wout*ld, row = Wout*ld, px = ld);
@@ -400,6 +406,17 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs &a, f32x16 (&acc)[W
             }
             if (do_stats) {
                 ssum += __shfl_xor(ssum, 32);
+                if constexpr (!bm) {
+                    if (a.stats_centred) {       // (wave-uniform) ConvArgs::stats_centred: a second pass over the accumulators
+                        const float m = ssum * 0.03125f;
+                        ssq = 0.f;
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            const float e = (__builtin_fmaf(acc[tm][tn][r], sc, bi) - sh) - m;
+                            ssq = __builtin_fmaf(e, e, ssq);
+                        }
+                    }
+                }
                 ssq += __shfl_xor(ssq, 32);
                 if (g == 0 && nok) {
                     float *dst = a.stats + (((size_t)img * a.ppi + patch0 + p) * a.CoutP + n) * 2;

@@ -327,6 +327,17 @@ __global__ __launch_bounds__(256, 1) void conv_wres_kernel(const ConvArgs a, con
         vmax = fmaxf(vmax, e_live ? tmax : 0.f);
         if constexpr (BM || STATS) {
             ssum += __shfl_xor(ssum, 32);
+            if constexpr (STATS && !BM && !RES) {
+                if (a.stats_centred) {           // ConvArgs::stats_centred, exactly as conv_epilogue forms it (Y is still the tile's)
+                    const float m = ssum * 0.03125f;
+                    ssq = 0.f;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const float e = (__builtin_fmaf(Y[r], sc, bi) - sh) - m;
+                        ssq = __builtin_fmaf(e, e, ssq);
+                    }
+                }
+            }
             ssq += __shfl_xor(ssq, 32);
             if (g == 0 && nok && e_live) {
                 float *dst = a.stats + (((size_t)e_img * a.ppi + e_patch) * a.CoutP + ncol) * 2;

@@ -390,7 +390,9 @@ __global__ __launch_bounds__(256) void head_attn_kernel(const float *__restrict_
                                                          float *__restrict__ shift) {
     const int b = blockIdx.x, h = blockIdx.y, c = threadIdx.x & 63, part = threadIdx.x >> 6;
     const int CP = NUM_HEADS * HEAD_CH;
-    // per-patch partials (conv epilogue) summed in fp64: four waves take interleaved quarters, fixed order
+    // per-patch partials (conv epilogue, ConvArgs::stats_centred) combined in fp64: four waves take interleaved quarters, fixed
+    // order.  A patch brings S = sum d and M = sum (d - S / 32)^2 of its 32 values d = v - rm; Chan's formula for equal counts:
+    // sum (d - mean)^2 = sum_p (M_p + S_p^2 / 32) - (sum_p S_p)^2 / n.  s2 collects the first sum.
     double s1 = 0.0, s2 = 0.0;
     const float2 *q = reinterpret_cast<const float2 *>(stats) + (size_t)b * chunks * CP + h * HEAD_CH + c;
     int k = part;
@@ -399,12 +401,12 @@ __global__ __launch_bounds__(256) void head_attn_kernel(const float *__restrict_
 #pragma unroll
         for (int u = 0; u < 8; ++u) v[u] = q[(size_t)(k + 4 * u) * CP];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) { s1 += (double)v[u].x; s2 += (double)v[u].y; }
+        for (int u = 0; u < 8; ++u) { s1 += (double)v[u].x; s2 += (double)v[u].y + (double)v[u].x * (double)v[u].x * 0.03125; }
     }
     for (; k < chunks; k += 4) {
         const float2 v = q[(size_t)k * CP];
         s1 += (double)v.x;
-        s2 += (double)v.y;
+        s2 += (double)v.y + (double)v.x * (double)v.x * 0.03125;
     }
     __shared__ double red[2][4][64];
     red[0][part][c] = s1;

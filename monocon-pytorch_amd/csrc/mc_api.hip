@@ -276,6 +276,10 @@ struct Builder {
             *stats_out = mem.alloc((size_t)s0.B * chunks * L.coutp * 2);
             a.stats = *stats_out;
             a.stat_shift = stat_shift;
+            // per-patch centred second moments (head_attn_kernel combines them): whole 4x8 patches, no residual, and one partial
+            // per patch -- true of the head conv on any map the plan accepts (H, W multiples of 32: a quarter-resolution map of 8s)
+            a.stats_centred = 1;
+            if (res || Ho % 4 || Wo % 8 || chunks != (Ho / 4) * (Wo / 8)) { ok = false; h->err = "statistics of partial patches at " + L.conv; }
         }
         if (chunks_out) *chunks_out = chunks;
         op.flops = 2.0 * s0.B * Ho * Wo * (double)L.cout * cin * L.ks * L.ks;
@@ -437,6 +441,7 @@ static Plan *get_plan(mc_handle *h, int B, int H, int W) {
     for (int i = 0; i < 6; ++i) pl->lv[i] = t[g.lv[i]];
     const Tensor feat = t[g.feat];
     pl->feat = feat;
+    pl->nodes = t;
     pl->n_neck_ops = (int)pl->ops.size();
 
     // heads pass 1: fused 3x3 64 -> 9x64 (+bias) with per-(image,channel) statistics
@@ -446,6 +451,8 @@ static Plan *get_plan(mc_handle *h, int B, int H, int W) {
                             h->head_rm, &chunks);
     float *hs_scale = bd.mem.alloc((size_t)B * NUM_HEADS * HEAD_CH);
     float *hs_shift = bd.mem.alloc((size_t)B * NUM_HEADS * HEAD_CH);
+    pl->hidden = hidden; pl->hs_scale = hs_scale; pl->hs_shift = hs_shift;
+    pl->head_stats = stats; pl->head_chunks = chunks;
     {
         Op op{};
         op.kind = OP_HEAD_ATTN;
@@ -750,6 +757,62 @@ int mc_forward_infer(mc_handle *h, const float *img, int B, int H, int W, float 
     for (const Op &op : pl->ops)
         if (run_op(h, op, st)) return -1;
     if (feat_nchw) HIPCHK(h, launch_nhwc_to_nchw(pl->feat.p, B, pl->feat.C, pl->feat.H, pl->feat.W, feat_nchw, st));
+    return 0;
+}
+
+// debugging aid: read the eval plan of the last forward (h->last_plan) as NCHW, on the calling convention of
+// mc_train_debug_node.  The eval plan gives every tensor a buffer of its own, so everything stays readable after the forward.
+//   which = 0: the activation of graph node `node` (NetGraph ids, the train plan's: 0 = stem output, 1 = level0, ...)
+//   which = 1: the raw hidden map of the fused head conv, (B, 9 * 64, H/4, W/4): bias added, before AttnBN (`node` ignored)
+//   which = 2: head_attn_kernel's AttnBN affine as (B, 2, 9, 64): [b][0] the scale, [b][1] the shift of every
+//              (head, channel) of image b (`node` ignored)
+//   which = 3: the AttnBN statistic s = mean / sqrt(var + 1e-3) as (B, 1, 9, 64), folded on the HOST in fp64 from the conv
+//              epilogue's per-patch fp32 partials exactly as head_attn_kernel folds them (no launch; synchronises `stream`)
+int mc_infer_debug_node(mc_handle *h, int node, int which, float *out_nchw, int dims[4], void *stream) {
+    if (!h || !h->last_plan) return fail(h, "mc_infer_debug_node: no eval plan has run");
+    const Plan *pl = h->last_plan;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (which == 2) {
+        if (dims) { dims[0] = pl->B; dims[1] = 2; dims[2] = NUM_HEADS; dims[3] = HEAD_CH; }
+        if (!out_nchw) return 0;
+        const size_t n = (size_t)NUM_HEADS * HEAD_CH;
+        HIPCHK(h, hipMemcpy2DAsync(out_nchw, 2 * n * sizeof(float), pl->hs_scale, n * sizeof(float), n * sizeof(float), pl->B,
+                                   hipMemcpyDeviceToDevice, st));
+        HIPCHK(h, hipMemcpy2DAsync(out_nchw + n, 2 * n * sizeof(float), pl->hs_shift, n * sizeof(float), n * sizeof(float), pl->B,
+                                   hipMemcpyDeviceToDevice, st));
+        return 0;
+    }
+    if (which == 3) {
+        if (dims) { dims[0] = pl->B; dims[1] = 1; dims[2] = NUM_HEADS; dims[3] = HEAD_CH; }
+        if (!out_nchw) return 0;
+        const int CP = NUM_HEADS * HEAD_CH, chunks = pl->head_chunks;
+        std::vector<float> part((size_t)pl->B * chunks * CP * 2), rm(CP), s((size_t)pl->B * CP);
+        HIPCHK(h, hipStreamSynchronize(st));
+        HIPCHK(h, hipMemcpy(part.data(), pl->head_stats, part.size() * sizeof(float), hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(rm.data(), h->head_rm, rm.size() * sizeof(float), hipMemcpyDeviceToHost));
+        const double n = (double)pl->feat.H * pl->feat.W;
+        for (int b = 0; b < pl->B; ++b)
+            for (int c = 0; c < CP; ++c) {
+                double s1 = 0.0, s2 = 0.0;
+                for (int k = 0; k < chunks; ++k) {
+                    const float *q = &part[(((size_t)b * chunks + k) * CP + c) * 2];
+                    s1 += (double)q[0];
+                    s2 += (double)q[1] + (double)q[0] * (double)q[0] * 0.03125;       // (centred per-patch moments: Chan's formula)
+                }
+                const double mean = (double)rm[c] + s1 / n, var = (s2 - s1 * s1 / n) / (n - 1.0);
+                s[(size_t)b * CP + c] = (float)(mean / std::sqrt(var + 1e-3));
+            }
+        HIPCHK(h, hipMemcpy(out_nchw, s.data(), s.size() * sizeof(float), hipMemcpyHostToDevice));
+        return 0;
+    }
+    if (which != 0 && which != 1) return fail(h, "mc_infer_debug_node: which = %d (0 node, 1 hidden, 2 AttnBN affine, 3 s)", which);
+    if (!which && (node < 0 || node >= (int)pl->nodes.size()))
+        return fail(h, "mc_infer_debug_node: node %d of %d", node, (int)pl->nodes.size());
+    const Tensor &t = which ? pl->hidden : pl->nodes[node];
+    if (dims) { dims[0] = t.B; dims[1] = t.C; dims[2] = t.H; dims[3] = t.W; }
+    if (!out_nchw) return 0;
+    if (!t.p) return fail(h, "mc_infer_debug_node: node has no buffer");
+    HIPCHK(h, launch_nhwc_to_nchw(t.p, t.B, t.C, t.H, t.W, out_nchw, st));
     return 0;
 }
 

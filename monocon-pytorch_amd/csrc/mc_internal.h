@@ -145,6 +145,11 @@ struct Plan {
     std::vector<Op> ops;
     PlanMem mem;
     Tensor feat, lv[6];
+    std::vector<Tensor> nodes;   // activation of every graph node (mc_infer_debug_node)
+    Tensor hidden;               // the fused head conv's raw output: 9 x 64 channels, bias added, before AttnBN
+    float *hs_scale = nullptr, *hs_shift = nullptr;   // head_attn_kernel's per-(image, head, channel) AttnBN affine
+    const float *head_stats = nullptr;                // the head conv's per-patch (sum, sum of squares) of v - rm
+    int head_chunks = 0;                              // patches per image
     int stem_op = -1, head_apply_op = -1;
     int n_backbone_ops = 0, n_neck_ops = 0;
     double flops = 0, hbm_bytes = 0;

@@ -1,7 +1,8 @@
-"""The train plan's graph as the tests see it, the stressed state, and the layer-local backward reference.
+"""The network graph as the tests see it, the stressed state, and the layer-local backward and eval references.
 
 A plain module (no fixtures): `test_hip_operand_scale.py` (forward, layer by layer), `test_hip_backward_layers.py` (backward,
-layer by layer) and `test_backward_reference_cpu.py` (the checker checked against autograd) share it.
+layer by layer), `test_backward_reference_cpu.py` (the checker checked against autograd), `test_hip_eval_layers.py` (the eval
+plan, layer by layer) and `test_eval_reference_cpu.py` (that checker checked against the oracle) share it.
 
 The graph mirrors mc_api.hip `build_net` / mc_train_plan.hip: node 0 is the stem's output, every live conv + BatchNorm, every
 2x2 max-pool and every depthwise deconv makes one node, in forward order.
@@ -18,6 +19,7 @@ and nothing is amplified.  The buffers, as `mc_train_debug_node` hands them out 
              skipped and the buffer keeps d = dZ * [z > 0], the masked gradient.  With STEM_FUSE=0, in fp32 / bf16x3, or with
              MONOCON_HIP_BM_EPILOGUE=0 it holds dY.
 """
+import math
 import os
 import sys
 
@@ -92,6 +94,7 @@ class PlanGraph:
         self.recs, self.pools, self.deconvs, self.steps = [], [], [], []
         self.node_c, self.node_down = [16], [1]
         self.feat = -1
+        self.levels = []          # the nodes of the backbone's level outputs l0 .. l5
 
     @property
     def n_nodes(self):
@@ -175,6 +178,7 @@ def plan_graph():
     l3 = tree("backbone.level3", 2, 64, 128, 2, True, l2, [])
     l4 = tree("backbone.level4", 2, 128, 256, 2, True, l3, [])
     l5 = tree("backbone.level5", 1, 256, 512, 2, True, l4, [])
+    G.levels = [l0, l1, l2, l3, l4, l5]
     layers = [l2, l3, l4, l5]
     for i in range(3):
         j = 4 - i - 2
@@ -430,3 +434,315 @@ def compare_normwise(R, g, grads, stem_holds="dY"):
         out[("dZ", name)] = norm_err(g[o], R.dZ[o].ref)
     out[("stem g", STEM)] = norm_err(g[0], R.dY[0] if stem_holds == "dY" else R.d[0])
     return out
+
+
+# ------------------------------------------------------------------------------------------------ the eval plan
+# The eval plan (mc_api.hip get_plan) runs the same graph with the same node ids; `mc_infer_debug_node` reads it after a
+# forward: every node, the raw hidden map of the fused head conv, head_attn_kernel's AttnBN affine and its statistic s.
+# `eval_reference` is the layer-local fp64 reference of that forward: like the backward reference it never computes more than
+# ONE layer from the plan's own buffers, so no ReLU, max-pool or clamp decision of an earlier layer can flip.
+U24 = 2.0 ** -24
+ABN_EPS = 1e-3
+LOGIT_CLAMP = math.log(9999.0)          # sigmoid(x) = 1e-4 at -ln 9999, 1 - 1e-4 at +ln 9999
+HEADS = ("heatmap_head", "wh_head", "offset_head", "center2kpt_offset_head", "kpt_heatmap_head", "kpt_heatmap_offset_head",
+         "dim_head", "depth_head", "dir_feat")
+HEAD_OUT = {"heatmap_head": [("center_heatmap_pred", "head.heatmap_head.3")], "wh_head": [("wh_pred", "head.wh_head.3")],
+            "offset_head": [("offset_pred", "head.offset_head.3")],
+            "center2kpt_offset_head": [("center2kpt_offset_pred", "head.center2kpt_offset_head.3")],
+            "kpt_heatmap_head": [("kpt_heatmap_pred", "head.kpt_heatmap_head.3")],
+            "kpt_heatmap_offset_head": [("kpt_heatmap_offset_pred", "head.kpt_heatmap_offset_head.3")],
+            "dim_head": [("dim_pred", "head.dim_head.3")], "depth_head": [("depth_pred", "head.depth_head.3")],
+            "dir_feat": [("alpha_cls_pred", "head.dir_cls.0"), ("alpha_offset_pred", "head.dir_reg.0")]}
+HEAT_KEYS = ("center_heatmap_pred", "kpt_heatmap_pred")
+STEM_REC = (STEM, [-1], -1, True, 0, 7, 1)            # the stem as a conv record: its source "node -1" is the image
+EVAL_KINDS = ("stem", "3x3s1", "3x3s2", "1x1", "deconv", "head hidden")
+
+
+def heat_clamps():
+    """(floor, ceiling) of a float32 heat map: what the reference's clamp(sigmoid(x), 1e-4, 1 - 1e-4) saturates at"""
+    lo, hi = torch.clamp(torch.tensor([-1.0, 2.0], dtype=torch.float32), 1e-4, 1.0 - 1e-4)
+    return lo, hi
+
+
+def _bn_params(sd, bn, dtype):
+    return [sd[bn + k].to(dtype) for k in (".weight", ".bias", ".running_mean", ".running_var")]
+
+
+def eval_conv(sd, rec, nodes, dtype, batch_norm=None):
+    """one conv layer of the eval forward from `nodes`: conv of the source nodes, eval BatchNorm in the unfolded form
+    gamma (x - rm) / sqrt(rv + eps) + beta (batch_norm: a callable (y, gamma, beta, rm, rv) in its place), residual, ReLU"""
+    name, srcs, res, relu, o, ks, stride = rec
+    x = torch.cat([nodes[s].to(dtype) for s in srcs], 1)
+    y = F.conv2d(x, sd[name + ".weight"].to(dtype), stride=stride, padding=ks // 2)
+    g, b, rm, rv = _bn_params(sd, _bn_of(name), dtype)
+    v = lambda t: t[None, :, None, None]          # noqa: E731
+    if batch_norm is not None:
+        z = batch_norm(y, g, b, rm, rv)
+    else:
+        z = v(g) * (y - v(rm)) / torch.sqrt(v(rv) + EPS) + v(b)
+    if res >= 0:
+        z = z + nodes[res].to(dtype)
+    return z.clamp_min(0) if relu else z
+
+
+def eval_conv_mag(sd, rec, nodes):
+    """(M, split): M = |scale_c| conv(|x|, |w|) + |shift_c| + |res| in fp64 with the folded scale = gamma / sqrt(rv + eps),
+    shift = beta - rm scale; split = 2^-21 T_c |scale_c| per channel, the f16x2 operand-split term with T_c = sum over the
+    sources of max |x_s| sum |w_c,s| (test_hip_operand_scale)"""
+    name, srcs, res, relu, o, ks, stride = rec
+    D = torch.float64
+    w = sd[name + ".weight"].to(D).abs()
+    x = torch.cat([nodes[s].to(D).abs() for s in srcs], 1)
+    g, b, rm, rv = _bn_params(sd, _bn_of(name), D)
+    scale = g / torch.sqrt(rv + EPS)
+    shift = b - rm * scale
+    M = scale.abs()[None, :, None, None] * F.conv2d(x, w, stride=stride, padding=ks // 2) + shift.abs()[None, :, None, None]
+    if res >= 0:
+        M = M + nodes[res].to(D).abs()
+    tm, c0 = torch.zeros_like(g), 0
+    for s in srcs:
+        cs = nodes[s].shape[1]
+        tm += float(nodes[s].abs().max()) * w[:, c0:c0 + cs].sum((1, 2, 3))
+        c0 += cs
+    return M, 2.0 ** -21 * tm * scale.abs()
+
+
+def eval_deconv(sd, name, x, dtype, absolute=False):
+    """the depthwise ConvTranspose2d(k 4, s 2, p 1, groups C) of the neck"""
+    x, w = x.to(dtype), sd[name + ".weight"].to(dtype)
+    if absolute:
+        x, w = x.abs(), w.abs()
+    return F.conv_transpose2d(x, w, stride=2, padding=1, groups=x.shape[1])
+
+
+def head_hidden(sd, feat, dtype, absolute=False):
+    """the fused head conv: the nine 3x3 64 -> 64 convs side by side, bias added (576 channels, head-major)"""
+    w = torch.cat([sd["head.%s.0.weight" % h] for h in HEADS], 0).to(dtype)
+    b = torch.cat([sd["head.%s.0.bias" % h] for h in HEADS], 0).to(dtype)
+    x = feat.to(dtype)
+    if absolute:
+        x, w, b = x.abs(), w.abs(), b.abs()
+    return F.conv2d(x, w, b, padding=1)
+
+
+def attn_affine(sd, hidden, dtype, biased=False):
+    """AttnBN in eval mode as one affine per (image, head, channel), following the oracle's `_attn_bn`
+    (attentive_norm.py:79-91,154-164): y = g (x - rm) / sqrt(rv + 1e-3) + b = scale x + shift.
+    -> dict: scale, shift (B, 9, 64); unit_scale = sum_k |y_k| |weight_k,c| / sqrt(rv + 1e-3) and
+    unit_shift = sum_k |y_k| |bias_k,c| + |rm| unit_scale (what their rounding errors are relative to); s (B, 9, 64), the
+    statistic mean / sqrt(var + 1e-3) with the UNBIASED variance (biased=True: the defect of the negative control); ratio:
+    (mean - rm)^2 / (var + 1e-3), what the kernel's shifted one-pass sums cancel by"""
+    out = {k: [] for k in ("scale", "shift", "unit_scale", "unit_shift", "s", "ratio")}
+    B = hidden.shape[0]
+    for hd, head in enumerate(HEADS):
+        n = "head.%s.1" % head
+        x = hidden[:, 64 * hd:64 * hd + 64].to(dtype)
+        var, mean = torch.var_mean(x, dim=(2, 3), keepdim=True, unbiased=not biased)
+        s = mean * (var + ABN_EPS).rsqrt()
+        a = F.conv2d(s, sd[n + ".attn_weights.attention.0.weight"].to(dtype))
+        g, b, rm, rv = _bn_params(sd, n + ".attn_weights.attention.1", dtype)
+        a = F.batch_norm(a, rm, rv, g, b, False, 0.0, EPS)
+        y = (F.relu6(a + 3.0) / 6.0).view(B, -1)
+        wg, wb = sd[n + ".weight_"].to(dtype), sd[n + ".bias_"].to(dtype)
+        rm, rv = sd[n + ".running_mean"].to(dtype), sd[n + ".running_var"].to(dtype)
+        inv = (rv + ABN_EPS).rsqrt()
+        scale = (y @ wg) * inv
+        out["scale"].append(scale)
+        out["shift"].append(y @ wb - rm * scale)
+        us = (y.abs() @ wg.abs()) * inv
+        out["unit_scale"].append(us)
+        out["unit_shift"].append(y.abs() @ wb.abs() + rm.abs() * us)
+        out["s"].append(s.view(B, 64))
+        out["ratio"].append(((mean.view(B, 64) - rm) ** 2 / (var.view(B, 64) + ABN_EPS)))
+    return {k: torch.stack(v, 1) for k, v in out.items()}
+
+
+def head_outputs(sd, hidden, scale, shift, dtype):
+    """the second head pass from (hidden, AttnBN scale, shift): h = relu(scale x + shift), the 65 rows of the 1x1 convs, the
+    sigmoid-and-clamp epilogue of the two heat maps and the depth epilogue 1 / (sigmoid(v) + 1e-12) - 1 of depth row 0.
+    -> (raw, out) per prediction key; dtype float64 also -> mag: M_row = sum_c |w_c| |h_c| + |b|"""
+    raw, out, mag = {}, {}, {}
+    for hd, head in enumerate(HEADS):
+        x = hidden[:, 64 * hd:64 * hd + 64].to(dtype)
+        h = (x * scale[:, hd, :, None, None].to(dtype) + shift[:, hd, :, None, None].to(dtype)).clamp_min(0)
+        for key, conv in HEAD_OUT[head]:
+            w, b = sd[conv + ".weight"].to(dtype), sd[conv + ".bias"].to(dtype)
+            r = F.conv2d(h, w, b)
+            raw[key] = r
+            if dtype == torch.float64:
+                mag[key] = F.conv2d(h.abs(), w.abs(), b.abs())
+            if key in HEAT_KEYS:
+                r = torch.clamp(torch.sigmoid(r), 1e-4, 1.0 - 1e-4)
+            elif key == "depth_pred":
+                r = torch.cat([1.0 / (torch.sigmoid(r[:, 0:1]) + 1e-12) - 1.0, r[:, 1:2]], 1)
+            out[key] = r
+    return (raw, out, mag) if dtype == torch.float64 else (raw, out)
+
+
+class EvalReference:
+    """what `eval_reference` found.  layers: [(kind, label, node or None, Triple, split)] for the stem, every live conv, every
+    deconv and the head's hidden map (Triple: fp64 value, magnitude M, the float32 yard-stick; split: the per-channel f16x2
+    operand-split term, None where there is none); pools: [(in, out)]; attn / attn32: `attn_affine` of HIP's hidden in fp64 /
+    float32; raw, out, mag / raw32, out32: `head_outputs` of HIP's hidden and HIP's AttnBN affine in fp64 / float32"""
+
+    def __init__(self, graph):
+        self.graph, self.layers, self.pools = graph, [], []
+
+
+def eval_reference(sd, G, nodes, hidden, attn, yardstick=True, stem=True):
+    """The layer-local eval forward in float64 from the plan's own buffers.  nodes: {node id: float32 NCHW activation}, with
+    the image as node -1; hidden: the fused head conv's raw output (B, 576, h, w); attn: (B, 2, 9, 64), HIP's AttnBN scale
+    [:, 0] and shift [:, 1].
+
+        stem, live convs   conv of the HIP source nodes, unfolded eval BatchNorm, residual, ReLU
+        pools              listed only: the 2x2 max must be BIT-equal (`evaluate_eval`)
+        deconvs            the depthwise 4x4 stride-2 transposed conv of the HIP input node
+        head hidden        from node `feat`
+        AttnBN             scale and shift from HIP's hidden, following the oracle's `_attn_bn`
+        the ten maps       from HIP's hidden and HIP's scale and shift
+
+    Every conv-like quantity comes with its magnitude M, the same operation on absolute values, floored at 2^-10 of the
+    tensor maximum when it divides (Triple.floored).  yardstick: the same layer by torch in float32 from the same float32
+    buffers (F.conv2d, unfolded F.batch_norm).  stem=False with a graph without steps: the head alone, from nodes[G.feat]."""
+    R = EvalReference(G)
+    D, S = torch.float64, torch.float32
+    fbn = lambda y, g, b, rm, rv: F.batch_norm(y, rm, rv, g, b, False, 0.0, EPS)          # noqa: E731
+    for st in ([("conv", STEM_REC)] if stem else []) + list(G.steps):
+        if st[0] == "conv":
+            rec = st[1]
+            M, split = eval_conv_mag(sd, rec, nodes)
+            t = Triple(eval_conv(sd, rec, nodes, D), M, eval_conv(sd, rec, nodes, S, fbn) if yardstick else None)
+            R.layers.append((layer_kind(rec[5], rec[6]), rec[0], rec[4], t, split))
+        elif st[0] == "pool":
+            R.pools.append((st[1], st[2]))
+        else:
+            _, name, i, o = st
+            t = Triple(eval_deconv(sd, name, nodes[i], D), eval_deconv(sd, name, nodes[i], D, True),
+                       eval_deconv(sd, name, nodes[i], S) if yardstick else None)
+            R.layers.append(("deconv", name, o, t, None))
+    feat = nodes[G.feat]
+    R.layers.append(("head hidden", "head.*.0", None, Triple(head_hidden(sd, feat, D), head_hidden(sd, feat, D, True),
+                                                               head_hidden(sd, feat, S) if yardstick else None), None))
+    R.attn = attn_affine(sd, hidden, D)
+    R.attn32 = attn_affine(sd, hidden, S) if yardstick else None
+    R.raw, R.out, R.mag = head_outputs(sd, hidden, attn[:, 0], attn[:, 1], D)
+    if yardstick:
+        R.raw32, R.out32 = head_outputs(sd, hidden, attn[:, 0], attn[:, 1], S)
+    return R
+
+
+class EvalFigures:
+    """what `evaluate_eval` measured.  yard / gate / worst: per class; bad: per class, the lines of what missed its gate (empty:
+    passed); rows: per class [(label, HIP error, float32 error, worst error / gate)]; excepted: per heat map, the share of
+    positions within 8 U M_row of a clamp; split_needed: the conv layers that pass only with the operand-split term"""
+
+    def __init__(self):
+        self.yard, self.gate, self.worst, self.bad, self.rows, self.excepted = {}, {}, {}, {}, {}, {}
+        self.split_needed = []
+
+    def ratio(self, cls):
+        """worst HIP error / float32 yard-stick of a class"""
+        return self.worst[cls] / max(self.yard[cls], 1e-300)
+
+
+def evaluate_eval(R, nodes, hidden, attn, maps, split_kinds=()):
+    """The gates of test_hip_eval_layers.py (U = 2^-24), also run by the CPU test on float32 stand-ins for the kernels.
+
+      conv kinds, deconv, head hidden: elementwise |got - ref| / M against 5 x (the float32 yard-stick's worst of the kind)
+        + 4 U; for the kinds in `split_kinds` the f16x2 operand-split term 2^-21 T_c |scale_c| / M is added
+      pools: bit-equal to max_pool2d of the input node
+      AttnBN scale, shift: |got - ref| / unit against 5 x the float32 `attn_affine` + 4 U
+      linear rows: |got - ref| / M_row against 5 x float32 + 4 U
+      heat maps: the positions at the floor and at the ceiling are the reference's (its output rounded to float32 -- a float32
+        map cannot show a value between the ceiling and its neighbour below), except where the fp64 raw logit lies within
+        8 U M_row of +-ln 9999, at most 0.1 % of a map; every value: |got - ref| / (M_row / 4) against 5 x float32 + 4 U
+      depth row 0: |got - ref| / ((1 + |d0|) (1 + M_row)) against 5 x float32 + 4 U"""
+    Fg = EvalFigures()
+    G = R.graph
+
+    def gated(cls, items):
+        """items: [(label, got, ref, float32, divisor, extra allowance in units of the divisor or None)]"""
+        errs = [(label, (got.double() - ref).abs() / div, float(((f32.double() - ref).abs() / div).max()), extra)
+                for label, got, ref, f32, div, extra in items]
+        Fg.yard[cls] = max(e[2] for e in errs)
+        Fg.gate[cls] = 5 * Fg.yard[cls] + 4 * U24
+        Fg.worst[cls] = max(float(e[1].max()) for e in errs)
+        Fg.rows[cls], Fg.bad[cls] = [], []
+        for label, e, f, extra in errs:
+            plain = float(e.max()) / Fg.gate[cls]
+            r = plain if extra is None else float((e / (Fg.gate[cls] + extra)).max())
+            if extra is not None and plain > 1.0 >= r:
+                Fg.split_needed.append(label)
+            Fg.rows[cls].append((label, float(e.max()), f, r))
+            if not r <= 1.0:
+                Fg.bad[cls].append("%s %s: %.3g of the gate (error %.3g, float32 %.3g)" % (cls, label, r, float(e.max()), f))
+
+    for kind in EVAL_KINDS:
+        items = []
+        for k, label, o, t, split in R.layers:
+            if k != kind:
+                continue
+            got = hidden if o is None else nodes[o]
+            assert got.shape == t.ref.shape, (label, got.shape, t.ref.shape)
+            extra = split[None, :, None, None] / t.floored() if (kind in split_kinds and split is not None) else None
+            items.append((label, got, t.ref, t.f32, t.floored(), extra))
+        if items:
+            gated(kind, items)
+    Fg.bad["pools"] = ["pool node %d of node %d is not bit-equal" % (o, i) for i, o in R.pools
+                       if not torch.equal(F.max_pool2d(nodes[i], 2), nodes[o])]
+    a, a32 = R.attn, R.attn32
+    gated("AttnBN", [("scale", attn[:, 0], a["scale"], a32["scale"], a["unit_scale"].clamp_min(1e-300), None),
+                     ("shift", attn[:, 1], a["shift"], a32["shift"], a["unit_shift"].clamp_min(1e-300), None)])
+    lin = []
+    for key in R.out:
+        if key in HEAT_KEYS:
+            continue
+        sl = slice(1, 2) if key == "depth_pred" else slice(None)
+        lin.append((key, maps[key][:, sl], R.out[key][:, sl], R.out32[key][:, sl], _floored(R.mag[key][:, sl]), None))
+    gated("linear rows", lin)
+    gated("heat maps", [(key, maps[key], R.out[key], R.out32[key], _floored(R.mag[key]) / 4, None) for key in HEAT_KEYS])
+    lo, hi = heat_clamps()
+    for key in HEAT_KEYS:
+        got, ref32 = maps[key], R.out[key].float()
+        near = ((R.raw[key].abs() - LOGIT_CLAMP).abs() <= 8 * U24 * R.mag[key])
+        Fg.excepted[key] = float(near.double().mean())
+        if Fg.excepted[key] > 1e-3:
+            Fg.bad["heat maps"].append("%s: %.3g of the map within 8 U M_row of a clamp" % (key, Fg.excepted[key]))
+        if float(got.min()) < float(lo) or float(got.max()) > float(hi):
+            Fg.bad["heat maps"].append("%s: values outside [1e-4, 1 - 1e-4]" % key)
+        for what, edge in (("floor", lo), ("ceiling", hi)):
+            wrong = ((got == edge) != (ref32 == edge)) & ~near
+            if bool(wrong.any()):
+                Fg.bad["heat maps"].append("%s: %d positions differ from the reference's set at the %s" % (key, int(wrong.sum()), what))
+    d0, m0 = R.out["depth_pred"][:, 0:1], R.mag["depth_pred"][:, 0:1]
+    gated("depth row 0", [("depth_pred[0]", maps["depth_pred"][:, 0:1], d0, R.out32["depth_pred"][:, 0:1],
+                           (1 + d0.abs()) * (1 + m0), None)])
+    return Fg
+
+
+def head_output_stress(sd, heat_gain=12.0, depth_gain=3.0):
+    """the state with the 1x1 weights of the two heat-map heads scaled by `heat_gain` (the raw logits reach both clamps and the
+    interior between them) and row 0 of depth_head.3, weight and bias, by `depth_gain` (the depth logit spans about +-15: d0
+    from 1e-7 to 1e5)"""
+    out = {k: v.clone() for k, v in sd.items()}
+    for h in ("heatmap_head", "kpt_heatmap_head"):
+        out["head.%s.3.weight" % h] = (sd["head.%s.3.weight" % h].double() * heat_gain).float()
+    for k in ("weight", "bias"):
+        t = out["head.depth_head.3." + k]
+        t[0] = (t[0].double() * depth_gain).float()
+    return out
+
+
+# ---- reading the eval plan
+def read_infer(eng, node, which=0):
+    """mc_infer_debug_node on the engine's last eval plan: NCHW float32 on the host"""
+    import ctypes as C
+    dims = (C.c_int * 4)()
+    rc = eng.lib.mc_infer_debug_node(eng.h, int(node), int(which), None, dims, None)
+    assert rc == 0, eng.lib.mc_last_error(eng.h)
+    out = torch.empty(tuple(dims), dtype=torch.float32, device="cuda")
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    rc = eng.lib.mc_infer_debug_node(eng.h, int(node), int(which), C.c_void_p(out.data_ptr()), dims, st)
+    assert rc == 0, eng.lib.mc_last_error(eng.h)
+    torch.cuda.synchronize()
+    return out.cpu()
