@@ -65,8 +65,18 @@ hipError_t launch_pack_conv_w_dgrad(const float *w, int Cout, int CinTotal, int 
 // draw are wave-uniform and come down the scalar path.  Replaces a dense 576->65 wgrad, a dense 65->576
 // dgrad (8/9 of both multiplying structural zeros) and a three-tensor reduction pass.
 // (reference model/dense_heads/monocon_heads.py:119-120 under autograd)
+//
+// The tile map.  Only the two heat-map heads receive a dense raw gradient (focal loss); the losses of the other seven are
+// gathered at the objects' centres and key points, so all but a few dozen pixels of their rows of draw are exact zeros.
+// dpred_pack_kernel, which stages every aligned 64-pixel tile of draw anyway, leaves one word per tile in nz[B][ceil(HW/64)]:
+// bit h is set when any row of head h is != 0.f anywhere in the tile.  A staged block of head_bwd_kernel overlaps one or two
+// of those tiles; when this head's bit is clear in all of them the block contributes exact zeros to dW1, sum d and sum d*x,
+// and the workgroup branches around it without touching x (MODE 0 stores d = 0, MODE 2 writes dx = Q*x + R without
+// staging draw).  Every other block is summed as before, in the same order: the results differ from nz == nullptr at most
+// in the sign of a zero.  nz == nullptr (MONOCON_HIP_HEAD_ZSKIP=0): every block is visited.
 struct HeadBwdArgs {
     const float *draw; int ld;
+    const unsigned *nz; int nz_tiles;   // the tile map (or null) and its row length ceil(HW / 64)
     const float *z, *x, *w1;          // z may be null: recomputed as relu(scale_bc * x + shift_bc), bit-identical to head_apply
     const float *scale, *shift;       // [B][CP] AttnBN coefficients of the forward (used when z is null)
     float *d, *dw_partial, *red_partial;
@@ -83,6 +93,19 @@ struct HeadBwdArgs {
 // pixels in LDS with coalesced 16-byte loads (fetched one block ahead into registers) and every wave reads its rows as
 // LDS broadcasts.
 constexpr int HB_PX = 64, HB_LD = 80;
+// The kernels below hard-code the HeadRow table -- (first row, row count) of each head:
+//   0:(0,3) 1:(3,2) 2:(5,2) 3:(7,18) 4:(25,9) 5:(34,2) 6:(36,3) 7:(39,2) 8:(41,24)
+// -- and their launchers refuse to run when head_row_begin() says otherwise.
+static bool head_rows_as_coded() {
+    const int *rbeg = head_row_begin();
+    static const int RB[NUM_HEADS + 1] = {0, 3, 5, 7, 25, 34, 36, 39, 41, 65};
+    for (int i = 0; i <= NUM_HEADS; ++i)
+        if (rbeg[i] != RB[i]) return false;
+    return true;
+}
+__device__ __forceinline__ int head_of_row(int r) {
+    return (r >= 3) + (r >= 5) + (r >= 7) + (r >= 25) + (r >= 34) + (r >= 36) + (r >= 39) + (r >= 41);
+}
 // Work per pixel is proportional to a head's row count (2 ... 24): with one wave per head in a nine-wave workgroup the two
 // widest heads set the pace of all nine (round 5, rows cut to two per head: 1.17 -> 0.50 ms).  The head is a GRID dimension
 // now: a workgroup = (pixel block, head), four waves that take the pixels i % 4 == wave of every staged block and fold their
@@ -167,6 +190,38 @@ struct HeadPart {
             one(gsh, i, gp, rez ? fmaxf(fmaf(xv1, zsc, zsh), 0.f) : zp[gp * CP], xv1);
         }
     }
+    // this part's pixels of a block [px0, px0 + n) whose raw-gradient rows are all zero (the tile map): d = 0 there, which adds
+    // nothing to acc, s1 or s2 in MODE 0 / 1.  MODE 0 stores that d; MODE 2 leaves dx = Q*x + R -- block()'s value for d = 0 --
+    // with the same s1 / s2 bookkeeping over the same pixels in the same order
+    __device__ __forceinline__ void zero_block(int px0, int n) {
+        if (MODE == 1) return;
+        const int cnt = n > sub ? (n - sub + nsub - 1) / nsub : 0;
+        if (MODE == 0) {
+            for (int k = 0; k < cnt; ++k) dp[(size_t)(px0 + sub + k * nsub) * CP] = 0.f;
+            return;
+        }
+        constexpr int U = 8;
+        int k = 0;
+        for (; k + U <= cnt; k += U) {
+            float xv[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) xv[u] = xp[(size_t)(px0 + sub + (k + u) * nsub) * CP];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const float o = fmaf(cq, xv[u], cr);
+                s1 += o;
+                s2 = fmaxf(s2, fabsf(o));
+                dp[(size_t)(px0 + sub + (k + u) * nsub) * CP] = o;
+            }
+        }
+        for (; k < cnt; ++k) {
+            const size_t gp = (size_t)(px0 + sub + k * nsub);
+            const float o = fmaf(cq, xp[gp * CP], cr);
+            s1 += o;
+            s2 = fmaxf(s2, fabsf(o));
+            dp[gp * CP] = o;
+        }
+    }
     // parts 1 .. n-1 of a shared head park their sums in LDS ...
     __device__ __forceinline__ void spill(float *red, int lane) const {
         if (nsub == 1 || sub == 0) return;
@@ -207,9 +262,19 @@ struct HeadPart {
 // block ahead into registers), every wave reads them as LDS broadcasts.
 template <int RB, int NR, int MODE>
 __device__ __forceinline__ void head_bwd_one(const HeadBwdArgs &a, float *gsh, float *red, int h, int wv, int lane, size_t p0, int np,
-                                             int blk, int b) {
+                                             int blk, int b, int r0) {
     HeadPart<RB, NR, MODE> P;
     P.init(a, h, lane, p0, b, wv, HB_WAVES);
+    // does block [px0, px0 + HB_PX) of this workgroup carry a non-zero raw gradient of head h?  It overlaps the aligned tiles
+    // of its first and of its last pixel (the same one when rows_per_block is a multiple of 64).  Workgroup-uniform: the
+    // whole block is branched around, barriers included.
+    const unsigned *nzb = a.nz ? a.nz + (size_t)b * a.nz_tiles : nullptr;
+    auto live = [&](int px0) -> bool {
+        if (!nzb) return true;
+        const int first = r0 + px0, last = r0 + min(px0 + HB_PX, np) - 1;
+        const unsigned m = nzb[first >> 6] | nzb[last >> 6];
+        return (__builtin_amdgcn_readfirstlane(m) >> h) & 1u;
+    };
     constexpr int NE = HB_PX * NR, NL = (NE + HB_NT - 1) / HB_NT;      // staged floats per block, loads per thread
     const int tid = threadIdx.x;
     const float *gsrc = a.draw + p0 * a.ld + RB;
@@ -221,17 +286,25 @@ __device__ __forceinline__ void head_bwd_one(const HeadBwdArgs &a, float *gsh, f
             pre[k] = (e < NE && px0 + px < np) ? gsrc[(size_t)(px0 + px) * a.ld + r] : 0.f;
         }
     };
-    fetch(0);
+    bool cur = np > 0 && live(0);
+    if (cur) fetch(0);
     for (int px0 = 0; px0 < np; px0 += HB_PX) {
-        __syncthreads();                              // the previous block's rows are no longer read
+        const bool nxt = px0 + HB_PX < np && live(px0 + HB_PX);
+        if (cur) {
+            __syncthreads();                          // the previous block's rows are no longer read
 #pragma unroll
-        for (int k = 0; k < NL; ++k) {
-            const int e = tid + k * HB_NT;
-            if (e < NE) gsh[e] = pre[k];
+            for (int k = 0; k < NL; ++k) {
+                const int e = tid + k * HB_NT;
+                if (e < NE) gsh[e] = pre[k];
+            }
+            __syncthreads();
+            if (nxt) fetch(px0 + HB_PX);              // next block's rows travel while this one is processed
+            P.block(gsh, px0, min(HB_PX, np - px0));
+        } else {
+            if (nxt) fetch(px0 + HB_PX);
+            P.zero_block(px0, min(HB_PX, np - px0));
         }
-        __syncthreads();
-        if (px0 + HB_PX < np) fetch(px0 + HB_PX);     // next block's rows travel while this one is processed
-        P.block(gsh, px0, min(HB_PX, np - px0));
+        cur = nxt;
     }
     P.spill(red, lane);
     __syncthreads();
@@ -250,21 +323,21 @@ __global__ __launch_bounds__(HB_NT) void head_bwd_kernel(const HeadBwdArgs a) {
     const int r0 = rb * a.rows_per_block;
     const int np = min(a.HW, r0 + a.rows_per_block) - r0;
     const size_t p0 = (size_t)b * a.HW + r0;
-    // (first row, row count) of each head in HeadRow order: 0:(0,3) 1:(3,2) 2:(5,2) 3:(7,18) 4:(25,9) 5:(34,2) 6:(36,3) 7:(39,2) 8:(41,24)
+    // (first row, row count) of each head in HeadRow order: see head_rows_as_coded()
     if (WIDE) {
         switch (blockIdx.y) {
-            case 0: head_bwd_one<41, 24, MODE>(a, gsh, red, 8, wv, lane, p0, np, blk, b); break;
-            case 1: head_bwd_one<7, 18, MODE>(a, gsh, red, 3, wv, lane, p0, np, blk, b); break;
-            default: head_bwd_one<25, 9, MODE>(a, gsh, red, 4, wv, lane, p0, np, blk, b); break;
+            case 0: head_bwd_one<41, 24, MODE>(a, gsh, red, 8, wv, lane, p0, np, blk, b, r0); break;
+            case 1: head_bwd_one<7, 18, MODE>(a, gsh, red, 3, wv, lane, p0, np, blk, b, r0); break;
+            default: head_bwd_one<25, 9, MODE>(a, gsh, red, 4, wv, lane, p0, np, blk, b, r0); break;
         }
     } else {
         switch (blockIdx.y) {
-            case 0: head_bwd_one<0, 3, MODE>(a, gsh, red, 0, wv, lane, p0, np, blk, b); break;
-            case 1: head_bwd_one<3, 2, MODE>(a, gsh, red, 1, wv, lane, p0, np, blk, b); break;
-            case 2: head_bwd_one<5, 2, MODE>(a, gsh, red, 2, wv, lane, p0, np, blk, b); break;
-            case 3: head_bwd_one<34, 2, MODE>(a, gsh, red, 5, wv, lane, p0, np, blk, b); break;
-            case 4: head_bwd_one<36, 3, MODE>(a, gsh, red, 6, wv, lane, p0, np, blk, b); break;
-            default: head_bwd_one<39, 2, MODE>(a, gsh, red, 7, wv, lane, p0, np, blk, b); break;
+            case 0: head_bwd_one<0, 3, MODE>(a, gsh, red, 0, wv, lane, p0, np, blk, b, r0); break;
+            case 1: head_bwd_one<3, 2, MODE>(a, gsh, red, 1, wv, lane, p0, np, blk, b, r0); break;
+            case 2: head_bwd_one<5, 2, MODE>(a, gsh, red, 2, wv, lane, p0, np, blk, b, r0); break;
+            case 3: head_bwd_one<34, 2, MODE>(a, gsh, red, 5, wv, lane, p0, np, blk, b, r0); break;
+            case 4: head_bwd_one<36, 3, MODE>(a, gsh, red, 6, wv, lane, p0, np, blk, b, r0); break;
+            default: head_bwd_one<39, 2, MODE>(a, gsh, red, 7, wv, lane, p0, np, blk, b, r0); break;
         }
     }
 }
@@ -275,25 +348,23 @@ static void head_bwd_launch(const HeadBwdArgs &a, int blocks, hipStream_t st) {
 }
 // blocks = chan_reduce_blocks(B, HW); rows_per_block = that partition's row count (kernels_train.hip)
 static hipError_t head_bwd_args(HeadBwdArgs &a, const float *draw, int ld, const float *z, const float *x, const float *w1, int B,
-                                int HW, int blocks, const float *scale, const float *shift) {
-    const int *rbeg = head_row_begin();
-    static const int RB[NUM_HEADS + 1] = {0, 3, 5, 7, 25, 34, 36, 39, 41, 65};
-    for (int i = 0; i <= NUM_HEADS; ++i)
-        if (rbeg[i] != RB[i]) return hipErrorInvalidValue;      // the switch above hard-codes the HeadRow table
+                                int HW, int blocks, const float *scale, const float *shift, const unsigned *nz) {
+    if (!head_rows_as_coded()) return hipErrorInvalidValue;     // the switch above hard-codes the HeadRow table
     if (blocks % B || ld != HB_LD) return hipErrorInvalidValue;
     if (!z && (!scale || !shift)) return hipErrorInvalidValue;
     a = HeadBwdArgs{};
     a.draw = draw; a.ld = ld; a.z = z; a.x = x; a.w1 = w1;
     a.scale = scale; a.shift = shift;
+    a.nz = nz; a.nz_tiles = (HW + 63) / 64;
     a.HW = HW; a.blocks_per_img = blocks / B; a.rows_per_block = (HW + a.blocks_per_img - 1) / a.blocks_per_img;
     return hipSuccess;
 }
-// d == nullptr: the masked gradient is not stored (launch_head_dx forms it again)
+// d == nullptr: the masked gradient is not stored (launch_head_dx forms it again); nz: launch_dpred_pack's tile map of draw, or null
 hipError_t launch_head_bwd(const float *draw, int ld, const float *z, const float *x, const float *w1, int B, int HW,
                            int blocks, float *d, float *dw_partial, float *red_partial, hipStream_t st, const float *scale,
-                           const float *shift) {
+                           const float *shift, const unsigned *nz) {
     HeadBwdArgs a;
-    hipError_t e = head_bwd_args(a, draw, ld, z, x, w1, B, HW, blocks, scale, shift);
+    hipError_t e = head_bwd_args(a, draw, ld, z, x, w1, B, HW, blocks, scale, shift, nz);
     if (e != hipSuccess) return e;
     a.d = d; a.dw_partial = dw_partial; a.red_partial = red_partial;
     if (d) head_bwd_launch<0>(a, blocks, st);
@@ -305,10 +376,10 @@ hipError_t launch_head_bwd(const float *draw, int ld, const float *z, const floa
 // workspace; csum_out [CP]: column sums of dx (bias gradients of the fused 3x3 convs); amax: slot of max |dx| (or null).
 hipError_t launch_head_dx(const float *draw, int ld, const float *x, const float *w1, const float *coef, int B, int HW, int blocks,
                           float *dx, float *csum, float *csum_out, unsigned *amax, hipStream_t st, const float *scale,
-                          const float *shift) {
+                          const float *shift, const unsigned *nz) {
     if (!coef || !dx || !csum || !csum_out) return hipErrorInvalidValue;
     HeadBwdArgs a;
-    hipError_t e = head_bwd_args(a, draw, ld, nullptr, x, w1, B, HW, blocks, scale, shift);
+    hipError_t e = head_bwd_args(a, draw, ld, nullptr, x, w1, B, HW, blocks, scale, shift, nz);
     if (e != hipSuccess) return e;
     a.d = dx; a.coef = coef; a.csum = csum; a.amax = amax;
     head_bwd_launch<2>(a, blocks, st);
@@ -321,6 +392,7 @@ struct DpredPackArgs {
     const float *dpred[10];
     int ld, B, HW;
     float *out;
+    unsigned *nz;      // [B][ceil(HW / 64)]: bit h = head h has a non-zero value in the tile (HeadBwdArgs), or null
     int row_pred[NUM_OUT_ROWS], row_ch[NUM_OUT_ROWS], pred_c[10];
 };
 // USER variant: a caller's gradients with respect to the prediction maps themselves join the loss gradients on the way in
@@ -348,6 +420,8 @@ __global__ __launch_bounds__(256) void dpred_pack_kernel(const std::conditional_
                                                      // (they live in scratch memory then: 267 us for 570 MB in round 5)
     __shared__ const float *rowg[USER ? NUM_OUT_ROWS : 1], *rowy[USER ? NUM_OUT_ROWS : 1];
     __shared__ int rowe[USER ? NUM_OUT_ROWS : 1];
+    __shared__ unsigned nzw;
+    if (threadIdx.x == 0) nzw = 0u;
     const int tiles = (a.HW + 63) / 64;
     const int b = blockIdx.x / tiles, hw0 = (blockIdx.x % tiles) * 64;
     if (threadIdx.x < NUM_OUT_ROWS) {
@@ -361,42 +435,48 @@ __global__ __launch_bounds__(256) void dpred_pack_kernel(const std::conditional_
         }
     }
     __syncthreads();
+    unsigned nzm = 0u;      // heads with a non-zero value among this wave's rows (a wave takes one row per turn: r is wave-uniform)
     for (int e = threadIdx.x; e < 64 * NUM_OUT_ROWS; e += 256) {
         const int r = e / 64, px = e % 64;
+        float v = 0.f;
         if constexpr (USER) {
             // one row per wave: the test on rowg[r] is wave-uniform, the three reads are coalesced along HW
-            float v = 0.f;
             if (hw0 + px < a.HW) {
                 v = rowp[r][px];
                 if (rowg[r]) v += pred_act_grad(rowe[r], rowy[r][px]) * rowg[r][px];
             }
-            t[px][r] = v;
         } else {
-            t[px][r] = (hw0 + px < a.HW) ? rowp[r][px] : 0.f;
+            if (hw0 + px < a.HW) v = rowp[r][px];
         }
+        t[px][r] = v;
+        if (__any(v != 0.f)) nzm |= 1u << head_of_row(r);
     }
+    if (a.nz && (threadIdx.x & 63) == 0 && nzm) atomicOr(&nzw, nzm);      // (an OR: the order of the four waves does not matter)
     __syncthreads();
+    if (a.nz && threadIdx.x == 0) a.nz[blockIdx.x] = nzw;
     for (int e = threadIdx.x; e < 64 * a.ld; e += 256) {
         const int px = e / a.ld, r = e % a.ld;
         if (hw0 + px < a.HW) a.out[((size_t)b * a.HW + hw0 + px) * a.ld + r] = r < NUM_OUT_ROWS ? t[px][r] : 0.f;
     }
 }
-static void dpred_pack_args(DpredPackArgs &a, const float *const dpred[10], int ld, int B, int HW, float *out) {
-    a.ld = ld; a.B = B; a.HW = HW; a.out = out;
+static void dpred_pack_args(DpredPackArgs &a, const float *const dpred[10], int ld, int B, int HW, float *out, unsigned *nz) {
+    a.ld = ld; a.B = B; a.HW = HW; a.out = out; a.nz = nz;
     const HeadRow *rows = head_rows();
     for (int i = 0; i < 10; ++i) { a.dpred[i] = dpred[i]; a.pred_c[i] = PRED_CH[i]; }
     for (int r = 0; r < NUM_OUT_ROWS; ++r) { a.row_pred[r] = rows[r].pred; a.row_ch[r] = rows[r].ch; }
 }
-hipError_t launch_dpred_pack(const float *const dpred[10], int ld, int B, int HW, float *out, hipStream_t st) {
+hipError_t launch_dpred_pack(const float *const dpred[10], int ld, int B, int HW, float *out, hipStream_t st, unsigned *nz) {
+    if (nz && !head_rows_as_coded()) return hipErrorInvalidValue;
     DpredPackArgs a;
-    dpred_pack_args(a, dpred, ld, B, HW, out);
+    dpred_pack_args(a, dpred, ld, B, HW, out, nz);
     hipLaunchKernelGGL(dpred_pack_kernel<false>, dim3(B * ((HW + 63) / 64)), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 hipError_t launch_dpred_pack_user(const float *const dpred[10], const float *const pred[10], const float *const grad[10], int ld,
-                                  int B, int HW, float *out, hipStream_t st) {
+                                  int B, int HW, float *out, hipStream_t st, unsigned *nz) {
+    if (nz && !head_rows_as_coded()) return hipErrorInvalidValue;
     DpredUserArgs a;
-    dpred_pack_args(a, dpred, ld, B, HW, out);
+    dpred_pack_args(a, dpred, ld, B, HW, out, nz);
     const HeadRow *rows = head_rows();
     for (int i = 0; i < 10; ++i) {
         if (!pred[i]) return hipErrorInvalidValue;

@@ -31,6 +31,7 @@ struct PlanSwitches {
     long long grad_pool;        // gradient maps from a recycling pool (TB::g_acquire)
     long long grad_pool_cool;   // head start of a returned buffer, in younger buffers of its size
     long long head_dx_fuse;     // the heads' masked gradient is never stored
+    long long head_zskip;       // 0 / 1 / 2: the heads' backward skips tiles whose raw gradient is all zero (2: not in head_dx)
     long long dgrad_s2_thin;    // level1's stride-2 data gradient in one pass
     long long stem_fuse;        // the stem's weight gradient forms dY on the fly
     long long bm_epilogue;      // 0 / 1 / <pixels per image>: BatchNorm-backward reductions in the data gradient's epilogue
@@ -47,6 +48,7 @@ const struct { const char *name; long long PlanSwitches::*field; long long def; 
     {"MONOCON_HIP_GRAD_POOL", &PlanSwitches::grad_pool, 1},
     {"MONOCON_HIP_GRAD_POOL_COOL", &PlanSwitches::grad_pool_cool, 2},
     {"MONOCON_HIP_HEAD_DX_FUSE", &PlanSwitches::head_dx_fuse, 1},
+    {"MONOCON_HIP_HEAD_ZSKIP", &PlanSwitches::head_zskip, 1},
     {"MONOCON_HIP_DGRAD_S2_THIN", &PlanSwitches::dgrad_s2_thin, 1},
     {"MONOCON_HIP_STEM_FUSE", &PlanSwitches::stem_fuse, 1},
     {"MONOCON_HIP_BM_EPILOGUE", &PlanSwitches::bm_epilogue, 1},
@@ -869,6 +871,17 @@ struct TB {   // train plan builder
     // ---- losses -> raw gradients -> heads -> the gradient of feat
     void heads_backward(int feat) {
         float *draw = alloc(raw_numel);
+        // MONOCON_HIP_HEAD_ZSKIP (default 1): seven of the nine heads take their loss gradient at the objects' centres and key
+        // points only, so their rows of draw are zero in all but a few dozen pixels.  The pack leaves one word per aligned
+        // 64-pixel tile (bit h: head h has a non-zero row there), and the two passes below branch around a head's all-zero
+        // tiles -- the statistics pass does not read x there at all.  Results are those of 0 up to the sign of a zero
+        // (DESIGN.md 3f.1).  2: the statistics pass only.  0: no map, every tile is visited.
+        const size_t nz_words = (size_t)B * ((HW + 63) / 64);
+        unsigned *nz = sw.head_zskip ? reinterpret_cast<unsigned *>(alloc(nz_words)) : nullptr;
+        const unsigned *nz_bwd = nz, *nz_dx = sw.head_zskip == 1 ? nz : nullptr;
+        if (sw.plan_debug)
+            fprintf(stderr, "[plan] heads backward: zero-tile skip %s (%zu tile words)\n",
+                    !sw.head_zskip ? "off" : sw.head_zskip == 1 ? "on" : "on in the statistics pass only", sw.head_zskip ? nz_words : (size_t)0);
         float *cs1 = alloc(colsum_partial_floats((size_t)B * HW, LD));
         float *db1 = alloc(NUM_OUT_ROWS), *dw1 = alloc((size_t)NUM_OUT_ROWS * HEAD_CH);
         push_bwd([=, ts = ts, B = B, fh = fh, fw = fw, HW = HW](mc_handle *hh, hipStream_t st) {
@@ -877,9 +890,9 @@ struct TB {   // train plan builder
             bool user = false;
             for (const float *g : ts->grad_preds) user = user || g != nullptr;
             if (user)
-                HIPCHK(hh, launch_dpred_pack_user(ts->dpred, ts->preds, ts->grad_preds, LD, B, HW, draw, st));
+                HIPCHK(hh, launch_dpred_pack_user(ts->dpred, ts->preds, ts->grad_preds, LD, B, HW, draw, st, nz));
             else
-                HIPCHK(hh, launch_dpred_pack(ts->dpred, LD, B, HW, draw, st));
+                HIPCHK(hh, launch_dpred_pack(ts->dpred, LD, B, HW, draw, st, nz));
             HIPCHK(hh, launch_colsum(draw, (size_t)B * HW, NUM_OUT_ROWS, LD, cs1, db1, st));
             return 0;
         });
@@ -907,7 +920,7 @@ struct TB {   // train plan builder
         seg("head.dir_reg.0", rb[8] + 12, 12);
         const float *xp = xh.p, *w1 = h->head_w1, *zsc = at.scale, *zsh = at.shift;
         push_bwd([=, B = B, HW = HW](mc_handle *hh, hipStream_t st) {
-            HIPCHK(hh, launch_head_bwd(draw, LD, nullptr, xp, w1, B, HW, nbr, dx_fuse ? nullptr : dh, dw1p, partial, st, zsc, zsh));
+            HIPCHK(hh, launch_head_bwd(draw, LD, nullptr, xp, w1, B, HW, nbr, dx_fuse ? nullptr : dh, dw1p, partial, st, zsc, zsh, nz_bwd));
             HIPCHK(hh, launch_splitk_reduce(dw1p, nbr, 1, NUM_OUT_ROWS, HEAD_CH, dw1, st));
             HIPCHK(hh, launch_copy_batch(segcb, st));
             return 0;
@@ -921,7 +934,7 @@ struct TB {   // train plan builder
             // leaves the column sums of dx (the 3x3 convs' bias gradients) instead of a second read of dx
             HIPCHK(hh, launch_attn_train_bwd(at, partial, rb_per_img, gp, coef, st));
             if (dx_fuse)
-                HIPCHK(hh, launch_head_dx(draw, LD, xp, w1, coef, B, HW, nbr, dx, cs3, db3, dxmax, st, zsc, zsh));
+                HIPCHK(hh, launch_head_dx(draw, LD, xp, w1, coef, B, HW, nbr, dx, cs3, db3, dxmax, st, zsc, zsh, nz_dx));
             else
                 HIPCHK(hh, launch_affine_bwd(dh, nullptr, xp, coef, B, (size_t)HW, CP, 1, 0, dx, nullptr, 0, st, nullptr, nullptr, cs3, db3,
                                              dxmax));

@@ -144,11 +144,14 @@ hipError_t launch_deconv4_bwd_w(const float *in, const float *dout, int B, int H
 // ---- head / stem train kernels (kernels_head_train.hip)
 hipError_t launch_pack_conv_w_dgrad(const float *w, int Cout, int CinTotal, int k, int c_off, int Cs, int CsP, int CoutPad,
                                     int cls, float *dst, hipStream_t st);
-hipError_t launch_dpred_pack(const float *const dpred[10], int ld, int B, int HW, float *out, hipStream_t st);
+// nz (both variants; may be null): [B][ceil(HW / 64)] words, bit h set when any row of head h is != 0.f in that aligned
+// 64-pixel tile of `out` -- the map launch_head_bwd / launch_head_dx skip all-zero tiles by
+hipError_t launch_dpred_pack(const float *const dpred[10], int ld, int B, int HW, float *out, hipStream_t st,
+                             unsigned *nz = nullptr);
 // the same pack with a caller's gradients wrt the prediction maps added in (grad[k] NCHW like pred[k], nullptr: none): row r
 // of map k gets dpred + (d map / d raw output, from pred[k]) * grad, in the same single pass
 hipError_t launch_dpred_pack_user(const float *const dpred[10], const float *const pred[10], const float *const grad[10], int ld,
-                                  int B, int HW, float *out, hipStream_t st);
+                                  int B, int HW, float *out, hipStream_t st, unsigned *nz = nullptr);
 struct AttnTrainArgs {
     const float *stats;            // [B][chunks][stat_ld][2] partial (sum, sumsq) of (x - running_mean)
     int chunks, stat_ld, B, HW;
@@ -173,10 +176,10 @@ hipError_t launch_attn_train_bwd(const AttnTrainArgs &a, const float *partial, i
                                  float *coef, hipStream_t st);
 hipError_t launch_head_bwd(const float *draw, int ld, const float *z, const float *x, const float *w1, int B, int HW,
                            int blocks, float *d, float *dw_partial, float *red_partial, hipStream_t st,
-                           const float *scale = nullptr, const float *shift = nullptr);
+                           const float *scale = nullptr, const float *shift = nullptr, const unsigned *nz = nullptr);
 hipError_t launch_head_dx(const float *draw, int ld, const float *x, const float *w1, const float *coef, int B, int HW, int blocks,
                           float *dx, float *csum, float *csum_out, unsigned *amax, hipStream_t st, const float *scale,
-                          const float *shift);
+                          const float *shift, const unsigned *nz = nullptr);
 hipError_t launch_splitk_reduce(const float *partial, int ksplit, int T, int Cout, int Cin, float *dw, hipStream_t st);
 int stem_wgrad_blocks(int B, int H, int W);
 // img_amax / dy_amax (mode 3): max-|x| slots of the image and of dY -> the fp16-pipe kernel (stem_f16.hip)
