@@ -99,12 +99,8 @@ __global__ __launch_bounds__(64 * WM * WN, SPL == 1 ? 3 : 2) void conv_bf16_kern
     const int wm = wave / WN, wn = wave % WN;
     const int g = lane >> 5, li = lane & 31;
 
-    const int ntiles = a.CoutP / BNT;
-    const int bid = xcd_order(blockIdx.x, gridDim.x);
-    const int nt = bid % ntiles;
-    const int mchunk = bid / ntiles;
-    const int img = mchunk / a.chunks, chunk = mchunk % a.chunks;
-    const int n0 = nt * BNT;
+    int img, chunk, n0;
+    conv_wg<BNT>(a, img, chunk, n0);
 
     // SPL == 2: the max-|x| words of the input tensor(s) are REQUESTED first thing and reduced only when the first staged
     // tile is about to be converted (below, behind the weight / coefficient / staging loads): read where the scale is
@@ -500,53 +496,30 @@ hipError_t launch_pack_conv_w_dgrad_bf16(const float *w, int Cout, int CinTotal,
 }
 
 // ---- dispatch
-template <int KS, int S, int WM, int WN, int WTM, int WTN, int SPL, bool BM = false, bool LZ = false>
+template <int KS, int S, class Sh, int SPL, bool BM = false, bool LZ = false>
 static hipError_t launch_b16_one(ConvArgs a, hipStream_t st, ConvArgs *resolved) {
-    using Cfg = ConvCfgB16<KS, S, WM, WN, WTM, WTN, SPL>;
+    using Cfg = ConvCfgB16<KS, S, Sh::WM, Sh::WN, Sh::WTM, Sh::WTN, SPL>;
+    static_assert(Cfg::PB == Sh::PB && Cfg::BNT == Sh::BNT, "the shape table and the kernel agree on the tile");
     if constexpr (!LZ) {
-        bool lazy = false;
-        for (int i = 0; i < a.nsrc; ++i) lazy |= a.src[i].la != nullptr;
-        if (lazy) {      // lazy sources: forward launches of the fp16-split mode (3x3 stride 1 / 2 and 1x1), never a data gradient
+        if (conv_any_lazy(a)) {      // lazy sources: forward launches of the fp16-split mode (3x3 stride 1 / 2 and 1x1), never a data gradient
             if constexpr (SPL == 2 && !BM && (KS == 3 || KS == 1)) {
                 if (a.bm_y) return hipErrorInvalidValue;
-                return launch_b16_one<KS, S, WM, WN, WTM, WTN, SPL, false, true>(a, st, resolved);
+                return launch_b16_one<KS, S, Sh, SPL, false, true>(a, st, resolved);
             } else {
                 return hipErrorInvalidValue;
             }
         }
     }
     if constexpr (!BM && S == 1 && (KS == 3 || KS == 1)) {      // backward-statistics epilogue: own instantiation
-        if (a.bm_y) return launch_b16_one<KS, S, WM, WN, WTM, WTN, SPL, true>(a, st, resolved);
+        if (a.bm_y) return launch_b16_one<KS, S, Sh, SPL, true>(a, st, resolved);
     } else if constexpr (!BM) {
         if (a.bm_y) return hipErrorInvalidValue;
     }
-    if (Cfg::LDS_BYTES > 160 * 1024) return hipErrorInvalidValue;
-    a.ppr = (a.Wout + 7) / 8;
-    a.ppi = a.ppr * ((a.Hout + 3) / 4);
-    a.chunks = (a.ppi + Cfg::PB - 1) / Cfg::PB;
+    conv_set_patches(a, Cfg::PB);
     if (a.CoutP % Cfg::BNT) return hipErrorInvalidValue;
     if (resolved) *resolved = a;
-    static DynLdsOnce attr_set;
-    auto kern = conv_bf16_kernel<KS, S, WM, WN, WTM, WTN, SPL, BM, LZ>;
-    {
-        const hipError_t e = attr_set.ensure(reinterpret_cast<const void *>(kern), (int)(Cfg::LDS_BYTES));
-        if (e != hipSuccess) return e;
-    }
-    const int ntiles = a.CoutP / Cfg::BNT;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(a.B * a.chunks * ntiles)), dim3(Cfg::NT), Cfg::LDS_BYTES, st, a);
-    return hipGetLastError();
-}
-template <int KS, int S, int SPL>
-static hipError_t launch_b16_shape(const ConvArgs &a, hipStream_t st, ConvArgs *resolved) {
-    switch (a.cfg & 15) {
-        case CFG_128x128: return launch_b16_one<KS, S, 2, 2, 2, 2, SPL>(a, st, resolved);
-        case CFG_128x64: return launch_b16_one<KS, S, 2, 2, 2, 1, SPL>(a, st, resolved);
-        case CFG_128x64m: return launch_b16_one<KS, S, 4, 1, 1, 2, SPL>(a, st, resolved);
-        case CFG_128x32: return launch_b16_one<KS, S, 4, 1, 1, 1, SPL>(a, st, resolved);
-        case CFG_64x128: return launch_b16_one<KS, S, 1, 4, 2, 1, SPL>(a, st, resolved);
-        case CFG_64x64: return launch_b16_one<KS, S, 2, 2, 1, 1, SPL>(a, st, resolved);
-        default: return hipErrorInvalidValue;
-    }
+    return launch_dyn_lds<conv_bf16_kernel<KS, S, Sh::WM, Sh::WN, Sh::WTM, Sh::WTN, SPL, BM, LZ>>(
+        Cfg::LDS_BYTES, dim3((unsigned)(a.B * a.chunks * (a.CoutP / Cfg::BNT))), dim3(Cfg::NT), st, a);
 }
 
 bool conv_bf16_ok(const ConvArgs &a, int ks, int stride) {
@@ -564,12 +537,11 @@ bool conv_bf16_ok(const ConvArgs &a, int ks, int stride) {
 
 template <int SPL>
 static hipError_t launch_conv_b16_spl(const ConvArgs &a, int ks, int stride, hipStream_t st, ConvArgs *resolved) {
-    if (ks == 3 && stride == 1) return launch_b16_shape<3, 1, SPL>(a, st, resolved);
-    if (ks == 3 && stride == 2) return launch_b16_shape<3, 2, SPL>(a, st, resolved);
-    if (ks == 1) return launch_b16_shape<1, 1, SPL>(a, st, resolved);
-    if (ks == 12) return launch_b16_shape<12, 1, SPL>(a, st, resolved);
-    if (ks == 21) return launch_b16_shape<21, 1, SPL>(a, st, resolved);
-    return launch_b16_shape<22, 1, SPL>(a, st, resolved);
+    return with_conv_window(ks, stride, [&](auto win) {
+        return with_conv_shape(a.cfg, [&](auto sh) {
+            return launch_b16_one<decltype(win)::KS, decltype(win)::S, decltype(sh), SPL>(a, st, resolved);
+        });
+    });
 }
 
 hipError_t launch_conv_bf16(const ConvArgs &a, int ks, int stride, hipStream_t st, ConvArgs *resolved) {

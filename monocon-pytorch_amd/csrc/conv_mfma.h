@@ -1,4 +1,4 @@
-// Fused implicit-GEMM convolution for gfx950 on the fp32 MFMA pipe.
+// Fused implicit-GEMM convolution for gfx950 on the fp32 MFMA pipe: contract, dispatch tables and shared device helpers.
 //
 //   out[b,y,x,n] = act( scale[n] * sum_{src,c,r,s} in_src[b, y*S-P+r, x*S-P+s, c] * W[n, c, r, s]
 //                       + bias[n] + residual[b,y,x,n] )
@@ -25,15 +25,20 @@
 //     output (and residual) may be a strided scatter (o_px / o_row), used by the stride-2 data gradient.
 //   * every global access is a buffer instruction: descriptor in SGPRs, lane offset resolved once,
 //     wave-uniform SGPR offset per K-chunk / tap -- no vector address arithmetic in the K loop.
-// Family: conv_mfma_kernel (this tiling), conv_mfma_ws_kernel (producer wave + double-buffered LDS),
-// conv_small_kernel (conv_small.hip: 16/32-channel layers on 16x16x4, no LDS), conv_bf16_kernel
+// Family: conv_mfma_kernel (this tiling) and conv_mfma_ws_kernel (producer wave + double-buffered LDS), both in
+// conv_mfma.hip; conv_small_kernel (conv_small.hip: 16/32-channel layers on 16x16x4, no LDS), conv_bf16_kernel
 // (conv_bf16.hip: bf16 operands, or fp32 emulated by a 3-way bf16 split).  launch_conv() dispatches on
 // ConvArgs::cfg / ::prec; results of the fp32 variants are bit-identical across workgroup shapes.
+// This header is what the family shares: the contract (ConvArgs, the shape ids and their table CONV_SHAPES, the
+// prototypes), the host-side visitors and the one dynamic-LDS launcher (with_conv_shape, with_conv_window,
+// launch_dyn_lds), and the device helpers every kernel file uses (buffer access, max-|x| slots, xcd_order, conv_wg,
+// conv_epilogue).  No kernel is defined here.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <atomic>
 #include <type_traits>
+#include <utility>
 
 namespace mc {
 
@@ -241,6 +246,20 @@ __device__ __forceinline__ int xcd_order(int b, int n) {
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
 }
 
+// The workgroup's place in the launch: image, chunk of PB patches, first column n0 of its BNT-column tile.  Shared by
+// conv_mfma_kernel, conv_mfma_ws_kernel and conv_bf16_kernel.  (Results as reference parameters, statements in this order:
+// returning them as a struct, or factoring the pinfo fill that follows in the kernels the same way, moved the kernarg load
+// of a.chunks and with it the schedule of the prologue in some instantiations.)
+template <int BNT>
+__device__ __forceinline__ void conv_wg(const ConvArgs &a, int &img, int &chunk, int &n0) {
+    const int ntiles = a.CoutP / BNT;
+    const int bid = xcd_order(blockIdx.x, gridDim.x);
+    const int nt = bid % ntiles;
+    const int mchunk = bid / ntiles;
+    img = mchunk / a.chunks, chunk = mchunk % a.chunks;
+    n0 = nt * BNT;
+}
+
 // Epilogue shared by both kernel variants.  C/D layout of v_mfma_f32_32x32x2: column = lane&31,
 // row m = (r&3) + 8*(r>>2) + 4*(lane>>5); row m of a 4x8 patch is pixel (oy0 + (m>>3), ox0 + (m&7))
 // = (oy0 + (r>>2), ox0 + (r&3) + 4*(lane>>5)).
@@ -430,365 +449,86 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs &a, f32x16 (&acc)[W
     else if (a.amax_out) amax_update_wave(a.amax_out, vmax);
 }
 
-template <int KS, int S, int CK, int WM, int WN, int WTM, int WTN, bool BM = false>
-__global__ __launch_bounds__(64 * WM * WN, 3) void conv_mfma_kernel(const ConvArgs a) {
-    using Cfg = ConvCfg<KS, S, CK, WM, WN, WTM, WTN>;
-    constexpr int PB = Cfg::PB, BNT = Cfg::BNT, NT = Cfg::NT, PAD = Cfg::PAD;
-    constexpr int IW = Cfg::IW, NPIX = Cfg::NPIX, CKP = Cfg::CKP;
-    constexpr int C4 = CK / 4;
-    static_assert(NT % C4 == 0, "a thread keeps one channel group across its staging elements");
-
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    int *pinfo = reinterpret_cast<int *>(lds + PB * NPIX * CKP);   // [PB][4] = b, oy0, ox0, valid
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave / WN, wn = wave % WN;
-    const int g = lane >> 5, li = lane & 31;
-
-    const int ntiles = a.CoutP / BNT;
-    const int bid = xcd_order(blockIdx.x, gridDim.x);
-    const int nt = bid % ntiles;
-    const int mchunk = bid / ntiles;
-    const int img = mchunk / a.chunks, chunk = mchunk % a.chunks;
-    const int n0 = nt * BNT;
-
-    if (tid < PB) {
-        const int pp = chunk * PB + tid;
-        const int valid = pp < a.ppi;
-        const int py = pp / a.ppr, px = pp % a.ppr;
-        pinfo[tid * 4 + 0] = img;
-        pinfo[tid * 4 + 1] = py * 4;
-        pinfo[tid * 4 + 2] = px * 8;
-        pinfo[tid * 4 + 3] = valid;
-    }
-    __syncthreads();
-
-    f32x16 acc[WTM][WTN];
-#pragma unroll
-    for (int tm = 0; tm < WTM; ++tm)
-#pragma unroll
-        for (int tn = 0; tn < WTN; ++tn)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
-
-    // ---- staging plan: element e = tid + NT*i of the [PB][NPIX][C4] halo tile.  Its input pixel
-    //      does not depend on the K-chunk, so the lane offsets are resolved once per source; inside
-    //      the K loop a chunk is NIT buffer loads (SGPR chunk offset) + NIT ds_write_b128 at
-    //      immediate offsets.
-    constexpr int TOTAL = PB * NPIX * C4;
-    constexpr int NIT = (TOTAL + NT - 1) / NT;
-    const int c4 = tid % C4;
-    float *stage_dst = lds + (tid / C4) * CKP + c4 * 4;
-
-    // A-fragment base offsets (floats) inside the LDS image for this lane
-    int a_off[WTM];
-#pragma unroll
-    for (int tm = 0; tm < WTM; ++tm)
-        a_off[tm] = ((wm * WTM + tm) * NPIX + ((li >> 3) * S) * IW + (li & 7) * S) * CKP + 4 * g;
-
-    const int Cin4 = a.Cin >> 2;
-    const __amdgpu_buffer_rsrc_t r_w = make_rsrc(a.wpk, (unsigned)(Cfg::KH * Cfg::KW * a.Cin * a.CoutP) * 4u);
-    const int w_lane = (g * a.CoutP + n0 + wn * WTN * 32 + li) * 16;   // bytes
-
-    // B fragment of step s (= tap * CK/8 + k8) of the K-chunk starting at concat channel kc
-    constexpr int K8 = CK / 8, NS = Cfg::KH * Cfg::KW * K8;
-    auto load_b = [&](f32x4(&dst)[WTN], int kc, int s) {
-        const int tap = s / K8, k8 = s % K8;
-        const int soff = (tap * Cin4 + ((kc + k8 * 8) >> 2)) * a.CoutP * 16;
-#pragma unroll
-        for (int tn = 0; tn < WTN; ++tn) dst[tn] = buf_load4(r_w, w_lane + tn * 32 * 16, soff);
-    };
-    auto load_a = [&](f32x4(&dst)[WTM], int s) {
-        const int tap = s / K8, k8 = s % K8;
-#pragma unroll
-        for (int tm = 0; tm < WTM; ++tm)
-            dst[tm] = *reinterpret_cast<const f32x4 *>(
-                &lds[a_off[tm] + ((tap / Cfg::KW) * IW + (tap % Cfg::KW)) * CKP + k8 * 8]);
-    };
-    f32x4 bcur[WTN];
-    load_b(bcur, 0, 0);   // weights do not depend on the staged tile: in flight across the barriers
-    const EpiCoef<WTN> coef = conv_epi_coef<WN, WTN, BM>(a, n0, wn, li);
-
-    int kbase = 0;   // channel offset of the current source inside the virtual concat
-    for (int si = 0; si < a.nsrc; ++si) {
-        const int Cs = a.src[si].C;
-        const __amdgpu_buffer_rsrc_t r_in =
-            make_rsrc(a.src[si].p + (size_t)img * a.Hin * a.Win * Cs, (unsigned)(a.Hin * a.Win * Cs) * 4u);
-        int voff[NIT];
-#pragma unroll
-        for (int i = 0; i < NIT; ++i) {
-            const int e = tid + NT * i;
-            const int t = e / C4;
-            const int pix = t % NPIX;
-            const int p = (t / NPIX) % PB;
-            const int iy = pix / IW, ix = pix % IW;
-            const int y = pinfo[p * 4 + 1] * S - PAD + iy;
-            const int x = pinfo[p * 4 + 2] * S - PAD + ix;
-            const bool ok = e < TOTAL && pinfo[p * 4 + 3] && y >= 0 && y < a.Hin && x >= 0 && x < a.Win;
-            voff[i] = ok ? ((y * a.Win + x) * Cs + c4 * 4) * 4 : BUF_OOB;
-        }
-        for (int c0 = 0; c0 < Cs; c0 += CK) {
-            if (kbase + c0 > 0) __syncthreads();   // previous chunk's fragment reads done
-            // ---- stage [PB][NPIX][CK] input halo, zero-filled outside the image
-            constexpr int UB = NIT > 8 ? 8 : NIT;   // loads in flight per batch
-#pragma unroll
-            for (int i0 = 0; i0 < NIT; i0 += UB) {
-                f32x4 v[UB];
-#pragma unroll
-                for (int u = 0; u < UB; ++u)
-                    if (i0 + u < NIT) v[u] = buf_load4(r_in, voff[i0 + u], c0 * 4);
-#pragma unroll
-                for (int u = 0; u < UB; ++u) {
-                    const int i = i0 + u;
-                    if (i < NIT && (NT * (i + 1) <= TOTAL || tid + NT * i < TOTAL))
-                        *reinterpret_cast<f32x4 *>(stage_dst + i * (NT / C4) * CKP) = v[u];
-                }
-            }
-            __syncthreads();
-            // ---- MFMA over taps x channel groups of 8; both operands are fetched one step ahead
-            //      (explicit register double-buffering: hipcc otherwise issues each weight load
-            //      right in front of the MFMA that consumes it and exposes the full L2 latency)
-            const int kc = kbase + c0;
-            const int kc_next = (kc + CK < a.Cin) ? kc + CK : kc;   // last chunk: harmless re-load
-            f32x4 acur[WTM];
-            load_a(acur, 0);
-#pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                f32x4 anext[WTM], bnext[WTN];
-                if (s + 1 < NS) {
-                    load_a(anext, s + 1);
-                    load_b(bnext, kc, s + 1);
-                } else {
-                    load_b(bnext, kc_next, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);   // keep the prefetch ahead of this step's MFMAs
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-#pragma unroll
-                    for (int tm = 0; tm < WTM; ++tm)
-#pragma unroll
-                        for (int tn = 0; tn < WTN; ++tn)
-                            acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(
-                                acur[tm][j], bcur[tn][j], acc[tm][tn], 0, 0, 0);
-                if (s + 1 < NS) {
-#pragma unroll
-                    for (int tm = 0; tm < WTM; ++tm) acur[tm] = anext[tm];
-                }
-#pragma unroll
-                for (int tn = 0; tn < WTN; ++tn) bcur[tn] = bnext[tn];
-            }
-        }
-        kbase += Cs;
-    }
-
-    conv_epilogue<WM, WN, WTM, WTN, BNT, BM>(a, acc, pinfo, chunk * PB, img, n0, wm, wn, g, li, coef);
-}
-
-// ---- wave-specialised variant -------------------------------------------------------------
-// Same math, same operand layouts and the same accumulation order as conv_mfma_kernel (results are
-// bit-identical), but the workgroup carries one extra PRODUCER wave that stages K-chunk i+1 into
-// the second half of a double-buffered LDS tile while the WM*WN consumer waves run the MFMA steps
-// of chunk i.  One barrier per chunk instead of two, and no MFMA wave ever waits on HBM.
-template <int KS, int S, int CK, int WM, int WN, int WTM, int WTN>
-struct ConvCfgWS : ConvCfg<KS, S, CK, WM, WN, WTM, WTN> {
-    using Base = ConvCfg<KS, S, CK, WM, WN, WTM, WTN>;
-    static constexpr int NT = 64 * (WM * WN + 1);
-    static constexpr int TILE = Base::PB * Base::NPIX * Base::CKP;
-    static constexpr int LDS_FLOATS = 2 * TILE + Base::PB * 4;
-    static constexpr size_t LDS_BYTES = sizeof(float) * LDS_FLOATS;
-};
-
-template <int KS, int S, int CK, int WM, int WN, int WTM, int WTN>
-__global__ __launch_bounds__(64 * (WM * WN + 1), 3) void conv_mfma_ws_kernel(const ConvArgs a) {
-    using Cfg = ConvCfgWS<KS, S, CK, WM, WN, WTM, WTN>;
-    constexpr int PB = Cfg::PB, BNT = Cfg::BNT, PAD = Cfg::PAD;
-    constexpr int IW = Cfg::IW, NPIX = Cfg::NPIX, CKP = Cfg::CKP, TILE = Cfg::TILE;
-    constexpr int C4 = CK / 4;
-
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    int *pinfo = reinterpret_cast<int *>(lds + 2 * TILE);   // [PB][4] = b, oy0, ox0, valid
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const bool producer = wave == WM * WN;
-    const int wm = wave / WN, wn = wave % WN;
-    const int g = lane >> 5, li = lane & 31;
-
-    const int ntiles = a.CoutP / BNT;
-    const int bid = xcd_order(blockIdx.x, gridDim.x);
-    const int nt = bid % ntiles;
-    const int mchunk = bid / ntiles;
-    const int img = mchunk / a.chunks, chunk = mchunk % a.chunks;
-    const int n0 = nt * BNT;
-
-    if (tid < PB) {
-        const int pp = chunk * PB + tid;
-        const int valid = pp < a.ppi;
-        const int py = pp / a.ppr, px = pp % a.ppr;
-        pinfo[tid * 4 + 0] = img;
-        pinfo[tid * 4 + 1] = py * 4;
-        pinfo[tid * 4 + 2] = px * 8;
-        pinfo[tid * 4 + 3] = valid;
-    }
-    __syncthreads();
-
-    if (producer) {
-        // ---- producer wave: element e = lane + 64*i of the [PB][NPIX][C4] tile (see
-        //      conv_mfma_kernel: lane offsets once per source, then loads + LDS writes only)
-        constexpr int TOTAL = PB * NPIX * C4;
-        constexpr int NIT = (TOTAL + 63) / 64;
-        constexpr int UB = NIT > 8 ? 8 : NIT;   // loads kept in flight per batch
-        static_assert(64 % C4 == 0, "a lane keeps one channel group across its elements");
-        const int c4 = lane % C4;
-        int ci = 0;
-        for (int si = 0; si < a.nsrc; ++si) {
-            const int Cs = a.src[si].C;
-            const __amdgpu_buffer_rsrc_t r_in =
-                make_rsrc(a.src[si].p + (size_t)img * a.Hin * a.Win * Cs, (unsigned)(a.Hin * a.Win * Cs) * 4u);
-            int voff[NIT];
-#pragma unroll
-            for (int i = 0; i < NIT; ++i) {
-                const int e = lane + 64 * i;
-                const int t = e / C4;
-                const int pix = t % NPIX;
-                const int p = (t / NPIX) % PB;
-                const int iy = pix / IW, ix = pix % IW;
-                const int y = pinfo[p * 4 + 1] * S - PAD + iy;
-                const int x = pinfo[p * 4 + 2] * S - PAD + ix;
-                const bool ok = e < TOTAL && pinfo[p * 4 + 3] && y >= 0 && y < a.Hin && x >= 0 && x < a.Win;
-                voff[i] = ok ? ((y * a.Win + x) * Cs + c4 * 4) * 4 : BUF_OOB;
-            }
-            for (int c0 = 0; c0 < Cs; c0 += CK, ++ci) {
-                float *dst = lds + (ci & 1) * TILE + (lane / C4) * CKP + c4 * 4;
-#pragma unroll
-                for (int i0 = 0; i0 < NIT; i0 += UB) {
-                    f32x4 v[UB];
-#pragma unroll
-                    for (int u = 0; u < UB; ++u)
-                        if (i0 + u < NIT) v[u] = buf_load4(r_in, voff[i0 + u], c0 * 4);
-#pragma unroll
-                    for (int u = 0; u < UB; ++u) {
-                        const int i = i0 + u;
-                        if (i < NIT && (64 * (i + 1) <= TOTAL || lane + 64 * i < TOTAL))
-                            *reinterpret_cast<f32x4 *>(dst + i * (64 / C4) * CKP) = v[u];
-                    }
-                }
-                __syncthreads();   // chunk ci is published; consumers are done with chunk ci-1
-            }
-        }
-    } else {
-        f32x16 acc[WTM][WTN];
-#pragma unroll
-        for (int tm = 0; tm < WTM; ++tm)
-#pragma unroll
-            for (int tn = 0; tn < WTN; ++tn)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
-
-        int a_off[WTM];
-#pragma unroll
-        for (int tm = 0; tm < WTM; ++tm)
-            a_off[tm] = ((wm * WTM + tm) * NPIX + ((li >> 3) * S) * IW + (li & 7) * S) * CKP + 4 * g;
-
-        const int Cin4 = a.Cin >> 2;
-        const __amdgpu_buffer_rsrc_t r_w = make_rsrc(a.wpk, (unsigned)(Cfg::KH * Cfg::KW * a.Cin * a.CoutP) * 4u);
-        const int w_lane = (g * a.CoutP + n0 + wn * WTN * 32 + li) * 16;   // bytes
-
-        constexpr int K8 = CK / 8, NS = Cfg::KH * Cfg::KW * K8;
-        auto load_b = [&](f32x4(&dst)[WTN], int kc, int s) {
-            const int tap = s / K8, k8 = s % K8;
-            const int soff = (tap * Cin4 + ((kc + k8 * 8) >> 2)) * a.CoutP * 16;
-#pragma unroll
-            for (int tn = 0; tn < WTN; ++tn) dst[tn] = buf_load4(r_w, w_lane + tn * 32 * 16, soff);
-        };
-        f32x4 bcur[WTN];
-        load_b(bcur, 0, 0);
-        const EpiCoef<WTN> coef = conv_epi_coef<WN, WTN, false>(a, n0, wn, li);
-        const int nch = a.Cin / CK;
-        __syncthreads();   // chunk 0 staged
-        for (int ci = 0; ci < nch; ++ci) {
-            const float *tile = lds + (ci & 1) * TILE;
-            auto load_a = [&](f32x4(&dst)[WTM], int s) {
-                const int tap = s / K8, k8 = s % K8;
-#pragma unroll
-                for (int tm = 0; tm < WTM; ++tm)
-                    dst[tm] = *reinterpret_cast<const f32x4 *>(
-                        &tile[a_off[tm] + ((tap / Cfg::KW) * IW + (tap % Cfg::KW)) * CKP + k8 * 8]);
-            };
-            const int kc = ci * CK;
-            const int kc_next = (ci + 1 < nch) ? kc + CK : kc;
-            f32x4 acur[WTM];
-            load_a(acur, 0);
-#pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                f32x4 anext[WTM], bnext[WTN];
-                if (s + 1 < NS) {
-                    load_a(anext, s + 1);
-                    load_b(bnext, kc, s + 1);
-                } else {
-                    load_b(bnext, kc_next, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-#pragma unroll
-                    for (int tm = 0; tm < WTM; ++tm)
-#pragma unroll
-                        for (int tn = 0; tn < WTN; ++tn)
-                            acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(
-                                acur[tm][j], bcur[tn][j], acc[tm][tn], 0, 0, 0);
-                if (s + 1 < NS) {
-#pragma unroll
-                    for (int tm = 0; tm < WTM; ++tm) acur[tm] = anext[tm];
-                }
-#pragma unroll
-                for (int tn = 0; tn < WTN; ++tn) bcur[tn] = bnext[tn];
-            }
-            if (ci + 1 < nch) __syncthreads();   // chunk ci+1 staged, chunk ci released
-        }
-        conv_epilogue<WM, WN, WTM, WTN, BNT>(a, acc, pinfo, chunk * PB, img, n0, wm, wn, g, li, coef);
-    }
-}
-
 // ---- host-side tile selection ---------------------------------------------------------
 // Workgroup shapes (WM x WN waves, each wave WTM x WTN 32x32 MFMA tiles).  A shape owns
 // PB = WM*WTM patches (32 output pixels each) and BNT = WN*WTN*32 output channels.
-struct ConvShape {
-    int WM, WN, WTM, WTN;
-    int PB() const { return WM * WTM; }
-    int BNT() const { return WN * WTN * 32; }
-};
 enum ConvCfgId {
     CFG_AUTO = 0,
     CFG_128x128 = 1,    // 2x2 waves, 2x2 tiles : 128 px x 128 ch
-    CFG_256x64 = 2,     // (retired: 8-patch shapes never won and spill under the 3-waves/SIMD cap)
-    CFG_256x32 = 3,
+                        // (2, 3 -- 256 x 64, 256 x 32 -- are retired and no shape id any more: 8-patch shapes never won and
+                        // spill under the 3-waves/SIMD cap)
     CFG_128x64 = 4,     // 2x2 waves, 2x1 tiles : 128 px x  64 ch
     CFG_128x64m = 5,    // 4x1 waves, 1x2 tiles : 128 px x  64 ch (waves split M only)
     CFG_128x32 = 6,     // 4x1 waves, 1x1 tiles : 128 px x  32 ch
     CFG_64x128 = 7,     // 1x4 waves, 2x1 tiles :  64 px x 128 ch
     CFG_64x64 = 8,      // 2x2 waves, 1x1 tiles :  64 px x  64 ch
-    CFG_COUNT = 9,
+    CFG_SHAPE_BITS = 15,
     CFG_WS = 16,        // flag: wave-specialised kernel (producer wave + double-buffered LDS)
     CFG_SMALL = 32,     // LDS-free 16x16x4 kernel for 16/32-channel 3x3 layers (conv_small.hip)
     CFG_WRES = 64       // flag: weight-resident persistent kernel (conv_wres.hip) where the launch is eligible; the shape
                         // bits name the tiling every other launch with this id takes (results are bit-identical)
 };
+// THE table of tilings: an id is a shape id exactly when it has an entry, and every entry has a kernel in each family
+// (conv_mfma.hip plain + WS, conv_bf16.hip).  conv_shape() reads it at run time, with_conv_shape() at compile time.
+struct ConvShape {
+    int id, WM, WN, WTM, WTN;
+    constexpr int PB() const { return WM * WTM; }
+    constexpr int BNT() const { return WN * WTN * 32; }
+};
+constexpr ConvShape CONV_SHAPES[] = {
+    {CFG_128x128, 2, 2, 2, 2}, {CFG_128x64, 2, 2, 2, 1}, {CFG_128x64m, 4, 1, 1, 2},
+    {CFG_128x32, 4, 1, 1, 1},  {CFG_64x128, 1, 4, 2, 1}, {CFG_64x64, 2, 2, 1, 1},
+};
+constexpr int CONV_NSHAPES = (int)(sizeof(CONV_SHAPES) / sizeof(CONV_SHAPES[0]));
+// the shape the bits `cfg & CFG_SHAPE_BITS` name; all zero (id 0) when they name none
 inline ConvShape conv_shape(int cfg) {
-    switch (cfg & 15) {
-        case CFG_128x128: return {2, 2, 2, 2};
-        case CFG_256x64: return {4, 1, 2, 2};
-        case CFG_256x32: return {4, 1, 2, 1};
-        case CFG_128x64: return {2, 2, 2, 1};
-        case CFG_128x64m: return {4, 1, 1, 2};
-        case CFG_128x32: return {4, 1, 1, 1};
-        case CFG_64x128: return {1, 4, 2, 1};
-        case CFG_64x64: return {2, 2, 1, 1};
-        default: return {0, 0, 0, 0};
-    }
+    for (const ConvShape &s : CONV_SHAPES)
+        if (s.id == (cfg & CFG_SHAPE_BITS)) return s;
+    return {0, 0, 0, 0, 0};
+}
+// entry I as a type: what a kernel family instantiates on
+template <int I>
+struct ConvShapeC {
+    static constexpr int WM = CONV_SHAPES[I].WM, WN = CONV_SHAPES[I].WN, WTM = CONV_SHAPES[I].WTM, WTN = CONV_SHAPES[I].WTN;
+    static constexpr int PB = CONV_SHAPES[I].PB(), BNT = CONV_SHAPES[I].BNT();
+};
+template <typename F, int... I>
+inline hipError_t with_conv_shape_seq(int id, F &f, std::integer_sequence<int, I...>) {
+    hipError_t e = hipErrorInvalidValue;
+    (void)((CONV_SHAPES[I].id == id && ((e = f(ConvShapeC<I>{})), true)) || ...);
+    return e;
+}
+// f(ConvShapeC<I>{}) for the entry `cfg`'s shape bits name; hipErrorInvalidValue when they name none
+template <typename F>
+inline hipError_t with_conv_shape(int cfg, F &&f) {
+    return with_conv_shape_seq(cfg & CFG_SHAPE_BITS, f, std::make_integer_sequence<int, CONV_NSHAPES>{});
+}
+// The filter window as a type.  f(ConvWin<KS, S>{}) for the (window code, stride) pairs that have kernels: 3x3 stride 1 / 2,
+// 1x1, and the three parity classes of a stride-2 data gradient; hipErrorInvalidValue otherwise.
+template <int KS_, int S_>
+struct ConvWin { static constexpr int KS = KS_, S = S_; };
+template <typename F>
+inline hipError_t with_conv_window(int ks, int stride, F &&f) {
+    if (ks == 3 && stride == 1) return f(ConvWin<3, 1>{});
+    if (ks == 3 && stride == 2) return f(ConvWin<3, 2>{});
+    if (stride != 1) return hipErrorInvalidValue;
+    if (ks == 1) return f(ConvWin<1, 1>{});
+    if (ks == 12) return f(ConvWin<12, 1>{});
+    if (ks == 21) return f(ConvWin<21, 1>{});
+    if (ks == 22) return f(ConvWin<22, 1>{});
+    return hipErrorInvalidValue;
+}
+
+// One launch of a kernel with dynamic LDS.  Owns the DynLdsOnce of its kernel (one instantiation per kernel: Kern is a
+// template argument), refuses a request above the 160 KB of a CU, launches and returns hipGetLastError().
+template <auto Kern, typename... Args>
+inline hipError_t launch_dyn_lds(size_t lds_bytes, dim3 grid, dim3 block, hipStream_t st, const Args &...args) {
+    if (lds_bytes > 160 * 1024) return hipErrorInvalidValue;
+    static DynLdsOnce attr_set;
+    const hipError_t e = attr_set.ensure(reinterpret_cast<const void *>(Kern), (int)lds_bytes);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(Kern, grid, block, lds_bytes, st, args...);
+    return hipGetLastError();
 }
 
 // Column padding of the packed weights for a layer with Cout columns (every shape's BNT that
@@ -809,13 +549,24 @@ inline int conv_ck(int ks, int stride, const int *src_c, int nsrc) {
 // stride (stride-2 halos are 9x17 pixels per patch, so fewer patches per workgroup keep several
 // workgroups resident per CU) and on how many workgroups the launch would have.
 int conv_pick_cfg(int Cout, int CoutP, int ks, int stride, int B, int Hout, int Wout);
-// patches per workgroup of the shape launch_conv() will use for these arguments
-inline int conv_patches_per_block(int cfg) { return conv_shape(cfg).PB(); }
 // statistics partials per image a launch with this shape writes (ConvArgs::chunks)
 inline int conv_chunks_per_image(int cfg, int Hout, int Wout) {
     if (cfg == CFG_SMALL) return Hout;                    // the row kernel: one partial per output row
     return ((Wout + 7) / 8) * ((Hout + 3) / 4);           // every tiling: one partial per 4x8 patch
 }
+// the patch grid of the output (ConvArgs::ppr / ppi) and the workgroup chunks per image of a kernel that owns PB patches
+inline void conv_set_patches(ConvArgs &a, int PB) {
+    a.ppr = (a.Wout + 7) / 8;
+    a.ppi = a.ppr * ((a.Hout + 3) / 4);
+    a.chunks = (a.ppi + PB - 1) / PB;
+}
+// does any source carry lazy coefficients (ConvSrc::la)?
+inline bool any_lazy_src(const ConvSrc *src, int nsrc) {
+    for (int i = 0; i < nsrc; ++i)
+        if (src[i].la) return true;
+    return false;
+}
+inline bool conv_any_lazy(const ConvArgs &a) { return any_lazy_src(a.src, a.nsrc); }
 bool conv_small_ok(const ConvArgs &a, int ks, int stride);
 bool conv_small_lazy_ok(const ConvArgs &a, int ks, int stride);     // conv_small_kernel<2, 16, 2, LZ>: lazy source (ConvSrc::la)
 bool conv_bf16_ok(const ConvArgs &a, int ks, int stride);

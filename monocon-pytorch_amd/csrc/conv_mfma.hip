@@ -1,4 +1,5 @@
-// Instantiations + dispatch of the fused MFMA convolution (see conv_mfma.h).
+// The fp32 kernels of the fused MFMA convolution (contract, helpers and epilogue: conv_mfma.h) and launch_conv(), the
+// dispatch of the whole family.
 #include <cstdlib>
 #include "conv_mfma.h"
 
@@ -16,75 +17,359 @@ static ProfLast conv_cost(const ConvArgs &a, int ks) {
 }
 
 template <int KS, int S, int CK, int WM, int WN, int WTM, int WTN, bool BM = false>
-static hipError_t launch_one(ConvArgs a, hipStream_t st, ConvArgs *resolved) {
+__global__ __launch_bounds__(64 * WM * WN, 3) void conv_mfma_kernel(const ConvArgs a) {
     using Cfg = ConvCfg<KS, S, CK, WM, WN, WTM, WTN>;
+    constexpr int PB = Cfg::PB, BNT = Cfg::BNT, NT = Cfg::NT, PAD = Cfg::PAD;
+    constexpr int IW = Cfg::IW, NPIX = Cfg::NPIX, CKP = Cfg::CKP;
+    constexpr int C4 = CK / 4;
+    static_assert(NT % C4 == 0, "a thread keeps one channel group across its staging elements");
+
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    int *pinfo = reinterpret_cast<int *>(lds + PB * NPIX * CKP);   // [PB][4] = b, oy0, ox0, valid
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave / WN, wn = wave % WN;
+    const int g = lane >> 5, li = lane & 31;
+
+    int img, chunk, n0;
+    conv_wg<BNT>(a, img, chunk, n0);
+
+    if (tid < PB) {
+        const int pp = chunk * PB + tid;
+        const int valid = pp < a.ppi;
+        const int py = pp / a.ppr, px = pp % a.ppr;
+        pinfo[tid * 4 + 0] = img;
+        pinfo[tid * 4 + 1] = py * 4;
+        pinfo[tid * 4 + 2] = px * 8;
+        pinfo[tid * 4 + 3] = valid;
+    }
+    __syncthreads();
+
+    f32x16 acc[WTM][WTN];
+#pragma unroll
+    for (int tm = 0; tm < WTM; ++tm)
+#pragma unroll
+        for (int tn = 0; tn < WTN; ++tn)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
+
+    // ---- staging plan: element e = tid + NT*i of the [PB][NPIX][C4] halo tile.  Its input pixel
+    //      does not depend on the K-chunk, so the lane offsets are resolved once per source; inside
+    //      the K loop a chunk is NIT buffer loads (SGPR chunk offset) + NIT ds_write_b128 at
+    //      immediate offsets.
+    constexpr int TOTAL = PB * NPIX * C4;
+    constexpr int NIT = (TOTAL + NT - 1) / NT;
+    const int c4 = tid % C4;
+    float *stage_dst = lds + (tid / C4) * CKP + c4 * 4;
+
+    // A-fragment base offsets (floats) inside the LDS image for this lane
+    int a_off[WTM];
+#pragma unroll
+    for (int tm = 0; tm < WTM; ++tm)
+        a_off[tm] = ((wm * WTM + tm) * NPIX + ((li >> 3) * S) * IW + (li & 7) * S) * CKP + 4 * g;
+
+    const int Cin4 = a.Cin >> 2;
+    const __amdgpu_buffer_rsrc_t r_w = make_rsrc(a.wpk, (unsigned)(Cfg::KH * Cfg::KW * a.Cin * a.CoutP) * 4u);
+    const int w_lane = (g * a.CoutP + n0 + wn * WTN * 32 + li) * 16;   // bytes
+
+    // B fragment of step s (= tap * CK/8 + k8) of the K-chunk starting at concat channel kc
+    constexpr int K8 = CK / 8, NS = Cfg::KH * Cfg::KW * K8;
+    auto load_b = [&](f32x4(&dst)[WTN], int kc, int s) {
+        const int tap = s / K8, k8 = s % K8;
+        const int soff = (tap * Cin4 + ((kc + k8 * 8) >> 2)) * a.CoutP * 16;
+#pragma unroll
+        for (int tn = 0; tn < WTN; ++tn) dst[tn] = buf_load4(r_w, w_lane + tn * 32 * 16, soff);
+    };
+    auto load_a = [&](f32x4(&dst)[WTM], int s) {
+        const int tap = s / K8, k8 = s % K8;
+#pragma unroll
+        for (int tm = 0; tm < WTM; ++tm)
+            dst[tm] = *reinterpret_cast<const f32x4 *>(
+                &lds[a_off[tm] + ((tap / Cfg::KW) * IW + (tap % Cfg::KW)) * CKP + k8 * 8]);
+    };
+    f32x4 bcur[WTN];
+    load_b(bcur, 0, 0);   // weights do not depend on the staged tile: in flight across the barriers
+    const EpiCoef<WTN> coef = conv_epi_coef<WN, WTN, BM>(a, n0, wn, li);
+
+    int kbase = 0;   // channel offset of the current source inside the virtual concat
+    for (int si = 0; si < a.nsrc; ++si) {
+        const int Cs = a.src[si].C;
+        const __amdgpu_buffer_rsrc_t r_in =
+            make_rsrc(a.src[si].p + (size_t)img * a.Hin * a.Win * Cs, (unsigned)(a.Hin * a.Win * Cs) * 4u);
+        int voff[NIT];
+#pragma unroll
+        for (int i = 0; i < NIT; ++i) {
+            const int e = tid + NT * i;
+            const int t = e / C4;
+            const int pix = t % NPIX;
+            const int p = (t / NPIX) % PB;
+            const int iy = pix / IW, ix = pix % IW;
+            const int y = pinfo[p * 4 + 1] * S - PAD + iy;
+            const int x = pinfo[p * 4 + 2] * S - PAD + ix;
+            const bool ok = e < TOTAL && pinfo[p * 4 + 3] && y >= 0 && y < a.Hin && x >= 0 && x < a.Win;
+            voff[i] = ok ? ((y * a.Win + x) * Cs + c4 * 4) * 4 : BUF_OOB;
+        }
+        for (int c0 = 0; c0 < Cs; c0 += CK) {
+            if (kbase + c0 > 0) __syncthreads();   // previous chunk's fragment reads done
+            // ---- stage [PB][NPIX][CK] input halo, zero-filled outside the image
+            constexpr int UB = NIT > 8 ? 8 : NIT;   // loads in flight per batch
+#pragma unroll
+            for (int i0 = 0; i0 < NIT; i0 += UB) {
+                f32x4 v[UB];
+#pragma unroll
+                for (int u = 0; u < UB; ++u)
+                    if (i0 + u < NIT) v[u] = buf_load4(r_in, voff[i0 + u], c0 * 4);
+#pragma unroll
+                for (int u = 0; u < UB; ++u) {
+                    const int i = i0 + u;
+                    if (i < NIT && (NT * (i + 1) <= TOTAL || tid + NT * i < TOTAL))
+                        *reinterpret_cast<f32x4 *>(stage_dst + i * (NT / C4) * CKP) = v[u];
+                }
+            }
+            __syncthreads();
+            // ---- MFMA over taps x channel groups of 8; both operands are fetched one step ahead
+            //      (explicit register double-buffering: hipcc otherwise issues each weight load
+            //      right in front of the MFMA that consumes it and exposes the full L2 latency)
+            const int kc = kbase + c0;
+            const int kc_next = (kc + CK < a.Cin) ? kc + CK : kc;   // last chunk: harmless re-load
+            f32x4 acur[WTM];
+            load_a(acur, 0);
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                f32x4 anext[WTM], bnext[WTN];
+                if (s + 1 < NS) {
+                    load_a(anext, s + 1);
+                    load_b(bnext, kc, s + 1);
+                } else {
+                    load_b(bnext, kc_next, 0);
+                }
+                __builtin_amdgcn_sched_barrier(0);   // keep the prefetch ahead of this step's MFMAs
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int tm = 0; tm < WTM; ++tm)
+#pragma unroll
+                        for (int tn = 0; tn < WTN; ++tn)
+                            acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(
+                                acur[tm][j], bcur[tn][j], acc[tm][tn], 0, 0, 0);
+                if (s + 1 < NS) {
+#pragma unroll
+                    for (int tm = 0; tm < WTM; ++tm) acur[tm] = anext[tm];
+                }
+#pragma unroll
+                for (int tn = 0; tn < WTN; ++tn) bcur[tn] = bnext[tn];
+            }
+        }
+        kbase += Cs;
+    }
+
+    conv_epilogue<WM, WN, WTM, WTN, BNT, BM>(a, acc, pinfo, chunk * PB, img, n0, wm, wn, g, li, coef);
+}
+
+// ---- wave-specialised variant -------------------------------------------------------------
+// Same math, same operand layouts and the same accumulation order as conv_mfma_kernel (results are
+// bit-identical), but the workgroup carries one extra PRODUCER wave that stages K-chunk i+1 into
+// the second half of a double-buffered LDS tile while the WM*WN consumer waves run the MFMA steps
+// of chunk i.  One barrier per chunk instead of two, and no MFMA wave ever waits on HBM.
+template <int KS, int S, int CK, int WM, int WN, int WTM, int WTN>
+struct ConvCfgWS : ConvCfg<KS, S, CK, WM, WN, WTM, WTN> {
+    using Base = ConvCfg<KS, S, CK, WM, WN, WTM, WTN>;
+    static constexpr int NT = 64 * (WM * WN + 1);
+    static constexpr int TILE = Base::PB * Base::NPIX * Base::CKP;
+    static constexpr int LDS_FLOATS = 2 * TILE + Base::PB * 4;
+    static constexpr size_t LDS_BYTES = sizeof(float) * LDS_FLOATS;
+};
+
+template <int KS, int S, int CK, int WM, int WN, int WTM, int WTN>
+__global__ __launch_bounds__(64 * (WM * WN + 1), 3) void conv_mfma_ws_kernel(const ConvArgs a) {
+    using Cfg = ConvCfgWS<KS, S, CK, WM, WN, WTM, WTN>;
+    constexpr int PB = Cfg::PB, BNT = Cfg::BNT, PAD = Cfg::PAD;
+    constexpr int IW = Cfg::IW, NPIX = Cfg::NPIX, CKP = Cfg::CKP, TILE = Cfg::TILE;
+    constexpr int C4 = CK / 4;
+
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    int *pinfo = reinterpret_cast<int *>(lds + 2 * TILE);   // [PB][4] = b, oy0, ox0, valid
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const bool producer = wave == WM * WN;
+    const int wm = wave / WN, wn = wave % WN;
+    const int g = lane >> 5, li = lane & 31;
+
+    int img, chunk, n0;
+    conv_wg<BNT>(a, img, chunk, n0);
+
+    if (tid < PB) {
+        const int pp = chunk * PB + tid;
+        const int valid = pp < a.ppi;
+        const int py = pp / a.ppr, px = pp % a.ppr;
+        pinfo[tid * 4 + 0] = img;
+        pinfo[tid * 4 + 1] = py * 4;
+        pinfo[tid * 4 + 2] = px * 8;
+        pinfo[tid * 4 + 3] = valid;
+    }
+    __syncthreads();
+
+    if (producer) {
+        // ---- producer wave: element e = lane + 64*i of the [PB][NPIX][C4] tile (see
+        //      conv_mfma_kernel: lane offsets once per source, then loads + LDS writes only)
+        constexpr int TOTAL = PB * NPIX * C4;
+        constexpr int NIT = (TOTAL + 63) / 64;
+        constexpr int UB = NIT > 8 ? 8 : NIT;   // loads kept in flight per batch
+        static_assert(64 % C4 == 0, "a lane keeps one channel group across its elements");
+        const int c4 = lane % C4;
+        int ci = 0;
+        for (int si = 0; si < a.nsrc; ++si) {
+            const int Cs = a.src[si].C;
+            const __amdgpu_buffer_rsrc_t r_in =
+                make_rsrc(a.src[si].p + (size_t)img * a.Hin * a.Win * Cs, (unsigned)(a.Hin * a.Win * Cs) * 4u);
+            int voff[NIT];
+#pragma unroll
+            for (int i = 0; i < NIT; ++i) {
+                const int e = lane + 64 * i;
+                const int t = e / C4;
+                const int pix = t % NPIX;
+                const int p = (t / NPIX) % PB;
+                const int iy = pix / IW, ix = pix % IW;
+                const int y = pinfo[p * 4 + 1] * S - PAD + iy;
+                const int x = pinfo[p * 4 + 2] * S - PAD + ix;
+                const bool ok = e < TOTAL && pinfo[p * 4 + 3] && y >= 0 && y < a.Hin && x >= 0 && x < a.Win;
+                voff[i] = ok ? ((y * a.Win + x) * Cs + c4 * 4) * 4 : BUF_OOB;
+            }
+            for (int c0 = 0; c0 < Cs; c0 += CK, ++ci) {
+                float *dst = lds + (ci & 1) * TILE + (lane / C4) * CKP + c4 * 4;
+#pragma unroll
+                for (int i0 = 0; i0 < NIT; i0 += UB) {
+                    f32x4 v[UB];
+#pragma unroll
+                    for (int u = 0; u < UB; ++u)
+                        if (i0 + u < NIT) v[u] = buf_load4(r_in, voff[i0 + u], c0 * 4);
+#pragma unroll
+                    for (int u = 0; u < UB; ++u) {
+                        const int i = i0 + u;
+                        if (i < NIT && (64 * (i + 1) <= TOTAL || lane + 64 * i < TOTAL))
+                            *reinterpret_cast<f32x4 *>(dst + i * (64 / C4) * CKP) = v[u];
+                    }
+                }
+                __syncthreads();   // chunk ci is published; consumers are done with chunk ci-1
+            }
+        }
+    } else {
+        f32x16 acc[WTM][WTN];
+#pragma unroll
+        for (int tm = 0; tm < WTM; ++tm)
+#pragma unroll
+            for (int tn = 0; tn < WTN; ++tn)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
+
+        int a_off[WTM];
+#pragma unroll
+        for (int tm = 0; tm < WTM; ++tm)
+            a_off[tm] = ((wm * WTM + tm) * NPIX + ((li >> 3) * S) * IW + (li & 7) * S) * CKP + 4 * g;
+
+        const int Cin4 = a.Cin >> 2;
+        const __amdgpu_buffer_rsrc_t r_w = make_rsrc(a.wpk, (unsigned)(Cfg::KH * Cfg::KW * a.Cin * a.CoutP) * 4u);
+        const int w_lane = (g * a.CoutP + n0 + wn * WTN * 32 + li) * 16;   // bytes
+
+        constexpr int K8 = CK / 8, NS = Cfg::KH * Cfg::KW * K8;
+        auto load_b = [&](f32x4(&dst)[WTN], int kc, int s) {
+            const int tap = s / K8, k8 = s % K8;
+            const int soff = (tap * Cin4 + ((kc + k8 * 8) >> 2)) * a.CoutP * 16;
+#pragma unroll
+            for (int tn = 0; tn < WTN; ++tn) dst[tn] = buf_load4(r_w, w_lane + tn * 32 * 16, soff);
+        };
+        f32x4 bcur[WTN];
+        load_b(bcur, 0, 0);
+        const EpiCoef<WTN> coef = conv_epi_coef<WN, WTN, false>(a, n0, wn, li);
+        const int nch = a.Cin / CK;
+        __syncthreads();   // chunk 0 staged
+        for (int ci = 0; ci < nch; ++ci) {
+            const float *tile = lds + (ci & 1) * TILE;
+            auto load_a = [&](f32x4(&dst)[WTM], int s) {
+                const int tap = s / K8, k8 = s % K8;
+#pragma unroll
+                for (int tm = 0; tm < WTM; ++tm)
+                    dst[tm] = *reinterpret_cast<const f32x4 *>(
+                        &tile[a_off[tm] + ((tap / Cfg::KW) * IW + (tap % Cfg::KW)) * CKP + k8 * 8]);
+            };
+            const int kc = ci * CK;
+            const int kc_next = (ci + 1 < nch) ? kc + CK : kc;
+            f32x4 acur[WTM];
+            load_a(acur, 0);
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                f32x4 anext[WTM], bnext[WTN];
+                if (s + 1 < NS) {
+                    load_a(anext, s + 1);
+                    load_b(bnext, kc, s + 1);
+                } else {
+                    load_b(bnext, kc_next, 0);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int tm = 0; tm < WTM; ++tm)
+#pragma unroll
+                        for (int tn = 0; tn < WTN; ++tn)
+                            acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(
+                                acur[tm][j], bcur[tn][j], acc[tm][tn], 0, 0, 0);
+                if (s + 1 < NS) {
+#pragma unroll
+                    for (int tm = 0; tm < WTM; ++tm) acur[tm] = anext[tm];
+                }
+#pragma unroll
+                for (int tn = 0; tn < WTN; ++tn) bcur[tn] = bnext[tn];
+            }
+            if (ci + 1 < nch) __syncthreads();   // chunk ci+1 staged, chunk ci released
+        }
+        conv_epilogue<WM, WN, WTM, WTN, BNT>(a, acc, pinfo, chunk * PB, img, n0, wm, wn, g, li, coef);
+    }
+}
+
+// ---- dispatch
+template <int KS, int S, int CK, class Sh, bool BM = false>
+static hipError_t launch_one(ConvArgs a, hipStream_t st, ConvArgs *resolved) {
+    using Cfg = ConvCfg<KS, S, CK, Sh::WM, Sh::WN, Sh::WTM, Sh::WTN>;
+    static_assert(Cfg::PB == Sh::PB && Cfg::BNT == Sh::BNT, "the shape table and the kernel agree on the tile");
     if constexpr (!BM && S == 1 && (KS == 3 || KS == 1)) {
         // backward-statistics epilogue (ConvArgs::bm_y): its own instantiation, so that every other launch keeps the
         // lean epilogue (the y / z loads cost ~25 VGPRs)
-        if (a.bm_y) return launch_one<KS, S, CK, WM, WN, WTM, WTN, true>(a, st, resolved);
+        if (a.bm_y) return launch_one<KS, S, CK, Sh, true>(a, st, resolved);
     } else if constexpr (!BM) {
         if (a.bm_y) return hipErrorInvalidValue;
     }
-    a.ppr = (a.Wout + 7) / 8;
-    a.ppi = a.ppr * ((a.Hout + 3) / 4);
-    a.chunks = (a.ppi + Cfg::PB - 1) / Cfg::PB;
+    conv_set_patches(a, Cfg::PB);
     if (a.CoutP % Cfg::BNT) return hipErrorInvalidValue;
     if (resolved) *resolved = a;
-    static DynLdsOnce attr_set;
-    auto kern = conv_mfma_kernel<KS, S, CK, WM, WN, WTM, WTN, BM>;
-    {
-        const hipError_t e = attr_set.ensure(reinterpret_cast<const void *>(kern), (int)(Cfg::LDS_BYTES));
-        if (e != hipSuccess) return e;
-    }
-    const int ntiles = a.CoutP / Cfg::BNT;
-    dim3 grid((unsigned)(a.B * a.chunks * ntiles));
-    hipLaunchKernelGGL(kern, grid, dim3(Cfg::NT), Cfg::LDS_BYTES, st, a);
-    return hipGetLastError();
+    return launch_dyn_lds<conv_mfma_kernel<KS, S, CK, Sh::WM, Sh::WN, Sh::WTM, Sh::WTN, BM>>(
+        Cfg::LDS_BYTES, dim3((unsigned)(a.B * a.chunks * (a.CoutP / Cfg::BNT))), dim3(Cfg::NT), st, a);
 }
 
-template <int KS, int S, int CK, int WM, int WN, int WTM, int WTN>
+template <int KS, int S, int CK, class Sh>
 static hipError_t launch_one_ws(ConvArgs a, hipStream_t st, ConvArgs *resolved) {
-    using Cfg = ConvCfgWS<KS, S, CK, WM, WN, WTM, WTN>;
-    if (Cfg::LDS_BYTES > 160 * 1024) return hipErrorInvalidValue;
-    a.ppr = (a.Wout + 7) / 8;
-    a.ppi = a.ppr * ((a.Hout + 3) / 4);
-    a.chunks = (a.ppi + Cfg::PB - 1) / Cfg::PB;
+    using Cfg = ConvCfgWS<KS, S, CK, Sh::WM, Sh::WN, Sh::WTM, Sh::WTN>;
+    static_assert(Cfg::PB == Sh::PB && Cfg::BNT == Sh::BNT, "the shape table and the kernel agree on the tile");
+    conv_set_patches(a, Cfg::PB);
     if (a.CoutP % Cfg::BNT) return hipErrorInvalidValue;
     if (resolved) *resolved = a;
-    static DynLdsOnce attr_set;
-    auto kern = conv_mfma_ws_kernel<KS, S, CK, WM, WN, WTM, WTN>;
-    {
-        const hipError_t e = attr_set.ensure(reinterpret_cast<const void *>(kern), (int)(Cfg::LDS_BYTES));
-        if (e != hipSuccess) return e;
-    }
-    const int ntiles = a.CoutP / Cfg::BNT;
-    dim3 grid((unsigned)(a.B * a.chunks * ntiles));
-    hipLaunchKernelGGL(kern, grid, dim3(Cfg::NT), Cfg::LDS_BYTES, st, a);
-    return hipGetLastError();
+    return launch_dyn_lds<conv_mfma_ws_kernel<KS, S, CK, Sh::WM, Sh::WN, Sh::WTM, Sh::WTN>>(
+        Cfg::LDS_BYTES, dim3((unsigned)(a.B * a.chunks * (a.CoutP / Cfg::BNT))), dim3(Cfg::NT), st, a);
 }
 
 template <int KS, int S, int CK>
 static hipError_t launch_shape(const ConvArgs &a, hipStream_t st, ConvArgs *resolved) {
-    if constexpr (KS == 3 || KS == 1) if ((a.cfg & CFG_WS) && !a.bm_y) {   // (the WS variant has no bm epilogue)
-        switch (a.cfg & ~CFG_WS) {
-            case CFG_128x128: return launch_one_ws<KS, S, CK, 2, 2, 2, 2>(a, st, resolved);
-            case CFG_128x64: return launch_one_ws<KS, S, CK, 2, 2, 2, 1>(a, st, resolved);
-            case CFG_128x64m: return launch_one_ws<KS, S, CK, 4, 1, 1, 2>(a, st, resolved);
-            case CFG_128x32: return launch_one_ws<KS, S, CK, 4, 1, 1, 1>(a, st, resolved);
-            case CFG_64x128: return launch_one_ws<KS, S, CK, 1, 4, 2, 1>(a, st, resolved);
-            case CFG_64x64: return launch_one_ws<KS, S, CK, 2, 2, 1, 1>(a, st, resolved);
-            default: return hipErrorInvalidValue;
-        }
-    }
-    switch (a.cfg & ~CFG_WS) {
-        case CFG_128x128: return launch_one<KS, S, CK, 2, 2, 2, 2>(a, st, resolved);
-        case CFG_128x64: return launch_one<KS, S, CK, 2, 2, 2, 1>(a, st, resolved);
-        case CFG_128x64m: return launch_one<KS, S, CK, 4, 1, 1, 2>(a, st, resolved);
-        case CFG_128x32: return launch_one<KS, S, CK, 4, 1, 1, 1>(a, st, resolved);
-        case CFG_64x128: return launch_one<KS, S, CK, 1, 4, 2, 1>(a, st, resolved);
-        case CFG_64x64: return launch_one<KS, S, CK, 2, 2, 1, 1>(a, st, resolved);
-        default: return hipErrorInvalidValue;
-    }
+    if (a.cfg & ~(CFG_SHAPE_BITS | CFG_WS)) return hipErrorInvalidValue;
+    return with_conv_shape(a.cfg, [&](auto sh) {
+        using Sh = decltype(sh);
+        if constexpr (KS == 3 || KS == 1)
+            if ((a.cfg & CFG_WS) && !a.bm_y) return launch_one_ws<KS, S, CK, Sh>(a, st, resolved);   // (the WS variant has no bm epilogue)
+        return launch_one<KS, S, CK, Sh>(a, st, resolved);
+    });
 }
 
 int conv_pick_cfg(int Cout, int CoutP, int ks, int stride, int B, int Hout, int Wout) {
@@ -106,8 +391,7 @@ bool conv_lazy_capable(const ConvArgs &a, int ks, int stride) {
 
 hipError_t launch_conv(const ConvArgs &a_in, int ks, int stride, hipStream_t st, ConvArgs *resolved) {
     ConvArgs a = a_in;
-    bool lazy = false;
-    for (int i = 0; i < a.nsrc; ++i) lazy |= a.src[i].la != nullptr;
+    const bool lazy = conv_any_lazy(a);
     const bool dense_out = a.o_px == 0;
     if (dense_out) { a.o_px = a.out_ld; a.o_row = a.Wout * a.out_ld; a.o_img = a.Hout * a.Wout * a.out_ld; }
     if (a.r_px == 0) { a.r_px = a.res_ld; a.r_row = a.Wout * a.res_ld; a.r_img = a.Hout * a.Wout * a.res_ld; }
@@ -120,9 +404,8 @@ hipError_t launch_conv(const ConvArgs &a_in, int ks, int stride, hipStream_t st,
     if (a.cfg == CFG_SMALL) {
         if (!conv_small_ok(a, ks, stride)) return hipErrorInvalidValue;
         if (lazy && !conv_thin_ok(a, ks, stride) && !conv_small_lazy_ok(a, ks, stride)) return hipErrorInvalidValue;
-        a.ppr = (a.Wout + 7) / 8;
-        a.ppi = a.ppr * ((a.Hout + 3) / 4);
-        a.chunks = a.Hout;
+        conv_set_patches(a, 1);
+        a.chunks = a.Hout;      // (the row kernel: one statistics partial per output row)
         if (resolved) *resolved = a;
         prof_last = conv_cost(a, ks);
         return launch_conv_small(a, stride, st);
@@ -137,19 +420,13 @@ hipError_t launch_conv(const ConvArgs &a_in, int ks, int stride, hipStream_t st,
     }
     if (a.prec >= 1 && conv_bf16_ok(a, ks, stride)) return launch_conv_bf16(a, ks, stride, st, resolved);
     if (lazy) return hipErrorInvalidValue;      // (nor do the fp32 MFMA kernels)
-    if (ks == 3 && stride == 1) {
-        return ck == 32 ? launch_shape<3, 1, 32>(a, st, resolved) : launch_shape<3, 1, 16>(a, st, resolved);
-    } else if (ks == 3 && stride == 2) {
-        return launch_shape<3, 2, 16>(a, st, resolved);
-    } else if (ks == 1 && stride == 1) {
-        return ck == 32 ? launch_shape<1, 1, 32>(a, st, resolved) : launch_shape<1, 1, 16>(a, st, resolved);
-    } else if (stride == 1 && (ks == 12 || ks == 21 || ks == 22)) {   // stride-2 data-gradient parity classes
-        if (a.cfg & CFG_WS) a.cfg &= ~CFG_WS;
-        if (ks == 12) return ck == 32 ? launch_shape<12, 1, 32>(a, st, resolved) : launch_shape<12, 1, 16>(a, st, resolved);
-        if (ks == 21) return ck == 32 ? launch_shape<21, 1, 32>(a, st, resolved) : launch_shape<21, 1, 16>(a, st, resolved);
-        return ck == 32 ? launch_shape<22, 1, 32>(a, st, resolved) : launch_shape<22, 1, 16>(a, st, resolved);
-    }
-    return hipErrorInvalidValue;
+    if (ks >= 10) a.cfg &= ~CFG_WS;      // the stride-2 data-gradient parity classes have no wave-specialised build
+    return with_conv_window(ks, stride, [&](auto win) {
+        constexpr int KS = decltype(win)::KS, S = decltype(win)::S;
+        if constexpr (!(KS == 3 && S == 2))      // (conv_ck: a stride-2 3x3 always stages 16-channel chunks)
+            if (ck == 32) return launch_shape<KS, S, 32>(a, st, resolved);
+        return launch_shape<KS, S, 16>(a, st, resolved);
+    });
 }
 
 }  // namespace mc

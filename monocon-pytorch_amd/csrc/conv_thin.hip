@@ -671,13 +671,7 @@ bool wgrad_thin_ok(const WgradArgs &a, int ks, int stride) {
 
 hipError_t launch_wgrad_thin(const WgradArgs &a, hipStream_t st) {
     const size_t lds = 2 * WT_PLANE + 9 * 4 * 64 * sizeof(float);
-    static DynLdsOnce attr_set;
-    {
-        const hipError_t e = attr_set.ensure(reinterpret_cast<const void *>(wgrad_thin16_kernel), (int)(lds));
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(wgrad_thin16_kernel, dim3(a.ksplit), dim3(256), lds, st, a);
-    return hipGetLastError();
+    return launch_dyn_lds<wgrad_thin16_kernel>(lds, dim3(a.ksplit), dim3(256), st, a);
 }
 
 }  // namespace mc

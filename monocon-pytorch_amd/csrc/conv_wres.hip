@@ -476,22 +476,14 @@ bool conv_wres_ok(const ConvArgs &a, int ks, int stride) {
 
 template <bool BM, bool RES, bool STATS, bool ZMASK, int EXP = 0, bool LZ = false>
 static hipError_t launch_wres_one(const ConvArgs &a, int tpr, int tpi, int total, int per_wg, int ngroups, int nwg, hipStream_t st) {
-    auto kern = conv_wres_kernel<BM, RES, STATS, ZMASK, EXP, LZ>;
-    static DynLdsOnce attr_set;
-    {
-        const hipError_t e = attr_set.ensure(reinterpret_cast<const void *>(kern), (int)(WresCfg::LDS_BYTES));
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)(nwg * ngroups)), dim3(256), WresCfg::LDS_BYTES, st, a, tpr, tpi, total, per_wg, ngroups);
-    return hipGetLastError();
+    return launch_dyn_lds<conv_wres_kernel<BM, RES, STATS, ZMASK, EXP, LZ>>(WresCfg::LDS_BYTES, dim3((unsigned)(nwg * ngroups)), dim3(256), st,
+                                                                            a, tpr, tpi, total, per_wg, ngroups);
 }
 
 hipError_t launch_conv_wres(const ConvArgs &a_in, int ks, int stride, hipStream_t st, ConvArgs *resolved) {
     if (!conv_wres_ok(a_in, ks, stride)) return hipErrorInvalidValue;
     ConvArgs a = a_in;
-    a.ppr = (a.Wout + 7) / 8;
-    a.ppi = a.ppr * ((a.Hout + 3) / 4);
-    a.chunks = a.ppi;
+    conv_set_patches(a, 1);
     if (resolved) *resolved = a;
     const int tpr = (a.Wout + 15) / 16, tpi = tpr * (a.Hout / 4), total = a.B * tpi, ngroups = a.CoutP / 64;
     // one workgroup per CU and column group where the work allows (>= 8 tiles each: the weight prologue is ~2 tiles of time)

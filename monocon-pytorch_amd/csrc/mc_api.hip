@@ -331,8 +331,7 @@ int mc_choose_conv_cfg(mc_handle *h, const ConvArgs &a_in, int ks, int stride) {
     int heuristic = small_ok ? (int)CFG_SMALL : conv_pick_cfg(a_in.Cout, a_in.CoutP, ks, stride, a_in.B, a_in.Hout, a_in.Wout);
     if (!h->autotune) return heuristic;
     const bool b16 = a_in.prec >= 1 && conv_bf16_ok(a_in, ks, stride);
-    bool lazy = false;      // lazy sources (ConvSrc::la) stage differently: their own entry
-    for (int i = 0; i < a_in.nsrc; ++i) lazy |= a_in.src[i].la != nullptr;
+    const bool lazy = conv_any_lazy(a_in);      // lazy sources (ConvSrc::la) stage differently: their own entry
     std::vector<int> key = {a_in.B, a_in.Hin, a_in.Win, ks, stride, a_in.Cout, a_in.CoutP, a_in.nsrc,
                             (a_in.res ? 1 : 0) | (b16 ? 2 * a_in.prec : 0) | (lazy ? 64 : 0)};
     for (int i = 0; i < a_in.nsrc; ++i) key.push_back(a_in.src[i].C);
@@ -1240,9 +1239,10 @@ int mc_bench_conv(mc_handle *h, int B, int Hin, int Win, int nsrc, const int src
 
 int mc_set_conv_cfg(mc_handle *h, int cfg) {
     if (!h) return -1;
-    if (cfg != CFG_SMALL && (cfg < 0 || (cfg & 15) >= CFG_COUNT || (cfg & ~(15 | CFG_WS | CFG_WRES))))
+    const int shape_bits = cfg & CFG_SHAPE_BITS;
+    if (cfg != CFG_SMALL && (cfg < 0 || (shape_bits && !conv_shape(cfg).id) || (cfg & ~(CFG_SHAPE_BITS | CFG_WS | CFG_WRES))))
         return fail(h, "mc_set_conv_cfg: unknown shape id");
-    if ((cfg & (CFG_WS | CFG_WRES)) && !(cfg & 15)) return fail(h, "mc_set_conv_cfg: the kernel-variant flags need a shape");
+    if ((cfg & (CFG_WS | CFG_WRES)) && !shape_bits) return fail(h, "mc_set_conv_cfg: the kernel-variant flags need a shape");
     h->force_cfg = cfg;
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipDeviceSynchronize());
@@ -1282,8 +1282,8 @@ int mc_tune_import(mc_handle *h, const int *buf, int n_ints) {
         std::vector<int> key(buf + o, buf + o + kl);
         o += kl;
         const int cfg = buf[o++];
-        // (a shape id is CFG_SMALL, or a tiling 1 .. CFG_COUNT - 1 with optional kernel-variant flags: a flag alone is no shape)
-        if (cfg != CFG_SMALL && (cfg <= 0 || (cfg & 15) < 1 || (cfg & 15) >= CFG_COUNT || (cfg & ~(15 | CFG_WS | CFG_WRES))))
+        // (a shape id is CFG_SMALL, or an entry of CONV_SHAPES with optional kernel-variant flags: a flag alone is no shape)
+        if (cfg != CFG_SMALL && (cfg <= 0 || !conv_shape(cfg).id || (cfg & ~(CFG_SHAPE_BITS | CFG_WS | CFG_WRES))))
             return fail(h, "mc_tune_import: unknown shape id %d", cfg);
         // a tiling whose column tile does not divide the signature's padded column count (key[6]) has no launch: every
         // dispatch refuses it -- but only when the plan RUNS, after the launches in front of it.  Refused here instead.

@@ -488,12 +488,8 @@ struct TB {   // train plan builder
             for (int i = 0; i < a.nsrc; ++i) a.amax_in[i] = ts->nodes[srcs[i]].t.amax;
             a.amax_w = Lr.w_amax;
         }
-        {
-            bool any_lazy = false;
-            for (int i = 0; i < a.nsrc; ++i) any_lazy |= a.src[i].la != nullptr;
-            if (any_lazy && !conv_lazy_capable(a, Lr.ks, Lr.stride)) {
-                for (int i = 0; i < a.nsrc; ++i) { materialise(srcs[i]); fill_src(a.src[i], srcs[i]); }
-            }
+        if (conv_any_lazy(a) && !conv_lazy_capable(a, Lr.ks, Lr.stride)) {
+            for (int i = 0; i < a.nsrc; ++i) { materialise(srcs[i]); fill_src(a.src[i], srcs[i]); }
         }
         unsigned *yslot = lazy ? slot() : nullptr;      // max |y|, left by the conv's epilogue: bn_finalize bounds max |z| with it
         a.amax_out = yslot;
@@ -658,9 +654,7 @@ struct TB {   // train plan builder
         a.dy = dy.p; a.dy_ld = dy_ld;
         a.prec = h->prec;
         wgrad_plan(a, ks, stride);
-        bool any_lazy = false;
-        for (int i = 0; i < a.nsrc; ++i) any_lazy |= a.src[i].la != nullptr;
-        if (any_lazy && !wgrad_lazy_capable(a, ks, stride)) {      // X is read by a kernel that cannot form it: store it after all
+        if (wgrad_any_lazy(a) && !wgrad_lazy_capable(a, ks, stride)) {      // X is read by a kernel that cannot form it: store it after all
             for (int s_ : srcs) materialise(s_);
             fill();
         }

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cstdlib>
 #include <vector>
 
 #include "conv_mfma.h"
@@ -209,6 +210,33 @@ struct WgradArgs {
     int pipe;                 // != 0: the software-pipelined fp16-split kernel (wgrad_pipe.hip) with this tile; ksplit = slices
     const unsigned *amax_x[4], *amax_dy;   // prec 3: max |x| (bit patterns) of every source and of dY (see ConvArgs::amax_in)
 };
+// the patch grid of dY (WgradArgs::ppr / ppi) and the staged pixel groups per image of a kernel that stages pb patches
+inline void wgrad_set_patches(WgradArgs &a, int pb) {
+    a.ppr = (a.Wout + 7) / 8;
+    a.ppi = a.ppr * ((a.Hout + 3) / 4);
+    a.groups_per_img = (a.ppi + pb - 1) / pb;
+}
+inline bool wgrad_any_lazy(const WgradArgs &a) { return any_lazy_src(a.src, a.nsrc); }
+// The (WN, WC) wave grid wgrad_shape() planned, as a type: f(WgTile<WN, WC>{}) -- 64n x 64c, 128n x 32c, 64n x 32c, 32n x 32c.
+template <int WN_, int WC_>
+struct WgTile { static constexpr int WN = WN_, WC = WC_; };
+template <typename F>
+inline hipError_t with_wgrad_tile(int WN, int WC, F &&f) {
+    if (WN == 2 && WC == 2) return f(WgTile<2, 2>{});
+    if (WN == 4) return f(WgTile<4, 1>{});
+    if (WN == 2) return f(WgTile<2, 1>{});
+    return f(WgTile<1, 1>{});
+}
+// the dynamic LDS request of a weight-gradient kernel that needs `need` bytes.  Experiment knob (only with -DMC_DEBUG_HOOKS):
+// MONOCON_HIP_WGRAD_LDS_KB pads the request, i.e. caps the workgroups per CU
+inline size_t wgrad_lds_request(size_t need) {
+#ifdef MC_DEBUG_HOOKS
+    static const size_t pad = [] { const char *e = std::getenv("MONOCON_HIP_WGRAD_LDS_KB"); return e ? (size_t)std::atoi(e) * 1024 : (size_t)0; }();
+    return pad > need ? pad : need;
+#else
+    return need;
+#endif
+}
 void wgrad_plan(WgradArgs &a, int ks, int stride);            // fills the tiling fields
 size_t wgrad_partial_floats(const WgradArgs &a, int ks);
 hipError_t launch_wgrad(const WgradArgs &a, int ks, int stride, float *dw_oihw, hipStream_t st);

@@ -401,31 +401,13 @@ static hipError_t launch_wg16(const WgradArgs &a, hipStream_t st) {
     using Cfg = WgB16Cfg<KS, S, WN, WC, SPL>;
     if (a.pb != Cfg::PB) return hipErrorInvalidValue;
     if constexpr (!LZ) {
-        for (int i = 0; i < a.nsrc; ++i)
-            if (a.src[i].la) {
-                if constexpr (SPL == 2) return launch_wg16<KS, S, WN, WC, SPL, true>(a, st);
-                else return hipErrorInvalidValue;
-            }
+        if (wgrad_any_lazy(a)) {
+            if constexpr (SPL == 2) return launch_wg16<KS, S, WN, WC, SPL, true>(a, st);
+            else return hipErrorInvalidValue;
+        }
     }
-    auto kern = wgrad_bf16_kernel<KS, S, WN, WC, SPL, LZ>;
-    static DynLdsOnce attr_set;
-    // experiment knob (only with -DMC_DEBUG_HOOKS): MONOCON_HIP_WGRAD_LDS_KB pads the dynamic LDS request, i.e. caps the
-    // workgroups per CU
-    static const size_t lds_req = [] {
-#ifdef MC_DEBUG_HOOKS
-        const char *e = std::getenv("MONOCON_HIP_WGRAD_LDS_KB");
-        const size_t pad = e ? (size_t)std::atoi(e) * 1024 : 0;
-        return pad > Cfg::LDS_BYTES ? pad : (size_t)Cfg::LDS_BYTES;
-#else
-        return (size_t)Cfg::LDS_BYTES;
-#endif
-    }();
-    {
-        const hipError_t e = attr_set.ensure(reinterpret_cast<const void *>(kern), (int)(lds_req));
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kern, dim3(a.ksplit * a.n_tiles * a.c_tiles), dim3(Cfg::NT), lds_req, st, a);
-    return hipGetLastError();
+    return launch_dyn_lds<wgrad_bf16_kernel<KS, S, WN, WC, SPL, LZ>>(wgrad_lds_request(Cfg::LDS_BYTES), dim3(a.ksplit * a.n_tiles * a.c_tiles),
+                                                                     dim3(Cfg::NT), st, a);
 }
 
 bool wgrad_bf16_ok(const WgradArgs &a, int ks, int stride) {
@@ -455,15 +437,12 @@ int wgrad_bf16_patches(int prec) { return prec >= 2 ? 1 : 2; }
 // the main kernel of launch_wgrad in the bf16-pipe modes (the split-K reduce is shared); WN / WC as planned
 template <int SPL>
 static hipError_t launch_wgrad_b16_spl(const WgradArgs &a, int ks, int stride, int WN, int WC, hipStream_t st) {
-#define WG16(KS_, S_)                                                        \
-    if (WN == 2 && WC == 2) return launch_wg16<KS_, S_, 2, 2, SPL>(a, st);   \
-    if (WN == 4) return launch_wg16<KS_, S_, 4, 1, SPL>(a, st);              \
-    if (WN == 2) return launch_wg16<KS_, S_, 2, 1, SPL>(a, st);              \
-    return launch_wg16<KS_, S_, 1, 1, SPL>(a, st);
-    if (ks == 3 && stride == 2) { WG16(3, 2) }
-    if (ks == 3) { WG16(3, 1) }
-    WG16(1, 1)
-#undef WG16
+    return with_wgrad_tile(WN, WC, [&](auto t) {
+        constexpr int N = decltype(t)::WN, C = decltype(t)::WC;
+        if (ks == 3 && stride == 2) return launch_wg16<3, 2, N, C, SPL>(a, st);
+        if (ks == 3) return launch_wg16<3, 1, N, C, SPL>(a, st);
+        return launch_wg16<1, 1, N, C, SPL>(a, st);
+    });
 }
 hipError_t launch_wgrad_bf16(const WgradArgs &a, int ks, int stride, int WN, int WC, hipStream_t st) {
     if (a.prec == 3) return launch_wgrad_b16_spl<2>(a, ks, stride, WN, WC, st);

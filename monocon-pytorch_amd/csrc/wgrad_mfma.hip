@@ -373,25 +373,8 @@ static bool wgrad_is_small(const WgradArgs &a, int ks, int stride) {
 template <int KS, int S, int WN, int WC>
 static hipError_t launch_wg(WgradArgs a, hipStream_t st) {
     using Cfg = WgCfg<KS, S, WN, WC>;
-    auto kern = wgrad_mfma_kernel<KS, S, WN, WC>;
-    static DynLdsOnce attr_set;
-    // experiment knob (only with -DMC_DEBUG_HOOKS): MONOCON_HIP_WGRAD_LDS_KB pads the dynamic LDS request, i.e. caps the
-    // workgroups per CU
-    static const size_t lds_req = [] {
-#ifdef MC_DEBUG_HOOKS
-        const char *e = std::getenv("MONOCON_HIP_WGRAD_LDS_KB");
-        const size_t pad = e ? (size_t)std::atoi(e) * 1024 : 0;
-        return pad > Cfg::LDS_BYTES ? pad : (size_t)Cfg::LDS_BYTES;
-#else
-        return (size_t)Cfg::LDS_BYTES;
-#endif
-    }();
-    {
-        const hipError_t e = attr_set.ensure(reinterpret_cast<const void *>(kern), (int)(lds_req));
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kern, dim3(a.ksplit * a.n_tiles * a.c_tiles), dim3(Cfg::NT), lds_req, st, a);
-    return hipGetLastError();
+    return launch_dyn_lds<wgrad_mfma_kernel<KS, S, WN, WC>>(wgrad_lds_request(Cfg::LDS_BYTES), dim3(a.ksplit * a.n_tiles * a.c_tiles),
+                                                            dim3(Cfg::NT), st, a);
 }
 
 // shape choice: 64n x 64c (2x2 waves) wherever both dimensions allow, 128 x 32 for thin inputs, single-wave tiles for <= 32
@@ -426,10 +409,8 @@ void wgrad_plan(WgradArgs &a, int ks, int stride) {
     wgrad_shape(a, &WN, &WC);
     a.n_tiles = (a.Cout + 32 * WN - 1) / (32 * WN);
     a.c_tiles = (a.Cin + 32 * WC - 1) / (32 * WC);
-    a.ppr = (a.Wout + 7) / 8;
-    a.ppi = a.ppr * ((a.Hout + 3) / 4);
     a.pb = (a.prec >= 1 && wgrad_bf16_ok(a, ks, stride)) ? wgrad_bf16_patches(a.prec) : 2;
-    a.groups_per_img = (a.ppi + a.pb - 1) / a.pb;
+    wgrad_set_patches(a, a.pb);
     const long long G = (long long)a.B * a.groups_per_img;
     // two resident 4-wave workgroups per CU (MONOCON_HIP_WGRAD_BLOCKS: experiment knob, e.g. 256 = one per CU, which
     // leaves half of every SIMD's registers to whatever the main stream runs beside it)
@@ -450,8 +431,7 @@ bool wgrad_lazy_capable(const WgradArgs &a, int ks, int stride) {
 }
 
 hipError_t launch_wgrad(const WgradArgs &a, int ks, int stride, float *dw_oihw, hipStream_t st) {
-    for (int i = 0; i < a.nsrc; ++i)
-        if (a.src[i].la && !wgrad_lazy_capable(a, ks, stride)) return hipErrorInvalidValue;
+    if (wgrad_any_lazy(a) && !wgrad_lazy_capable(a, ks, stride)) return hipErrorInvalidValue;
     prof_last = {2, 2.0 * a.B * a.Hout * a.Wout * (double)a.Cout * a.Cin * ks * ks,
                  4.0 * ((double)a.B * a.Hin * a.Win * a.Cin + (double)a.B * a.Hout * a.Wout * a.Cout + (double)ks * ks * a.Cin * a.Cout)};
     hipError_t e = hipErrorInvalidValue;
@@ -476,15 +456,13 @@ hipError_t launch_wgrad(const WgradArgs &a, int ks, int stride, float *dw_oihw, 
         if (a.prec >= 1 && wgrad_bf16_ok(a, ks, stride)) {
             e = launch_wgrad_bf16(a, ks, stride, WN, WC, st);
         } else {
-#define WG_DISPATCH(KS_, S_)                                                     \
-    if (WN == 4) e = launch_wg<KS_, S_, 4, 1>(a, st);                            \
-    else if (WN == 2 && WC == 2) e = launch_wg<KS_, S_, 2, 2>(a, st);            \
-    else if (WN == 2) e = launch_wg<KS_, S_, 2, 1>(a, st);                       \
-    else e = launch_wg<KS_, S_, 1, 1>(a, st);
-        if (ks == 3 && stride == 1) { WG_DISPATCH(3, 1) }
-        else if (ks == 3 && stride == 2) { WG_DISPATCH(3, 2) }
-        else if (ks == 1 && stride == 1) { WG_DISPATCH(1, 1) }
-#undef WG_DISPATCH
+            e = with_wgrad_tile(WN, WC, [&](auto t) {
+                constexpr int N = decltype(t)::WN, C = decltype(t)::WC;
+                if (ks == 3 && stride == 1) return launch_wg<3, 1, N, C>(a, st);
+                if (ks == 3 && stride == 2) return launch_wg<3, 2, N, C>(a, st);
+                if (ks == 1 && stride == 1) return launch_wg<1, 1, N, C>(a, st);
+                return hipErrorInvalidValue;
+            });
         }
     }
     if (e != hipSuccess) return e;

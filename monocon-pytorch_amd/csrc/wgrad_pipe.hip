@@ -327,22 +327,14 @@ template <int KS, int WN, int WC, int WK, bool LZ = false>
 static hipError_t launch_wp(const WgradArgs &a, hipStream_t st) {
     using Cfg = WgPipeCfg<KS, WN, WC, WK>;
     if constexpr (!LZ) {
-        for (int i = 0; i < a.nsrc; ++i)
-            if (a.src[i].la) {
-                if constexpr (WN == 2 && WC == 2 && WK == 1) return launch_wp<KS, WN, WC, WK, true>(a, st);      // (the default tile)
-                else return hipErrorInvalidValue;
-            }
+        if (wgrad_any_lazy(a)) {
+            if constexpr (WN == 2 && WC == 2 && WK == 1) return launch_wp<KS, WN, WC, WK, true>(a, st);      // (the default tile)
+            else return hipErrorInvalidValue;
+        }
     }
-    auto kern = wgrad_pipe_kernel<KS, WN, WC, WK, LZ>;
     constexpr size_t lds_bytes = Cfg::LDS_BYTES + (LZ ? 2 * (Cfg::CB / 4) * 16 : 0);      // (+ the lazy coefficient table)
-    static DynLdsOnce attr_set;
-    {
-        const hipError_t e = attr_set.ensure(reinterpret_cast<const void *>(kern), (int)(lds_bytes));
-        if (e != hipSuccess) return e;
-    }
     if (a.ksplit % WK) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(kern, dim3((a.ksplit / WK) * a.n_tiles * a.c_tiles), dim3(Cfg::NT), lds_bytes, st, a);
-    return hipGetLastError();
+    return launch_dyn_lds<wgrad_pipe_kernel<KS, WN, WC, WK, LZ>>(lds_bytes, dim3((a.ksplit / WK) * a.n_tiles * a.c_tiles), dim3(Cfg::NT), st, a);
 }
 
 // tile of the pipelined kernel for this layer (0: not eligible): 1 = 128n x 64c, 2 = 64n x 128c, 3 = 64n x 64c (two K halves)
@@ -381,9 +373,7 @@ void wgrad_pipe_plan(WgradArgs &a, int tile) {
     a.pb = 1;
     a.n_tiles = (a.Cout + NB - 1) / NB;
     a.c_tiles = (a.Cin + CB - 1) / CB;
-    a.ppr = (a.Wout + 7) / 8;
-    a.ppi = a.ppr * ((a.Hout + 3) / 4);
-    a.groups_per_img = a.ppi;
+    wgrad_set_patches(a, a.pb);
     const long long G = (long long)a.B * a.groups_per_img;
     // (read per plan, not cached: the tests shrink it to run long pixel loops on small inputs)
     const char *eb = std::getenv("MONOCON_HIP_WGRAD_PIPE_BLOCKS");

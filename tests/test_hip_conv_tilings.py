@@ -12,7 +12,8 @@ waiting for timing noise to select it:
 2. whole plans through the tune table (`build_train_plan` + `tune_export`, rewritten, `tune_import` on a fresh handle): the
    train step at (2, 96, 160) and the eval forward at (2, 64, 128), every tiling against the 128x32 run, which is held to the
    oracle / the golden.  The table must come back unchanged (a grown table = some launch was tuned instead of dictated).
-3. a table naming a tiling whose column tile does not divide the layer's padded column count is refused as a whole.
+3. a table naming a tiling whose column tile does not divide the layer's padded column count is refused as a whole, and so
+   is every id without an entry in the table of tilings (the retired 2 and 3), by `set_conv_cfg` and `tune_import` alike.
 
 Covered by the whole-plan matrix (checked by test_plan_matrix_covers_every_conv_class and the twin-line assertion of every
 run; "BM" = backward-statistics epilogue twins, "LZ" = lazy-source staging, reached with MONOCON_HIP_LAZY_Z=3 /
@@ -48,7 +49,7 @@ from test_hip_train_step import build, check_step_vs_oracle, oracle_step_referen
 pytestmark = pytest.mark.gpu
 
 MODES = {0: "fp32", 1: "bf16", 2: "bf16x3", 3: "f16x2"}
-TILINGS = (1, 4, 5, 6, 7, 8)                       # (2 and 3 are retired in the dispatch)
+TILINGS = (1, 4, 5, 6, 7, 8)                       # (2 and 3 are retired: no entry in CONV_SHAPES, refused as shape ids)
 BNT = {1: 128, 4: 64, 5: 64, 6: 32, 7: 128, 8: 64}    # column tile of a shape: WN * WTN * 32 of conv_shape() (conv_mfma.h)
 CFG_WS, CFG_SMALL, CFG_WRES = 16, 32, 64
 
@@ -492,3 +493,22 @@ def test_a_table_naming_an_indivisible_tiling_is_refused_whole(golden_sd, monkey
     del m, eng
     run = dictated_step(golden_sd, "fp32", dictate(entries, 6), capfd)
     assert torch.equal(run["losses"], base["losses"]) and torch.equal(run["grads"], base["grads"])
+
+
+def test_the_retired_ids_are_no_shape_ids():
+    """ids 2 and 3 (256x64, 256x32) have no entry in CONV_SHAPES (conv_mfma.h): mc_set_conv_cfg and mc_tune_import refuse them
+    as they refuse any unknown id, on the host and before anything is built -- not at the first launch of a plan"""
+    from hipmonocon.engine import Engine
+    from hipmonocon.lib import MonoconHipError
+    eng = Engine(0)
+    key = (2, 96, 160, 3, 1, 64, 64, 1, 0, 64)        # B, Hin, Win, ks, stride, Cout, CoutP, nsrc, flags, C_0
+    for cfg in (2, 3, 2 | CFG_WS):
+        with pytest.raises(MonoconHipError, match="unknown shape id"):
+            eng.set_conv_cfg(cfg)
+    with pytest.raises(MonoconHipError, match="unknown shape id"):
+        eng.tune_import(flat_table([(key, 2)]))
+    assert eng.tune_export() == []
+    eng.set_conv_cfg(6)
+    assert eng.tune_import(flat_table([(key, 6)])) == 1
+    assert parse_table(eng.tune_export()) == [(key, 6)]
+    eng.close()
