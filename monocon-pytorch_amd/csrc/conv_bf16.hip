@@ -417,84 +417,6 @@ __global__ __launch_bounds__(64 * WM * WN, SPL == 1 ? 3 : 2) void conv_bf16_kern
 #endif
 }
 
-// ---- weight packing: OIHW fp32 -> [tap][Cin/8][CoutP][8] bf16 (forward) and the dgrad variants
-// (transposed + flipped per source, or one output-parity class of a stride-2 data gradient; same tap
-// conventions as pack_conv_w_kernel / pack_conv_w_dgrad_kernel)
-// nsplit == 2: fp16 pieces of w * 2^e_w (e_w from the weight tensor's max |w|, `amax`), else bf16 pieces of w
-__device__ __forceinline__ void store_pieces(float r, unsigned short *dst, size_t plane, int nsplit) {
-    if (nsplit == 2) {
-        const _Float16 hi = (_Float16)r;
-        const _Float16 lo = (_Float16)(r - (float)hi);
-        dst[0] = __builtin_bit_cast(unsigned short, hi);
-        dst[plane] = __builtin_bit_cast(unsigned short, lo);
-    } else {
-        for (int q = 0; q < nsplit; ++q) {
-            const __bf16 piece = (__bf16)r;
-            dst[q * plane] = __builtin_bit_cast(unsigned short, piece);
-            r -= (float)piece;
-        }
-    }
-}
-__global__ void pack_conv_w_bf16_kernel(const float *__restrict__ w, int Cout, int Cin, int k, unsigned short *__restrict__ dst,
-                                        int CinPanel, int CoutP, int n_off, int c_off, int nsplit, const unsigned *amax) {
-    const size_t plane = (size_t)k * k * CinPanel * CoutP;
-    const float wscale = nsplit == 2 ? exp2i(f16_scale_exp(*amax)) : 1.f;
-    const int kk = k * k;
-    const size_t total = (size_t)Cout * Cin * kk;
-    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-        const int tap = e % kk;
-        const int c = (e / kk) % Cin;
-        const int n = e / ((size_t)kk * Cin);
-        const int cc = c + c_off, nn = n + n_off;
-        store_pieces(w[e] * wscale, dst + (((size_t)tap * (CinPanel >> 3) + (cc >> 3)) * CoutP + nn) * 8 + (cc & 7), plane, nsplit);
-    }
-}
-hipError_t launch_pack_conv_w_bf16(const float *w, int Cout, int Cin, int k, void *dst, int CinPanel, int CoutP, int n_off,
-                                   int c_off, int nsplit, hipStream_t st, const unsigned *amax) {
-    if (nsplit == 2 && !amax) return hipErrorInvalidValue;
-    const size_t total = (size_t)Cout * Cin * k * k;
-    size_t gsz = (total + 255) / 256;
-    if (gsz > 4096) gsz = 4096;
-    hipLaunchKernelGGL(pack_conv_w_bf16_kernel, dim3((unsigned)gsz), dim3(256), 0, st, w, Cout, Cin, k,
-                       static_cast<unsigned short *>(dst), CinPanel, CoutP, n_off, c_off, nsplit, amax);
-    return hipGetLastError();
-}
-__global__ void pack_conv_w_dgrad_bf16_kernel(const float *__restrict__ w, int Cout, int CinTotal, int k, int c_off, int Cs,
-                                              int CsP, int CoutPad, int cls, int nsplit, unsigned short *__restrict__ dst,
-                                              const unsigned *amax) {
-    const float wscale = nsplit == 2 ? exp2i(f16_scale_exp(*amax)) : 1.f;
-    const size_t plane = (size_t)(cls < 0 ? k * k : (1 + (cls >> 1)) * (1 + (cls & 1))) * CoutPad * CsP;
-    const int kk = k * k;
-    const size_t total = (size_t)Cout * Cs * kk;
-    const int py = cls >> 1, px = cls & 1;
-    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-        const int tap = e % kk;
-        const int cl = (e / kk) % Cs;
-        const int n = e / ((size_t)kk * Cs);
-        const int r = tap / k, s = tap % k;
-        int tapd;
-        if (cls < 0) {
-            tapd = (k - 1 - r) * k + (k - 1 - s);
-        } else {
-            if ((py == 0) != (r == 1) || (px == 0) != (s == 1)) continue;
-            const int dr = py ? (2 - r) / 2 : 0, ds = px ? (2 - s) / 2 : 0;
-            tapd = dr * (1 + px) + ds;
-        }
-        const float rem = w[(((size_t)n * CinTotal + c_off + cl) * k + r) * k + s] * wscale;
-        store_pieces(rem, dst + (((size_t)tapd * (CoutPad >> 3) + (n >> 3)) * CsP + cl) * 8 + (n & 7), plane, nsplit);
-    }
-}
-hipError_t launch_pack_conv_w_dgrad_bf16(const float *w, int Cout, int CinTotal, int k, int c_off, int Cs, int CsP, int CoutPad,
-                                         int cls, int nsplit, void *dst, hipStream_t st, const unsigned *amax) {
-    if (nsplit == 2 && !amax) return hipErrorInvalidValue;
-    const size_t total = (size_t)Cout * Cs * k * k;
-    size_t gsz = (total + 255) / 256;
-    if (gsz > 4096) gsz = 4096;
-    hipLaunchKernelGGL(pack_conv_w_dgrad_bf16_kernel, dim3((unsigned)gsz), dim3(256), 0, st, w, Cout, CinTotal, k, c_off, Cs,
-                       CsP, CoutPad, cls, nsplit, static_cast<unsigned short *>(dst), amax);
-    return hipGetLastError();
-}
-
 // ---- dispatch
 template <int KS, int S, class Sh, int SPL, bool BM = false, bool LZ = false>
 static hipError_t launch_b16_one(ConvArgs a, hipStream_t st, ConvArgs *resolved) {

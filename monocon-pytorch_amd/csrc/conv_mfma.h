@@ -538,6 +538,10 @@ inline int conv_coutp(int Cout) {
     const int t = conv_ntile(Cout);
     return (Cout + t - 1) / t * t;
 }
+// output extent of a k x k window with padding k / 2
+inline int conv_out_dim(int in, int ks, int stride) { return (in + 2 * (ks / 2) - ks) / stride + 1; }
+// 16-bit pieces per weight / activation element in precision mode `prec`: one bf16, three bf16 (mode 2), two fp16 (mode 3)
+inline int split_pieces(int prec) { return prec == 2 ? 3 : (prec == 3 ? 2 : 1); }
 // K-chunk: 32 when every source is a multiple of 32 channels and the 3x3 is stride 1 (or 1x1).
 inline int conv_ck(int ks, int stride, const int *src_c, int nsrc) {
     bool all32 = true;
@@ -571,11 +575,6 @@ bool conv_small_ok(const ConvArgs &a, int ks, int stride);
 bool conv_small_lazy_ok(const ConvArgs &a, int ks, int stride);     // conv_small_kernel<2, 16, 2, LZ>: lazy source (ConvSrc::la)
 bool conv_bf16_ok(const ConvArgs &a, int ks, int stride);
 hipError_t launch_conv_bf16(const ConvArgs &a, int ks, int stride, hipStream_t st, ConvArgs *resolved);
-// nsplit: 1 = bf16, 3 = three bf16 pieces, 2 = two fp16 pieces of w * 2^e_w (amax: the weight tensor's max |w|, see ConvArgs)
-hipError_t launch_pack_conv_w_bf16(const float *w, int Cout, int Cin, int k, void *dst, int CinPanel, int CoutP, int n_off,
-                                   int c_off, int nsplit, hipStream_t st, const unsigned *amax = nullptr);
-hipError_t launch_pack_conv_w_dgrad_bf16(const float *w, int Cout, int CinTotal, int k, int c_off, int Cs, int CsP, int CoutPad,
-                                         int cls, int nsplit, void *dst, hipStream_t st, const unsigned *amax = nullptr);
 // max |x| of a dense fp32 tensor folded into *slot (bit pattern; the caller zeroes the slot): for tensors that enter the
 // fp16-split mode from outside the plans' own producers (op-level entry points, stage-level forwards)
 // (single_word: a weight slot -- one word; otherwise a tensor slot of AMAX_WORDS words)

@@ -6,18 +6,11 @@
 namespace mc {
 
 // ---- parameter preparation ---------------------------------------------------------------
-// OIHW (Cout, Cin, k, k) -> [k*k][CinTotal/4][CoutP][4] at column offset n_off / row offset c_off
-hipError_t launch_pack_conv_w(const float *w_oihw, int Cout, int Cin, int ks, float *dst, int CinTotal,
-                              int CoutP, int n_off, int c_off, hipStream_t st);
-hipError_t launch_zero(float *p, size_t n, hipStream_t st);
-// eval-mode BN fold: scale = g*rsqrt(rv+eps), shift = b - rm*scale (g/b may be null => 1/0)
-hipError_t launch_fold_bn(const float *g, const float *b, const float *rm, const float *rv, float eps,
-                          int C, float *scale, float *shift, hipStream_t st);
+// (conv weights and the eval-mode BatchNorm folds: PackBatch / FoldBatch in train.h)
 // stem weights OIHW (16,3,7,7) -> [c][r][s][16]
 hipError_t launch_pack_stem_w(const float *w, float *dst, hipStream_t st);
 // deconv weights (C,1,4,4) -> [ky][kx][C]
 hipError_t launch_pack_deconv_w(const float *w, int C, float *dst, hipStream_t st);
-hipError_t launch_copy(const float *src, float *dst, size_t n, hipStream_t st);
 // up to COPY_BATCH_MAX small device-to-device copies in ONE launch (the per-step shuffling of head weights / gradients
 // between the parameter tensors and the fused-head layouts was ~70 separate 4-us copies)
 constexpr int COPY_BATCH_MAX = 32;

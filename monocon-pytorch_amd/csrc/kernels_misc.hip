@@ -9,33 +9,6 @@
 namespace mc {
 
 // ============================================================================ packing
-__global__ void pack_conv_w_kernel(const float *__restrict__ w, int Cout, int Cin, int kk, float *dst,
-                                   int CinTotal, int CoutP, int n_off, int c_off) {
-    const size_t total = (size_t)Cout * Cin * kk;
-    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-        const int tap = e % kk;
-        const int c = (e / kk) % Cin;
-        const int n = e / ((size_t)kk * Cin);
-        const int cg = c + c_off;
-        dst[(((size_t)tap * (CinTotal >> 2) + (cg >> 2)) * CoutP + n + n_off) * 4 + (cg & 3)] = w[e];
-    }
-}
-
-hipError_t launch_pack_conv_w(const float *w, int Cout, int Cin, int ks, float *dst, int CinTotal, int CoutP,
-                              int n_off, int c_off, hipStream_t st) {
-    const size_t total = (size_t)Cout * Cin * ks * ks;
-    const int blocks = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
-    hipLaunchKernelGGL(pack_conv_w_kernel, dim3(blocks), dim3(256), 0, st, w, Cout, Cin, ks * ks, dst, CinTotal,
-                       CoutP, n_off, c_off);
-    return hipGetLastError();
-}
-
-hipError_t launch_zero(float *p, size_t n, hipStream_t st) { return hipMemsetAsync(p, 0, n * sizeof(float), st); }
-
-hipError_t launch_copy(const float *src, float *dst, size_t n, hipStream_t st) {
-    return hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, st);
-}
-
 __global__ __launch_bounds__(256) void copy_batch_kernel(const CopyBatch cb) {
     const int seg = blockIdx.y;                    // wave-uniform: the table is read through scalar loads
     const float *s = cb.src[seg];
@@ -50,22 +23,6 @@ hipError_t launch_copy_batch(const CopyBatch &cb, hipStream_t st) {
     int gx = (mx + 1023) / 1024;                   // ~4 elements per thread for the largest segment
     if (gx > 64) gx = 64;
     hipLaunchKernelGGL(copy_batch_kernel, dim3(gx, cb.count), dim3(256), 0, st, cb);
-    return hipGetLastError();
-}
-
-__global__ void fold_bn_kernel(const float *g, const float *b, const float *rm, const float *rv, float eps, int C,
-                               float *scale, float *shift) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= C) return;
-    const float inv = 1.0f / sqrtf(rv[c] + eps);
-    const float s = (g ? g[c] : 1.f) * inv;
-    scale[c] = s;
-    shift[c] = (b ? b[c] : 0.f) - rm[c] * s;
-}
-
-hipError_t launch_fold_bn(const float *g, const float *b, const float *rm, const float *rv, float eps, int C,
-                          float *scale, float *shift, hipStream_t st) {
-    hipLaunchKernelGGL(fold_bn_kernel, dim3((C + 63) / 64), dim3(64), 0, st, g, b, rm, rv, eps, C, scale, shift);
     return hipGetLastError();
 }
 

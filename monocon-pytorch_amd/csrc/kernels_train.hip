@@ -523,22 +523,6 @@ hipError_t launch_affine_bwd(const float *dz, const float *z, const float *y, co
     return hipGetLastError();
 }
 
-// ------------------------------------------------------------------ small helpers
-__global__ void add_kernel(f32x4 *__restrict__ a, const f32x4 *__restrict__ b, size_t n4) {
-    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < n4; e += (size_t)gridDim.x * blockDim.x) {
-        f32x4 x = a[e];
-        const f32x4 yv = b[e];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) x[j] += yv[j];
-        a[e] = x;
-    }
-}
-hipError_t launch_add(float *a, const float *b, size_t n, hipStream_t st) {
-    hipLaunchKernelGGL(add_kernel, dim3(grid_for(n / 4, 256)), dim3(256), 0, st, reinterpret_cast<f32x4 *>(a),
-                       reinterpret_cast<const f32x4 *>(b), n / 4);
-    return hipGetLastError();
-}
-
 // column sums of a [rows][ld] matrix -> out[C] (conv bias gradients): coalesced row-block partial sums
 // (chan_reduce, mode 0) followed by a per-column reduction of the partials
 __global__ __launch_bounds__(256) void colsum_final_kernel(const float *__restrict__ partial, int nb, int Cstride,

@@ -238,8 +238,7 @@ struct Builder {
                 bool use_layer_affine = true, float **stats_out = nullptr, const float *stat_shift = nullptr,
                 int *chunks_out = nullptr) {
         const Tensor &s0 = srcs[0];
-        const int Ho = (s0.H + 2 * (L.ks / 2) - L.ks) / L.stride + 1;
-        const int Wo = (s0.W + 2 * (L.ks / 2) - L.ks) / L.stride + 1;
+        const int Ho = conv_out_dim(s0.H, L.ks, L.stride), Wo = conv_out_dim(s0.W, L.ks, L.stride);
         Tensor out = into ? *into : alloc(s0.B, Ho, Wo, L.cout);
         Op op{};
         op.kind = OP_CONV;
@@ -637,13 +636,8 @@ int mc_pack_params(mc_handle *h, int train_mode, void *stream) {
     if (rebuild) h->w_amax_of.clear();
     auto add_fwd = [&](const float *w, int Cout, int Cin, int ks, float *dst32, void *dst16, int CinPanel, int CoutP, int n_off,
                        unsigned *amax) {
-        mc::PackJobDesc j{};
-        j.w = w; j.dst32 = dst32; j.dst16 = (h->prec >= 1 && CinPanel % 8 == 0) ? dst16 : nullptr;
-        j.kind = 0; j.Cout = Cout; j.Cin = Cin; j.k = ks; j.CinTotal = CinPanel; j.CoutP = CoutP; j.n_off = n_off; j.c_off = 0;
-        j.nsplit = h->prec == 2 ? 3 : (h->prec == 3 ? 2 : 1); j.cls = -1;
-        j.amax = amax;
         h->w_amax_of[w] = amax;
-        h->fwd_pack.add(j);
+        h->fwd_pack.add(mc::pack_job_fwd(w, Cout, Cin, ks, dst32, dst16, CinPanel, CoutP, n_off, h->prec, amax));
     };
     for (auto &kv : h->convs) {
         if (!rebuild) break;
@@ -951,36 +945,32 @@ int mc_op_conv(mc_handle *h, const float *const src[], const int src_channels[],
     }
     a.nsrc = nsrc;
     a.B = B; a.Hin = Hin; a.Win = Win;
-    a.Hout = (Hin + 2 * (ksize / 2) - ksize) / stride + 1;
-    a.Wout = (Win + 2 * (ksize / 2) - ksize) / stride + 1;
+    a.Hout = conv_out_dim(Hin, ksize, stride);
+    a.Wout = conv_out_dim(Win, ksize, stride);
     a.Cin = cin; a.Cout = Cout; a.CoutP = conv_coutp(Cout);
-    const size_t wn = (size_t)ksize * ksize * cin * a.CoutP;
+    const size_t wn = fwd_panel_elems(ksize, cin, a.CoutP);
     ScratchBuf wpk, wpk16;
     HIPCHK(h, wpk.alloc(wn * sizeof(float)));
     HIPCHK(h, hipMemsetAsync(wpk.p, 0, wn * sizeof(float), st));
-    HIPCHK(h, launch_pack_conv_w(weight_oihw, Cout, cin, ksize, wpk.as<float>(), cin, a.CoutP, 0, 0, st));
     a.wpk = wpk.as<float>();
-    ScratchBuf slots;       // mode 3: max |x| of every source and of the weight, each from a pass of its own
-    if (h->prec >= 1 && cin % 8 == 0) {
-        const int pieces = h->prec == 2 ? 3 : (h->prec == 3 ? 2 : 1);
-        unsigned *sl = nullptr;
+    ScratchBuf slots;       // mode 3: max |x| of every source from a pass of its own; the pack finds max |w|
+    unsigned *w_amax = nullptr;
+    if (panel_has_pieces(h->prec, cin)) {
         if (h->prec == 3) {
-            HIPCHK(h, slots.alloc(5 * AMAX_WORDS * sizeof(unsigned)));
-            sl = slots.as<unsigned>();
-            HIPCHK(h, hipMemsetAsync(sl, 0, 5 * AMAX_WORDS * sizeof(unsigned), st));
-            for (int i = 0; i < nsrc; ++i) {
-                HIPCHK(h, launch_absmax(src[i], (size_t)B * Hin * Win * src_channels[i], sl + i * AMAX_WORDS, st));
-                a.amax_in[i] = sl + i * AMAX_WORDS;
-            }
-            sl += 4 * AMAX_WORDS;                                       // the weight's single-word slot
-            HIPCHK(h, launch_absmax(weight_oihw, (size_t)Cout * cin * ksize * ksize, sl, st, true));
-            a.amax_w = sl;
+            size_t n[4];
+            for (int i = 0; i < nsrc; ++i) n[i] = (size_t)B * Hin * Win * src_channels[i];
+            HIPCHK(h, op_amax_slots(slots, src, n, nsrc, nullptr, 0, true, st));
+            for (int i = 0; i < nsrc; ++i) a.amax_in[i] = slots.as<unsigned>() + i * AMAX_WORDS;
+            a.amax_w = w_amax = slots.as<unsigned>() + 4 * AMAX_WORDS;
         }
-        HIPCHK(h, wpk16.alloc(wn * 2 * pieces));
-        HIPCHK(h, hipMemsetAsync(wpk16.p, 0, wn * 2 * pieces, st));
-        HIPCHK(h, launch_pack_conv_w_bf16(weight_oihw, Cout, cin, ksize, wpk16.p, cin, a.CoutP, 0, 0, pieces, st, sl));
+        const size_t bytes16 = wn * 2 * split_pieces(h->prec);
+        HIPCHK(h, wpk16.alloc(bytes16));
+        HIPCHK(h, hipMemsetAsync(wpk16.p, 0, bytes16, st));
         a.wpk16 = wpk16.p; a.prec = h->prec;
     }
+    PackBatch pack;         // the plans' packer, one job
+    pack.add(pack_job_fwd(weight_oihw, Cout, cin, ksize, wpk.as<float>(), wpk16.p, cin, a.CoutP, 0, h->prec, w_amax));
+    HIPCHK(h, pack.launch(st, h->prec == 3));
     a.scale = scale; a.bias = bias; a.res = residual; a.res_ld = Cout;
     a.out = out; a.out_ld = Cout; a.out_coff = 0; a.relu = relu;
     a.cfg = h->force_cfg;
@@ -1150,8 +1140,8 @@ int mc_bench_conv(mc_handle *h, int B, int Hin, int Win, int nsrc, const int src
     }
     a.nsrc = nsrc;
     a.B = B; a.Hin = Hin; a.Win = Win;
-    a.Hout = (Hin + 2 * (ksize / 2) - ksize) / stride + 1;
-    a.Wout = (Win + 2 * (ksize / 2) - ksize) / stride + 1;
+    a.Hout = conv_out_dim(Hin, ksize, stride);
+    a.Wout = conv_out_dim(Win, ksize, stride);
     a.Cin = cin; a.Cout = Cout; a.CoutP = conv_coutp(Cout);
     a.wpk = alloc_fill((size_t)ksize * ksize * cin * a.CoutP, 0.05f);
     a.scale = alloc_fill(Cout, 1.0f);

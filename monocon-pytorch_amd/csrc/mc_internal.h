@@ -241,7 +241,21 @@ struct ScratchBuf {
     template <class T> T *as() const { return static_cast<T *>(p); }
 };
 
-#define HIPCHK(h, expr)                                                                       \
+// The mode-3 max-|x| slots of an op-level entry point, zeroed on `st`: slot i < 4 <- max |src[i]| (n[i] elements), slot 4 is
+// the one more operand's -- `extra` non-null: max |extra| (n_extra elements; single_word: a weight's slot), null: left
+// zeroed for the caller's own pass.  Slot i is at buf.as<unsigned>() + i * AMAX_WORDS.
+static inline hipError_t op_amax_slots(ScratchBuf &buf, const float *const src[], const size_t n[], int nsrc, const float *extra,
+                                       size_t n_extra, bool single_word, hipStream_t st) {
+    const size_t bytes = 5 * mc::AMAX_WORDS * sizeof(unsigned);
+    hipError_t e = buf.alloc(bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(buf.p, 0, bytes, st);
+    unsigned *sl = buf.as<unsigned>();
+    for (int i = 0; i < nsrc && e == hipSuccess; ++i) e = mc::launch_absmax(src[i], n[i], sl + i * mc::AMAX_WORDS, st);
+    if (extra && e == hipSuccess) e = mc::launch_absmax(extra, n_extra, sl + 4 * mc::AMAX_WORDS, st, single_word);
+    return e;
+}
+
+#define HIPCHK(h, expr)                                                                      \
     do {                                                                                      \
         hipError_t e_ = (expr);                                                               \
         if (e_ != hipSuccess) return fail(h, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \

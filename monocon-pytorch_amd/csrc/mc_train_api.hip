@@ -177,21 +177,17 @@ int mc_op_conv_wgrad(mc_handle *h, const float *const src[], const int src_chann
         cin += src_channels[i];
     }
     a.nsrc = nsrc; a.B = B; a.Hin = Hin; a.Win = Win;
-    a.Hout = (Hin + 2 * (ksize / 2) - ksize) / stride + 1;
-    a.Wout = (Win + 2 * (ksize / 2) - ksize) / stride + 1;
+    a.Hout = mc::conv_out_dim(Hin, ksize, stride);
+    a.Wout = mc::conv_out_dim(Win, ksize, stride);
     a.Cin = cin; a.Cout = Cout; a.dy = dy; a.dy_ld = Cout;
     a.prec = h->prec;
     ScratchBuf slots;       // mode 3: max |x| of every source and of dY
     if (h->prec == 3) {
-        HIPCHK(h, slots.alloc(5 * mc::AMAX_WORDS * sizeof(unsigned)));
-        unsigned *sl = slots.as<unsigned>();
-        HIPCHK(h, hipMemsetAsync(sl, 0, 5 * mc::AMAX_WORDS * sizeof(unsigned), st));
-        for (int i = 0; i < nsrc; ++i) {
-            HIPCHK(h, mc::launch_absmax(src[i], (size_t)B * Hin * Win * src_channels[i], sl + i * mc::AMAX_WORDS, st));
-            a.amax_x[i] = sl + i * mc::AMAX_WORDS;
-        }
-        HIPCHK(h, mc::launch_absmax(dy, (size_t)B * a.Hout * a.Wout * Cout, sl + 4 * mc::AMAX_WORDS, st));
-        a.amax_dy = sl + 4 * mc::AMAX_WORDS;
+        size_t n[4];
+        for (int i = 0; i < nsrc; ++i) n[i] = (size_t)B * Hin * Win * src_channels[i];
+        HIPCHK(h, op_amax_slots(slots, src, n, nsrc, dy, (size_t)B * a.Hout * a.Wout * Cout, false, st));
+        for (int i = 0; i < nsrc; ++i) a.amax_x[i] = slots.as<unsigned>() + i * mc::AMAX_WORDS;
+        a.amax_dy = slots.as<unsigned>() + 4 * mc::AMAX_WORDS;
     }
     mc::wgrad_plan(a, ksize, stride);
     void *part = nullptr;
@@ -215,59 +211,40 @@ int mc_op_conv_dgrad(mc_handle *h, const float *dy, const float *weight_oihw, in
     if (stride == 2 && ((Hin | Win) & 1)) return fail(h, "mc_op_conv_dgrad: stride 2 needs even Hin, Win");
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const int Ho = (Hin + 2 * (ksize / 2) - ksize) / stride + 1, Wo = (Win + 2 * (ksize / 2) - ksize) / stride + 1;
-    const int CsP = mc::conv_coutp(Cs), pieces = h->prec == 2 ? 3 : (h->prec == 3 ? 2 : 1);
+    const int Ho = mc::conv_out_dim(Hin, ksize, stride), Wo = mc::conv_out_dim(Win, ksize, stride);
     const int nclass = stride == 2 ? 4 : 1;
-    std::vector<void *> tmp;
-    hipError_t e = hipSuccess;
-    ScratchBuf slots;       // mode 3: max |dy| and max |w|
-    unsigned *sl = nullptr;
+    ScratchBuf slots;       // mode 3: max |dy| and max |w| (a data-gradient job takes its scale from an existing slot)
+    unsigned *dy_amax = nullptr, *w_amax = nullptr;
     if (h->prec == 3) {
-        HIPCHK(h, slots.alloc((mc::AMAX_WORDS + 1) * sizeof(unsigned)));
-        sl = slots.as<unsigned>();
-        HIPCHK(h, hipMemsetAsync(sl, 0, (mc::AMAX_WORDS + 1) * sizeof(unsigned), st));
-        HIPCHK(h, mc::launch_absmax(dy, (size_t)B * Ho * Wo * Cout, sl, st));
-        HIPCHK(h, mc::launch_absmax(weight_oihw, (size_t)Cout * CinTotal * ksize * ksize, sl + mc::AMAX_WORDS, st, true));
+        const size_t ndy = (size_t)B * Ho * Wo * Cout;
+        HIPCHK(h, op_amax_slots(slots, &dy, &ndy, 1, weight_oihw, (size_t)Cout * CinTotal * ksize * ksize, true, st));
+        dy_amax = slots.as<unsigned>();
+        w_amax = dy_amax + 4 * mc::AMAX_WORDS;
     }
-    for (int cls = 0; cls < nclass && e == hipSuccess; ++cls) {
-        const int cid = stride == 2 ? cls : -1;
-        const int py = cls >> 1, px = cls & 1;
-        const int taps = stride == 2 ? (1 + py) * (1 + px) : ksize * ksize;
-        const size_t pn = (size_t)taps * Cout * CsP;
-        void *panel = nullptr, *panel16 = nullptr;
-        if (hipMalloc(&panel, pn * 4) != hipSuccess) { e = hipErrorOutOfMemory; break; }
-        tmp.push_back(panel);
-        (void)hipMemsetAsync(panel, 0, pn * 4, st);
-        e = mc::launch_pack_conv_w_dgrad(weight_oihw, Cout, CinTotal, ksize, c_off, Cs, CsP, Cout, cid, static_cast<float *>(panel), st);
-        if (e != hipSuccess) break;
-        if (h->prec >= 1 && Cout % 32 == 0) {
-            if (hipMalloc(&panel16, pn * 2 * pieces) != hipSuccess) { e = hipErrorOutOfMemory; break; }
-            tmp.push_back(panel16);
-            (void)hipMemsetAsync(panel16, 0, pn * 2 * pieces, st);
-            e = mc::launch_pack_conv_w_dgrad_bf16(weight_oihw, Cout, CinTotal, ksize, c_off, Cs, CsP, Cout, cid, pieces, panel16, st,
-                                                  sl ? sl + mc::AMAX_WORDS : nullptr);
-            if (e != hipSuccess) break;
+    // one panel per class (stride 2: the four output-parity classes), packed by the plans' packer in one grid
+    ScratchBuf panel[4], panel16[4];
+    mc::PackBatch pack;
+    for (int c = 0; c < nclass; ++c) {
+        const int cls = stride == 2 ? c : -1;
+        const size_t pn = mc::dgrad_panel_elems(ksize, cls, Cout, Cs);
+        HIPCHK(h, panel[c].alloc(pn * 4));
+        HIPCHK(h, hipMemsetAsync(panel[c].p, 0, pn * 4, st));
+        if (mc::panel_has_pieces(h->prec, Cout)) {
+            const size_t bytes16 = pn * 2 * mc::split_pieces(h->prec);
+            HIPCHK(h, panel16[c].alloc(bytes16));
+            HIPCHK(h, hipMemsetAsync(panel16[c].p, 0, bytes16, st));
         }
-        mc::ConvArgs d{};
-        d.nsrc = 1; d.src[0].p = dy; d.src[0].C = Cout;
-        d.B = B; d.Hin = Ho; d.Win = Wo; d.Hout = Ho; d.Wout = Wo;
-        d.Cin = Cout; d.Cout = Cs; d.CoutP = CsP; d.wpk = static_cast<float *>(panel);
-        d.wpk16 = panel16; d.prec = panel16 ? h->prec : 0;
-        if (sl) { d.amax_in[0] = sl; d.amax_w = sl + mc::AMAX_WORDS; }
-        d.out = dx; d.out_ld = Cs;
-        int kk = ksize;
-        if (stride == 2) {
-            d.out = dx + ((size_t)py * Win + px) * Cs;
-            d.o_px = 2 * Cs; d.o_row = 2 * Win * Cs; d.o_img = Hin * Win * Cs;
-            kk = (1 + py) * 10 + (1 + px);
-            if (kk == 11) kk = 1;
-        }
-        if (accumulate) { d.res = d.out; d.res_ld = Cs; d.r_px = d.o_px; d.r_row = d.o_row; d.r_img = d.o_img; }
+        pack.add(mc::pack_job_dgrad(weight_oihw, Cout, CinTotal, ksize, c_off, Cs, Cout, cls, panel[c].as<float>(), panel16[c].p,
+                                    h->prec, w_amax));
+    }
+    hipError_t e = pack.launch(st);
+    for (int c = 0; c < nclass && e == hipSuccess; ++c) {
+        mc::ConvArgs d;
+        const int kk = mc::dgrad_conv_args(d, pack.jobs[c], h->prec, dy, dy_amax, B, Ho, Wo, Cout, dx, Hin, Win, accumulate != 0);
         d.cfg = h->force_cfg;
         e = mc::launch_conv(d, kk, 1, st);
     }
     hipError_t e2 = hipStreamSynchronize(st);   // test entry point: the panels are temporaries
-    for (void *q : tmp) (void)hipFree(q);
     HIPCHK(h, e);
     HIPCHK(h, e2);
     return 0;

@@ -106,15 +106,6 @@ struct TNode {
     bool lrelu = true;
 };
 
-struct PackJob {           // dgrad panel refreshed from the master weights before every forward
-    const float *w;
-    int Cout, CinTotal, k, c_off, Cs, CsP, CoutPad;
-    int cls;           // -1: stride-1 panel; 0..3: output-parity class of a stride-2 data gradient
-    float *dst;
-    void *dst16;       // bf16 / fp16 piece planes of the panel (precision modes 1..3) or null
-    unsigned *amax;    // mode 3: max-|w| slot of the master weight
-};
-
 enum RecKind { REC_STEM, REC_CONV, REC_POOL, REC_DECONV, REC_HEAD };
 struct Rec {
     RecKind kind;
@@ -166,8 +157,7 @@ struct TrainState {
     hipEvent_t side_done = nullptr;
     bool dual = true;                // side steps run on `side` (false: MONOCON_HIP_DUAL_STREAM=0, or the stream / an event could not be created)
     unsigned *img_amax = nullptr;      // mode 3: max |image| slot (written by the forward stem, read by its weight gradient)
-    std::vector<PackJob> packs;
-    mc::PackBatch pack_batch;        // the data-gradient panels of `packs`, one grid per forward
+    mc::PackBatch pack_batch;        // the data-gradient panels, refreshed from the master weights in one grid per forward
     std::vector<Fn> pack_fns;
     // per-call external pointers
     const float *img = nullptr;
@@ -217,7 +207,6 @@ struct TB {   // train plan builder
     PlanAlloc mem{h, ts->mem, ts->ok, 1, 1024};
     const PlanSwitches &sw = ts->sw;
     const int B = ts->B, H = ts->H, W = ts->W, fh = H / 4, fw = W / 4, HW = fh * fw;
-    void *last_panel16 = nullptr;   // bf16 twin of the panel the last pack_job() made
 
     float *alloc(size_t n) { return mem.alloc(n); }
     unsigned *slot() { return mem.slot(); }
@@ -453,7 +442,7 @@ struct TB {   // train plan builder
         const bool relu = s.relu, dead = s.dead, never_lazy = s.never_lazy && !sw.lazy_feat;
         const Tensor s0 = ts->nodes[srcs[0]].t;   // by value: node() below may reallocate ts->nodes
         const int B = s0.B;
-        const int Ho = (s0.H + 2 * (Lr.ks / 2) - Lr.ks) / Lr.stride + 1, Wo = (s0.W + 2 * (Lr.ks / 2) - Lr.ks) / Lr.stride + 1;
+        const int Ho = conv_out_dim(s0.H, Lr.ks, Lr.stride), Wo = conv_out_dim(s0.W, Lr.ks, Lr.stride);
         Rec r;
         r.kind = REC_CONV; r.L = &Lr; r.srcs = srcs; r.res = res; r.relu = relu; r.dead = dead; r.bn = Lr.bn;
         r.y.B = B; r.y.H = Ho; r.y.W = Wo; r.y.C = Lr.cout;
@@ -543,19 +532,14 @@ struct TB {   // train plan builder
     }
 
     // ---------------------------------------------------------------- backward pieces
-    void pack_job(const float *w, int Cout, int CinTotal, int k, int c_off, int Cs, int CoutPad, float **dst_out, int *csp_out,
-                  int cls = -1) {
-        PackJob j;
-        j.w = w; j.Cout = Cout; j.CinTotal = CinTotal; j.k = k; j.c_off = c_off; j.Cs = Cs;
-        j.CsP = conv_coutp(Cs); j.CoutPad = CoutPad; j.cls = cls;
-        const int taps = cls < 0 ? k * k : (1 + (cls >> 1)) * (1 + (cls & 1));
-        j.dst = alloc((size_t)taps * CoutPad * j.CsP);
-        j.dst16 = (h->prec >= 1 && CoutPad % 8 == 0) ? alloc((3 * (size_t)taps * CoutPad * j.CsP + 1) / 2) : nullptr;
-        j.amax = w_slot(w);
-        last_panel16 = j.dst16;
-        ts->packs.push_back(j);
-        *dst_out = j.dst;
-        *csp_out = j.CsP;
+    // a data-gradient panel (train.h: pack_job_dgrad), refreshed with the plan's other panels before every forward (the
+    // precision mode is baked into a plan: mc_set_precision bumps bind_gen)
+    const PackJobDesc &pack_job(const float *w, int Cout, int CinTotal, int k, int c_off, int Cs, int CoutPad, int cls) {
+        const size_t pn = dgrad_panel_elems(k, cls, CoutPad, Cs);
+        float *dst = alloc(pn);
+        void *dst16 = panel_has_pieces(h->prec, CoutPad) ? alloc((3 * pn + 1) / 2) : nullptr;     // room for three planes
+        ts->pack_batch.add(pack_job_dgrad(w, Cout, CinTotal, k, c_off, Cs, CoutPad, cls, dst, dst16, h->prec, w_slot(w)));
+        return ts->pack_batch.jobs.back();
     }
 
     // dgrad: g_src (+)= conv_s1(dy (optionally dilated), flipped panel)
@@ -564,19 +548,10 @@ struct TB {   // train plan builder
         TNode &sn = ts->nodes[srcnode];
         if (!sn.needs_grad) return;
         g_acquire(srcnode);
-        // a stride-1 conv over dY with the panel of one output-parity class (-1: the whole flipped kernel)
-        auto dgrad_conv = [&](int cls) {
-            float *panel;
-            int csp;
-            pack_job(w_master, Cout_fwd, CinTotal, ks, c_off, sn.t.C, CoutPad, &panel, &csp, cls);
-            ConvArgs d{};
-            d.nsrc = 1;
-            d.src[0].p = dy.p; d.src[0].C = dy.C;
-            d.B = dy.B; d.Hin = dy.H; d.Win = dy.W; d.Hout = dy.H; d.Wout = dy.W;
-            d.Cin = dy.C; d.Cout = sn.t.C; d.CoutP = csp; d.wpk = panel;
-            d.wpk16 = last_panel16; d.prec = last_panel16 ? h->prec : 0;
-            d.amax_in[0] = dy.amax; d.amax_w = w_slot(w_master);
-            return d;
+        // a stride-1 conv over dY with the panel of one output-parity class (-1: the whole flipped kernel); returns its window code
+        auto dgrad_conv = [&](int cls, ConvArgs &d) {
+            const PackJobDesc &p = pack_job(w_master, Cout_fwd, CinTotal, ks, c_off, sn.t.C, CoutPad, cls);
+            return dgrad_conv_args(d, p, h->prec, dy.p, dy.amax, dy.B, dy.H, dy.W, dy.C, sn.g, sn.t.H, sn.t.W, sn.ginit);
         };
         if (stride == 2 && ks == 3) {
             // four output-parity classes, each a small stride-1 window conv over dY that scatters to every
@@ -597,23 +572,16 @@ struct TB {   // train plan builder
                 return;
             }
             for (int cls = 0; cls < 4; ++cls) {
-                const int py = cls >> 1, px = cls & 1;
-                ConvArgs d = dgrad_conv(cls);
-                const int ld = sn.t.C;
-                d.out = sn.g + ((size_t)py * sn.t.W + px) * ld; d.out_ld = ld;
-                d.o_px = 2 * ld; d.o_row = 2 * sn.t.W * ld; d.o_img = sn.t.H * sn.t.W * ld;
-                if (sn.ginit) { d.res = d.out; d.res_ld = ld; d.r_px = d.o_px; d.r_row = d.o_row; d.r_img = d.o_img; }
-                const int kcode = (1 + py) * 10 + (1 + px);
-                const int kk = kcode == 11 ? 1 : kcode;
+                ConvArgs d;
+                const int kk = dgrad_conv(cls, d);
                 d.cfg = ts->ok ? mc_choose_conv_cfg(h, d, kk, 1) : CFG_128x32;
                 push_bwd([=](mc_handle *hh, hipStream_t st) { HIPCHK(hh, launch_conv(d, kk, 1, st)); return 0; });
             }
             wrote(srcnode);
             return;
         }
-        ConvArgs d = dgrad_conv(-1);
-        d.out = sn.g; d.out_ld = sn.t.C;
-        if (sn.ginit) { d.res = sn.g; d.res_ld = sn.t.C; }
+        ConvArgs d;
+        dgrad_conv(-1, d);
         if (dy.H != sn.t.H || dy.W != sn.t.W) { ts->ok = false; h->err = "train plan: dgrad shape mismatch"; }
         d.cfg = ts->ok ? mc_choose_conv_cfg(h, d, ks, 1) : CFG_128x32;
         // The weight-resident kernel (conv_wres.hip) owns its CU -- four waves with the whole register file -- so beside the
@@ -1171,17 +1139,6 @@ static int forward_train_impl(mc_handle *h, const float *img, const mc_labels *l
     if (!h->pack_clean && mc_pack_params(h, 1, stream)) return -1;   // mc_pack_params / the optimizer step track staleness
     for (auto &f : ts->pack_fns)       // dense head weight copies first: some dgrad panels are cut from them
         if (f(h, st)) return -1;
-    if (ts->pack_batch.jobs.size() != ts->packs.size()) {      // first forward of the plan: table of the data-gradient panels
-        ts->pack_batch.clear();
-        for (const PackJob &j : ts->packs) {
-            mc::PackJobDesc d{};
-            d.w = j.w; d.dst32 = j.dst; d.dst16 = j.dst16; d.kind = 1;
-            d.Cout = j.Cout; d.Cin = j.Cs; d.k = j.k; d.CinTotal = j.CinTotal; d.CoutP = j.CoutPad; d.n_off = 0; d.c_off = j.c_off;
-            d.CsP = j.CsP; d.cls = j.cls; d.nsplit = h->prec == 2 ? 3 : (h->prec == 3 ? 2 : 1);
-            d.amax = j.amax;
-            ts->pack_batch.add(d);
-        }
-    }
     HIPCHK(h, ts->pack_batch.launch(st));
     h->train_generation = ++g_train_generation;
     ts->gfeat_ext = nullptr;      // (a previous mc_head_backward's output tensor may be gone by now)

@@ -5,8 +5,17 @@
 // per layer that was one launch for the fp32 panel, one for the bf16 planes and one BatchNorm fold -- ~200 launches of
 // ~5 us per step in fp32 mode, ~400 in the bf16x3 mode, i.e. 1-2 ms of a 80-100 ms step spent on launch cadence.
 // A job table (one entry per weight tensor, block ranges by prefix sum) turns each family into a single grid.
-// Layouts are those of pack_conv_w_kernel / pack_conv_w_bf16_kernel / pack_conv_w_dgrad_kernel /
-// pack_conv_w_dgrad_bf16_kernel (kernels_misc.hip, conv_bf16.hip, kernels_head_train.hip), element for element.
+// The op-level entry points (mc_op_conv, mc_op_conv_dgrad) pack through the same table, one job per panel.
+//
+// Forward panel of W (Cout, Cin, k, k), tap = r * k + s:
+//   dst32[tap][c/4][n (CoutP columns)][c%4] = W[n][c][r][s];   dst16[piece][tap][c/8][n][c%8] = its 16-bit pieces
+// Data-gradient panel: the transposed / flipped convolution that maps dY (Cout channels, padded to CoutPad) to dX of ONE
+// source (channels [c_off, c_off + Cs) of W (Cout, CinTotal, k, k)):
+//   dst32[tap'][n/4][c_local (padded to CsP)][n%4] = W[n][c_off + c_local][k-1-r'][k-1-s'];   dst16[piece][tap'][n/8][c_local][n%8]
+// cls < 0: the stride-1 case above.  cls = 2*py + px: output-parity class of a stride-2 3x3 data gradient,
+//   dX[2i+py][2j+px] = sum_{dr<KH, ds<KW} dY[i+dr][j+ds] . W[.][.][r(dr)][s(ds)],   KH = 1 + py, KW = 1 + px,
+//   r(dr) = 1 (py = 0) or 2 - 2*dr (py = 1), same for s: the panel keeps only those KH*KW taps, window order.
+// Pieces: nsplit bf16 pieces of w, or (nsplit == 2) two fp16 pieces of w * 2^e_w, e_w from the weight tensor's max |w|.
 #include "kernels.h"
 #include "train.h"
 #include "conv_mfma.h"

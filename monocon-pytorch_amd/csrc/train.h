@@ -62,6 +62,56 @@ struct PackJobDesc {
     int block_begin, nblocks;
     unsigned *amax;        // nsplit == 2: slot holding max |w| of the master weight(s) behind the panel (conv_mfma.h)
 };
+// does a panel whose K dimension (forward: its channels, data gradient: CoutPad) is K get 16-bit piece planes in mode prec?
+inline bool panel_has_pieces(int prec, int K) { return prec >= 1 && K % 8 == 0; }
+// taps of a data-gradient panel: the whole flipped kernel (cls < 0) or the window of one output-parity class
+inline int dgrad_taps(int k, int cls) { return cls < 0 ? k * k : (1 + (cls >> 1)) * (1 + (cls & 1)); }
+// elements of a panel (one fp32 plane; a piece plane has as many 16-bit elements)
+inline size_t fwd_panel_elems(int k, int CinPanel, int CoutP) { return (size_t)k * k * CinPanel * CoutP; }
+inline size_t dgrad_panel_elems(int k, int cls, int CoutPad, int Cs) { return (size_t)dgrad_taps(k, cls) * CoutPad * conv_coutp(Cs); }
+// forward panel: w (Cout, Cin, k, k) -> columns [n_off, n_off + Cout) of a panel of CinPanel channels x CoutP columns.
+// dst16 is ignored where the panel has no piece planes; amax: the weight's max-|w| slot (mode 3)
+inline PackJobDesc pack_job_fwd(const float *w, int Cout, int Cin, int k, float *dst32, void *dst16, int CinPanel, int CoutP,
+                                int n_off, int prec, unsigned *amax) {
+    PackJobDesc j{};
+    j.w = w; j.dst32 = dst32; j.dst16 = panel_has_pieces(prec, CinPanel) ? dst16 : nullptr;
+    j.kind = 0; j.Cout = Cout; j.Cin = Cin; j.k = k; j.CinTotal = CinPanel; j.CoutP = CoutP; j.n_off = n_off;
+    j.cls = -1; j.nsplit = split_pieces(prec); j.amax = amax;
+    return j;
+}
+// data-gradient panel of ONE source (channels [c_off, c_off + Cs) of the forward weight w (Cout, CinTotal, k, k)) and one
+// class (-1: stride 1; 0..3: output-parity class of a stride-2 3x3 data gradient); dY has CoutPad >= Cout channels
+inline PackJobDesc pack_job_dgrad(const float *w, int Cout, int CinTotal, int k, int c_off, int Cs, int CoutPad, int cls,
+                                  float *dst32, void *dst16, int prec, unsigned *amax) {
+    PackJobDesc j{};
+    j.w = w; j.dst32 = dst32; j.dst16 = panel_has_pieces(prec, CoutPad) ? dst16 : nullptr;
+    j.kind = 1; j.Cout = Cout; j.Cin = Cs; j.k = k; j.CinTotal = CinTotal; j.CoutP = CoutPad; j.c_off = c_off;
+    j.CsP = conv_coutp(Cs); j.cls = cls; j.nsplit = split_pieces(prec); j.amax = amax;
+    return j;
+}
+// The launch of one data-gradient panel: a stride-1 conv over dY (B, Hd, Wd, Cd channels, max-|dY| slot dy_amax) with the
+// panel of job `p` in precision mode prec, into g, the NHWC gradient (Hs x Ws) of the panel's source -- dense for the
+// stride-1 panel, every second pixel from (py, px) for a parity class; accumulate: on top of what g holds.  Fills d (shape
+// id and epilogue extras stay the caller's) and returns the window code to hand launch_conv() as ks, with stride 1.
+inline int dgrad_conv_args(ConvArgs &d, const PackJobDesc &p, int prec, const float *dy, const unsigned *dy_amax, int B, int Hd,
+                           int Wd, int Cd, float *g, int Hs, int Ws, bool accumulate) {
+    const int ld = p.Cin, py = p.cls >> 1, px = p.cls & 1;
+    d = ConvArgs{};
+    d.nsrc = 1; d.src[0].p = dy; d.src[0].C = Cd;
+    d.B = B; d.Hin = Hd; d.Win = Wd; d.Hout = Hd; d.Wout = Wd;
+    d.Cin = Cd; d.Cout = ld; d.CoutP = p.CsP; d.wpk = p.dst32;
+    d.wpk16 = p.dst16; d.prec = p.dst16 ? prec : 0;
+    d.amax_in[0] = dy_amax; d.amax_w = p.amax;
+    d.out = g; d.out_ld = ld;
+    if (p.cls >= 0) {
+        d.out = g + ((size_t)py * Ws + px) * ld;
+        d.o_px = 2 * ld; d.o_row = 2 * Ws * ld; d.o_img = Hs * Ws * ld;
+    }
+    if (accumulate) { d.res = d.out; d.res_ld = ld; d.r_px = d.o_px; d.r_row = d.o_row; d.r_img = d.o_img; }
+    if (p.cls < 0) return p.k;
+    const int code = (1 + py) * 10 + (1 + px);      // window KH x KW as KH * 10 + KW; 1 x 1 is the plain 1x1 conv
+    return code == 11 ? 1 : code;
+}
 struct PackBatch {
     std::vector<PackJobDesc> jobs;
     PackJobDesc *dev = nullptr;
@@ -128,7 +178,6 @@ hipError_t launch_affine_bwd(const float *dz, const float *z, const float *y, co
                              unsigned *amax = nullptr);   // amax: max |z| / max |dy| folded into the slot (see ConvArgs::amax_in)
 // csum: scratch of affine_bwd_blocks(B, rows, C) * C * 2 floats -> csum_out[C] = column sums of dy (the conv bias gradient)
 int affine_bwd_blocks(int B, size_t rows_per_img, int C);
-hipError_t launch_add(float *a, const float *b, size_t n, hipStream_t st);
 size_t colsum_partial_floats(size_t rows, int ld);
 hipError_t launch_colsum(const float *x, size_t rows, int C, int ld, float *partial, float *out, hipStream_t st);
 hipError_t launch_colsum_final(const float *partial, int nb, int C, float *out, hipStream_t st);   // partial [nb][C][2] -> out[C]
@@ -143,8 +192,6 @@ hipError_t launch_deconv4_bwd_w(const float *in, const float *dout, int B, int H
                                 float *stats = nullptr);   // [B * H][C][2] (lazy `in` only): din masked by its ReLU + its BatchNorm-backward partials
 
 // ---- head / stem train kernels (kernels_head_train.hip)
-hipError_t launch_pack_conv_w_dgrad(const float *w, int Cout, int CinTotal, int k, int c_off, int Cs, int CsP, int CoutPad,
-                                    int cls, float *dst, hipStream_t st);
 // nz (both variants; may be null): [B][ceil(HW / 64)] words, bit h set when any row of head h is != 0.f in that aligned
 // 64-pixel tile of `out` -- the map launch_head_bwd / launch_head_dx skip all-zero tiles by
 hipError_t launch_dpred_pack(const float *const dpred[10], int ld, int B, int HW, float *out, hipStream_t st,

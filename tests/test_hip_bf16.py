@@ -415,6 +415,29 @@ def test_dgrad_on_the_bf16_pipe(mode, tol, case):
         assert e > 1e-5       # the bf16 kernel really ran
 
 
+def test_thin16_dgrad_on_the_fp16_pipe():
+    """the 16 -> 16 stride-1 data gradient in mode 3 through op_conv_dgrad, on the row-kernel shape id as the train plan
+    launches it (there csrc/conv_thin.hip takes it: the entry point gives the panel piece planes by the plan's rule, K % 8 == 0),
+    vs autograd in fp64 at the gate test_thin16_conv_on_the_fp16_pipe sets for that kernel at the same K = 144, and within
+    2e-6 of the same call in fp32 (the row kernel)"""
+    from hipmonocon.engine import Engine
+    B, H, W = 1, 6, 32
+    w = rnd(1400, "w", (16, 16, 3, 3), (2.0 / (9 * 16)) ** 0.5)
+    dy = rnd(1400, "dy", (B, 16, H, W))
+    x = torch.zeros(B, 16, H, W, dtype=torch.float64, requires_grad=True)
+    F.conv2d(x, w.double(), None, 1, 1).backward(dy.double())
+    eng = Engine()
+    try:
+        eng.set_conv_cfg(32)
+        eng.set_precision(3)
+        got = eng.op_conv_dgrad(nhwc(dy).cuda(), w.cuda(), (H, W), 0, 16, 1).cpu()
+        eng.set_precision(0)
+        base = eng.op_conv_dgrad(nhwc(dy).cuda(), w.cuda(), (H, W), 0, 16, 1).cpu()
+    finally:
+        eng.close()
+    assert rel_err(got.permute(0, 3, 1, 2), x.grad) < 5e-6
+    assert rel_err(got, base) < 2e-6
+
 
 # ----------------------------------------------------------------------------------------------- mode 3: operand scaling
 @pytest.mark.parametrize("xscale,wscale", [(1e-7, 1.0), (3e5, 1.0), (1.0, 1e-6), (2e4, 5e3), (1e-20, 1e12)],

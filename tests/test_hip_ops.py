@@ -225,13 +225,15 @@ DGRAD_CASES = [
     ("dg_s2_16_32", 1, 24, 32, 16, 0, 16, 32, 3, 2),
     ("dg_s2_256_512_tiny", 1, 8, 8, 256, 0, 256, 512, 3, 2),
     ("dg_head_576_64", 1, 8, 16, 64, 0, 64, 576, 3, 1),
+    ("dg_s1_16_16", 1, 6, 32, 16, 0, 16, 16, 3, 1),               # Cout % 32 != 0; the smallest map the 16-channel row kernels take
 ]
 
 
 @pytest.mark.parametrize("case", DGRAD_CASES, ids=[c[0] for c in DGRAD_CASES])
 def test_conv_dgrad(eng, case):
-    """data gradient through exactly the launches the train plan emits (transposed / flipped panel for stride 1,
-    output-parity classes scattering into dx for stride 2) vs autograd in fp64; then the accumulate form."""
+    """data gradient through the train plan's own packer and launch description (transposed / flipped panel for stride 1,
+    output-parity classes scattering into dx for stride 2; the workgroup shape is the handle's, and the plan's one-pass kernel
+    for level1's stride-2 gradient is not taken here) vs autograd in fp64; then the accumulate form."""
     name, B, H, W, cin_total, c_off, cs, cout, k, stride = case
     seed = 600 + DGRAD_CASES.index(case)
     Ho, Wo = (H + 2 * (k // 2) - k) // stride + 1, (W + 2 * (k // 2) - k) // stride + 1
@@ -249,3 +251,38 @@ def test_conv_dgrad(eng, case):
     eng.op_conv_dgrad(nhwc(dy).to(dev), w.to(dev), (H, W), c_off, cs, stride, accumulate_into=acc)
     assert rel_err(acc.cpu().permute(0, 3, 1, 2), ref + base.double()) < tol
 
+
+def misaligned(t):
+    """the same values as a contiguous view that starts 4 bytes into its storage"""
+    flat = torch.empty(t.numel() + 1, dtype=t.dtype, device=t.device)
+    v = flat[1:1 + t.numel()].view(t.shape)
+    v.copy_(t)
+    assert v.is_contiguous() and v.data_ptr() % 16 == 4
+    return v
+
+
+@pytest.mark.parametrize("mode", [0, 3], ids=["fp32", "f16x2"])
+def test_master_weight_four_bytes_off_alignment(eng, mode):
+    """op_conv and op_conv_dgrad at s1_64_64 with the master weight 4 bytes off 16-byte alignment: bit-identical to the same
+    call on an aligned copy.  Such a weight takes the packer's element-wise path (pack_batch_kernel and, in f16x2, the max-|w|
+    pass of the forward panel), which no bound model reaches: every parameter tensor is 16-byte aligned.  The data gradient in
+    f16x2 finds max |w| with the 16-byte-load pass of the activations, which refuses such a pointer: that stays an error."""
+    from hipmonocon.lib import MonoconHipError
+    B, H, W, C = 2, 16, 24, 64
+    dev = eng.device
+    x = nhwc(rnd(700, "x", (B, C, H, W))).to(dev)
+    dy = nhwc(rnd(700, "dy", (B, C, H, W))).to(dev)
+    w = rnd(700, "w", (C, C, 3, 3), (2.0 / (9 * C)) ** 0.5).to(dev)
+    w_off = misaligned(w)
+    assert w.data_ptr() % 16 == 0 and torch.equal(w, w_off)
+    try:
+        eng.set_precision(mode)
+        assert torch.equal(eng.op_conv([x], w_off, 1), eng.op_conv([x], w, 1))
+        want = eng.op_conv_dgrad(dy, w, (H, W), 0, C, 1)
+        if mode == 3:
+            with pytest.raises(MonoconHipError):
+                eng.op_conv_dgrad(dy, w_off, (H, W), 0, C, 1)
+        else:
+            assert torch.equal(eng.op_conv_dgrad(dy, w_off, (H, W), 0, C, 1), want)
+    finally:
+        eng.set_precision(0)
