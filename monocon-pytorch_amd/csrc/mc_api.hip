@@ -73,6 +73,24 @@ void *mc_param(mc_handle *h, const std::string &name, int64_t numel, int dtype) 
     return b.ptr;
 }
 
+ConvLayer &mc_conv_layer(mc_handle *h, const std::string &name, bool &ok) {
+    auto it = h->convs.find(name);
+    if (it == h->convs.end()) { ok = false; h->err = "no layer " + name; static ConvLayer d; return d; }
+    return it->second;
+}
+
+int mc_head_conv_args(mc_handle *h, PlanAlloc &mem, const Tensor &feat, float *hidden, ConvArgs &a) {
+    const ConvLayer &L = h->head3;
+    conv_fwd_args(a, L, {&feat}, h->prec);
+    a.bias = h->head_bias;
+    a.out = hidden; a.out_ld = L.cout;
+    a.cfg = L.cfg;
+    const int chunks = conv_chunks_per_image(a.cfg, a.Hout, a.Wout);
+    a.stats = mem.alloc((size_t)a.B * chunks * L.coutp * 2);
+    a.stat_shift = h->head_rm;
+    return chunks;
+}
+
 // ------------------------------------------------------------------------------ network graph
 namespace {
 struct GraphBuilder {
@@ -233,58 +251,49 @@ struct Builder {
         return t;
     }
 
-    Tensor conv(const ConvLayer &L, const std::vector<Tensor> &srcs, const Tensor *res, bool relu,
-                Tensor *into = nullptr, const float *scale = nullptr, const float *shift = nullptr,
-                bool use_layer_affine = true, float **stats_out = nullptr, const float *stat_shift = nullptr,
-                int *chunks_out = nullptr) {
-        const Tensor &s0 = srcs[0];
-        const int Ho = conv_out_dim(s0.H, L.ks, L.stride), Wo = conv_out_dim(s0.W, L.ks, L.stride);
-        Tensor out = into ? *into : alloc(s0.B, Ho, Wo, L.cout);
-        Op op{};
+    // a conv launch whose arguments op.ca holds, with its algorithmic cost
+    void push_conv(Op &op) {
+        const ConvArgs &a = op.ca;
         op.kind = OP_CONV;
+        const double out_elems = (double)a.B * a.Hout * a.Wout * a.Cout;
+        op.flops = 2.0 * out_elems * a.Cin * op.ks * op.ks;
+        op.bytes = 4.0 * ((double)a.B * a.Hin * a.Win * a.Cin + out_elems * (a.res ? 2 : 1));
+        pl->ops.push_back(op);
+    }
+
+    Tensor conv(const ConvLayer &L, const std::vector<const Tensor *> &srcs, const Tensor *res, bool relu) {
+        Op op{};
         op.ks = L.ks; op.stride = L.stride;
         ConvArgs &a = op.ca;
-        a.nsrc = (int)srcs.size();
-        int cin = 0;
-        double in_elems = 0;
-        for (int i = 0; i < a.nsrc; ++i) {
-            a.src[i].p = srcs[i].p;
-            a.src[i].C = srcs[i].C;
-            cin += srcs[i].C;
-            in_elems += (double)srcs[i].numel();
-        }
-        if (cin != L.cin) { ok = false; h->err = "channel mismatch at " + L.conv; }
-        a.B = s0.B; a.Hin = s0.H; a.Win = s0.W; a.Hout = Ho; a.Wout = Wo;
-        a.Cin = cin; a.Cout = L.cout; a.CoutP = L.coutp;
-        a.wpk = L.wpk;
-        a.wpk16 = L.wpk16; a.prec = h->prec;
-        if (h->prec == 3) {
-            for (int i = 0; i < a.nsrc; ++i) a.amax_in[i] = srcs[i].amax;
-            a.amax_w = L.w_amax;
-            a.amax_out = out.amax;
-        }
-        a.scale = use_layer_affine ? L.scale : scale;
-        a.bias = use_layer_affine ? L.shift : shift;
+        if (!conv_fwd_args(a, L, srcs, h->prec)) { ok = false; h->err = "channel mismatch at " + L.conv; }
+        Tensor out = alloc(a.B, a.Hout, a.Wout, L.cout);
+        a.amax_out = out.amax;
+        a.scale = L.scale; a.bias = L.shift;
         a.res = res ? res->p : nullptr;
         a.res_ld = res ? res->C : 0;
-        a.out = out.p; a.out_ld = out.C; a.out_coff = 0;
+        a.out = out.p; a.out_ld = out.C;
         a.relu = relu ? 1 : 0;
         a.cfg = L.cfg ? L.cfg : (ok ? mc_choose_conv_cfg(h, a, L.ks, L.stride) : CFG_128x32);
-        const int chunks = conv_chunks_per_image(a.cfg, Ho, Wo);
-        if (stats_out) {
-            *stats_out = mem.alloc((size_t)s0.B * chunks * L.coutp * 2);
-            a.stats = *stats_out;
-            a.stat_shift = stat_shift;
-            // per-patch centred second moments (head_attn_kernel combines them): whole 4x8 patches, no residual, and one partial
-            // per patch -- true of the head conv on any map the plan accepts (H, W multiples of 32: a quarter-resolution map of 8s)
-            a.stats_centred = 1;
-            if (res || Ho % 4 || Wo % 8 || chunks != (Ho / 4) * (Wo / 8)) { ok = false; h->err = "statistics of partial patches at " + L.conv; }
-        }
-        if (chunks_out) *chunks_out = chunks;
-        op.flops = 2.0 * s0.B * Ho * Wo * (double)L.cout * cin * L.ks * L.ks;
-        op.bytes = 4.0 * (in_elems + (double)s0.B * Ho * Wo * L.cout * (res ? 2 : 1));
-        pl->ops.push_back(op);
+        push_conv(op);
         return out;
+    }
+
+    // heads pass 1: the fused 3x3 64 -> 9x64 (+bias) with per-(image, patch, channel) statistics for head_attn_kernel
+    Tensor head_conv(const Tensor &feat) {
+        const ConvLayer &L = h->head3;
+        Tensor hidden = alloc(feat.B, feat.H, feat.W, L.cout);
+        Op op{};
+        op.ks = L.ks; op.stride = L.stride;
+        ConvArgs &a = op.ca;
+        pl->head_chunks = mc_head_conv_args(h, mem, feat, hidden.p, a);
+        pl->head_stats = a.stats;
+        a.amax_out = hidden.amax;
+        // per-patch centred second moments (head_attn_kernel combines them): whole 4x8 patches, no residual, and one partial
+        // per patch -- true of the head conv on any map the plan accepts (H, W multiples of 32: a quarter-resolution map of 8s)
+        a.stats_centred = 1;
+        if (a.Hout % 4 || a.Wout % 8 || pl->head_chunks != (a.Hout / 4) * (a.Wout / 8)) { ok = false; h->err = "statistics of partial patches at " + L.conv; }
+        push_conv(op);
+        return hidden;
     }
 
     Tensor pool(const Tensor &x) {
@@ -308,12 +317,6 @@ struct Builder {
         op.bytes = 4.0 * ((double)x.numel() + (double)o.numel());
         pl->ops.push_back(op);
         return o;
-    }
-
-    const ConvLayer &L(const std::string &n) {
-        auto it = h->convs.find(n);
-        if (it == h->convs.end()) { ok = false; h->err = "no layer " + n; static ConvLayer d; return d; }
-        return it->second;
     }
 };
 }  // namespace
@@ -427,9 +430,9 @@ static Plan *get_plan(mc_handle *h, int B, int H, int W) {
         if ((int)i == g.n_backbone) pl->n_backbone_ops = (int)pl->ops.size();
         if (s.dead) continue;
         if (s.kind == STEP_CONV) {
-            std::vector<Tensor> srcs;
-            for (int x : s.srcs) srcs.push_back(t[x]);
-            t[s.out] = bd.conv(bd.L(s.name), srcs, s.res >= 0 ? &t[s.res] : nullptr, s.relu);
+            std::vector<const Tensor *> srcs;
+            for (int x : s.srcs) srcs.push_back(&t[x]);
+            t[s.out] = bd.conv(mc_conv_layer(h, s.name, bd.ok), srcs, s.res >= 0 ? &t[s.res] : nullptr, s.relu);
         } else if (s.kind == STEP_POOL) {
             t[s.out] = bd.pool(t[s.srcs[0]]);
         } else {
@@ -442,20 +445,15 @@ static Plan *get_plan(mc_handle *h, int B, int H, int W) {
     pl->nodes = t;
     pl->n_neck_ops = (int)pl->ops.size();
 
-    // heads pass 1: fused 3x3 64 -> 9x64 (+bias) with per-(image,channel) statistics
-    float *stats = nullptr;
-    int chunks = 0;
-    Tensor hidden = bd.conv(h->head3, {feat}, nullptr, false, nullptr, nullptr, h->head_bias, false, &stats,
-                            h->head_rm, &chunks);
+    const Tensor hidden = bd.head_conv(feat);
     float *hs_scale = bd.mem.alloc((size_t)B * NUM_HEADS * HEAD_CH);
     float *hs_shift = bd.mem.alloc((size_t)B * NUM_HEADS * HEAD_CH);
     pl->hidden = hidden; pl->hs_scale = hs_scale; pl->hs_shift = hs_shift;
-    pl->head_stats = stats; pl->head_chunks = chunks;
     {
         Op op{};
         op.kind = OP_HEAD_ATTN;
-        op.in = stats; op.B = B; op.chunks = chunks; op.H = feat.H; op.W = feat.W;
-        op.out = hs_scale; op.shift = hs_shift;
+        op.in = pl->head_stats; op.B = B; op.chunks = pl->head_chunks; op.H = feat.H; op.W = feat.W;
+        op.out = hs_scale; op.out2 = hs_shift;
         pl->ops.push_back(op);
     }
     {
@@ -516,14 +514,10 @@ static int run_op(mc_handle *h, const Op &op, hipStream_t st) {
             HIPCHK(h, launch_deconv4(op.in, op.B, op.H, op.W, op.C, op.w, op.out, st, op.amax));
             break;
         case OP_HEAD_ATTN:
-            HIPCHK(h, launch_head_attn(op.in, op.B, op.chunks, op.H * op.W, h->hap, op.out,
-                                       const_cast<float *>(op.shift), st));
+            HIPCHK(h, launch_head_attn(op.in, op.B, op.chunks, op.H * op.W, h->hap, op.out, op.out2, st));
             break;
         case OP_HEAD_APPLY:
             HIPCHK(h, launch_head_apply(op.ha, st));
-            break;
-        case OP_TO_NCHW:
-            HIPCHK(h, launch_nhwc_to_nchw(op.in, op.B, op.C, op.H, op.W, op.out, st));
             break;
     }
     return 0;
@@ -667,18 +661,15 @@ int mc_pack_params(mc_handle *h, int train_mode, void *stream) {
         if (rebuild) h->folds.add(mc::FoldJobDesc{g, b, rm, rv, 1e-5f, 16, h->stem_scale, h->stem_shift});
     }
     // heads
-    const HeadRow *rows = head_rows();
-    const int *rb = head_row_begin();
-    (void)rows;
     CopyBatch headcb;      // the 1x1 head weights / biases -> the fused [65][64] / [65] tables, one launch
     CopyBatch headcb2;     // 3x3 head biases and AttnBN running means -> their concatenated tables
     for (int hd = 0; hd < NUM_HEADS && has_head; ++hd) {
-        const std::string pre = std::string("head.") + HEAD_NAMES[hd];
-        NEEDP(w3, pre + ".0.weight", 64 * 64 * 9);
-        NEEDP(b3, pre + ".0.bias", 64);
+        const HeadKeys keys = mc_head_keys(hd);
+        NEEDP(w3, keys.conv3 + ".weight", 64 * 64 * 9);
+        NEEDP(b3, keys.conv3 + ".bias", 64);
         if (rebuild) add_fwd(w3, 64, 64, 3, h->head3.wpk, h->head3.wpk16, 64, h->head3.coutp, hd * HEAD_CH, h->head3.w_amax);
         if (!headcb2.add(b3, h->head_bias + hd * HEAD_CH, 64)) return fail(h, "mc_pack_params: head copy table overflow");
-        const std::string an = pre + ".1";
+        const std::string &an = keys.attn;
         NEEDP(rm, an + ".running_mean", 64);
         NEEDP(rv, an + ".running_var", 64);
         if (!headcb2.add(rm, h->head_rm + hd * HEAD_CH, 64)) return fail(h, "mc_pack_params: head copy table overflow");
@@ -697,20 +688,10 @@ int mc_pack_params(mc_handle *h, int train_mode, void *stream) {
         h->hap.bias_[hd] = wb;
         h->hap.rm[hd] = rm;
         h->hap.rv[hd] = rv;
-        if (hd < 8) {
-            const int nr = rb[hd + 1] - rb[hd];
-            NEEDP(w1, pre + ".3.weight", (int64_t)nr * 64);
-            NEEDP(b1, pre + ".3.bias", nr);
-            if (!headcb.add(w1, h->head_w1 + (size_t)rb[hd] * HEAD_CH, (size_t)nr * 64) || !headcb.add(b1, h->head_b1 + rb[hd], nr))
-                return fail(h, "mc_pack_params: head copy table overflow");
-        } else {
-            NEEDP(wc, "head.dir_cls.0.weight", 12 * 64);
-            NEEDP(bc, "head.dir_cls.0.bias", 12);
-            NEEDP(wr, "head.dir_reg.0.weight", 12 * 64);
-            NEEDP(br, "head.dir_reg.0.bias", 12);
-            if (!headcb.add(wc, h->head_w1 + (size_t)rb[8] * HEAD_CH, 12 * 64) ||
-                !headcb.add(wr, h->head_w1 + (size_t)(rb[8] + 12) * HEAD_CH, 12 * 64) || !headcb.add(bc, h->head_b1 + rb[8], 12) ||
-                !headcb.add(br, h->head_b1 + rb[8] + 12, 12))
+        for (const HeadOutLayer &o : keys.out) {
+            NEEDP(w1, o.layer + ".weight", (int64_t)o.rows * HEAD_CH);
+            NEEDP(b1, o.layer + ".bias", o.rows);
+            if (!headcb.add(w1, h->head_w1 + (size_t)o.row0 * HEAD_CH, (size_t)o.rows * HEAD_CH) || !headcb.add(b1, h->head_b1 + o.row0, o.rows))
                 return fail(h, "mc_pack_params: head copy table overflow");
         }
     }
@@ -935,44 +916,42 @@ int mc_op_conv(mc_handle *h, const float *const src[], const int src_channels[],
         return fail(h, "mc_op_conv: unsupported k=%d stride=%d", ksize, stride);
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    ConvArgs a{};
-    int cin = 0;
+    Tensor x[4];
+    std::vector<const Tensor *> xs;
+    ConvLayer L;            // the temporary panel, described the way the plans describe a layer's
+    L.ks = ksize; L.stride = stride; L.cout = Cout; L.coutp = conv_coutp(Cout);
     for (int i = 0; i < nsrc; ++i) {
         if (!src[i] || src_channels[i] % 16) return fail(h, "mc_op_conv: source %d needs C %% 16 == 0", i);
-        a.src[i].p = src[i];
-        a.src[i].C = src_channels[i];
-        cin += src_channels[i];
+        x[i] = operand_tensor(src[i], B, Hin, Win, src_channels[i]);
+        xs.push_back(&x[i]);
+        L.cin += src_channels[i];
     }
-    a.nsrc = nsrc;
-    a.B = B; a.Hin = Hin; a.Win = Win;
-    a.Hout = conv_out_dim(Hin, ksize, stride);
-    a.Wout = conv_out_dim(Win, ksize, stride);
-    a.Cin = cin; a.Cout = Cout; a.CoutP = conv_coutp(Cout);
-    const size_t wn = fwd_panel_elems(ksize, cin, a.CoutP);
+    const size_t wn = fwd_panel_elems(ksize, L.cin, L.coutp);
     ScratchBuf wpk, wpk16;
     HIPCHK(h, wpk.alloc(wn * sizeof(float)));
     HIPCHK(h, hipMemsetAsync(wpk.p, 0, wn * sizeof(float), st));
-    a.wpk = wpk.as<float>();
+    L.wpk = wpk.as<float>();
     ScratchBuf slots;       // mode 3: max |x| of every source from a pass of its own; the pack finds max |w|
-    unsigned *w_amax = nullptr;
-    if (panel_has_pieces(h->prec, cin)) {
+    if (panel_has_pieces(h->prec, L.cin)) {
         if (h->prec == 3) {
             size_t n[4];
-            for (int i = 0; i < nsrc; ++i) n[i] = (size_t)B * Hin * Win * src_channels[i];
+            for (int i = 0; i < nsrc; ++i) n[i] = x[i].numel();
             HIPCHK(h, op_amax_slots(slots, src, n, nsrc, nullptr, 0, true, st));
-            for (int i = 0; i < nsrc; ++i) a.amax_in[i] = slots.as<unsigned>() + i * AMAX_WORDS;
-            a.amax_w = w_amax = slots.as<unsigned>() + 4 * AMAX_WORDS;
+            for (int i = 0; i < nsrc; ++i) x[i].amax = slots.as<unsigned>() + i * AMAX_WORDS;
+            L.w_amax = slots.as<unsigned>() + 4 * AMAX_WORDS;
         }
         const size_t bytes16 = wn * 2 * split_pieces(h->prec);
         HIPCHK(h, wpk16.alloc(bytes16));
         HIPCHK(h, hipMemsetAsync(wpk16.p, 0, bytes16, st));
-        a.wpk16 = wpk16.p; a.prec = h->prec;
+        L.wpk16 = wpk16.p;
     }
     PackBatch pack;         // the plans' packer, one job
-    pack.add(pack_job_fwd(weight_oihw, Cout, cin, ksize, wpk.as<float>(), wpk16.p, cin, a.CoutP, 0, h->prec, w_amax));
+    pack.add(pack_job_fwd(weight_oihw, Cout, L.cin, ksize, L.wpk, L.wpk16, L.cin, L.coutp, 0, h->prec, L.w_amax));
     HIPCHK(h, pack.launch(st, h->prec == 3));
+    ConvArgs a{};
+    conv_fwd_args(a, L, xs, h->prec);
     a.scale = scale; a.bias = bias; a.res = residual; a.res_ld = Cout;
-    a.out = out; a.out_ld = Cout; a.out_coff = 0; a.relu = relu;
+    a.out = out; a.out_ld = Cout; a.relu = relu;
     a.cfg = h->force_cfg;
     hipError_t e = launch_conv(a, ksize, stride, st);
     hipError_t e2 = hipStreamSynchronize(st);   // test entry point: the packed weights are a temporary
@@ -1115,7 +1094,6 @@ int mc_bench_conv(mc_handle *h, int B, int Hin, int Win, int nsrc, const int src
     if (!h || !src_channels || !ms_avg) return fail(h, "mc_bench_conv: null argument");
     HIPCHK(h, hipSetDevice(h->device));
     ConvArgs a{};
-    int cin = 0;
     std::vector<void *> bufs;
     // MONOCON_BENCH_ZERO=1: all-zero operands (same instruction stream, minimal toggling): how much of a launch's time is
     // the power limit (DVFS) rather than stalls
@@ -1132,34 +1110,35 @@ int mc_bench_conv(mc_handle *h, int B, int Hin, int Win, int nsrc, const int src
             (void)hipMemcpy((float *)q + off, hst.data(), std::min(hst.size(), n - off) * sizeof(float), hipMemcpyHostToDevice);
         return (float *)q;
     };
+    Tensor x[4];
+    std::vector<const Tensor *> xs;
+    ConvLayer L;            // the synthetic panel, described the way the plans describe a layer's
+    L.ks = ksize; L.stride = stride; L.cout = Cout; L.coutp = conv_coutp(Cout);
     for (int i = 0; i < nsrc; ++i) {
-        a.src[i].C = src_channels[i];
-        a.src[i].p = alloc_fill((size_t)B * Hin * Win * src_channels[i], 1.0f);
-        if (!a.src[i].p) return fail(h, "mc_bench_conv: out of memory");
-        cin += src_channels[i];
+        x[i] = operand_tensor(alloc_fill((size_t)B * Hin * Win * src_channels[i], 1.0f), B, Hin, Win, src_channels[i]);
+        if (!x[i].p) return fail(h, "mc_bench_conv: out of memory");
+        xs.push_back(&x[i]);
+        L.cin += src_channels[i];
     }
-    a.nsrc = nsrc;
-    a.B = B; a.Hin = Hin; a.Win = Win;
-    a.Hout = conv_out_dim(Hin, ksize, stride);
-    a.Wout = conv_out_dim(Win, ksize, stride);
-    a.Cin = cin; a.Cout = Cout; a.CoutP = conv_coutp(Cout);
-    a.wpk = alloc_fill((size_t)ksize * ksize * cin * a.CoutP, 0.05f);
+    const int Ho = conv_out_dim(Hin, ksize, stride), Wo = conv_out_dim(Win, ksize, stride);
+    const size_t wn = fwd_panel_elems(ksize, L.cin, L.coutp), on = (size_t)B * Ho * Wo * Cout;
+    const size_t stats_n = (size_t)B * conv_chunks_per_image(CFG_AUTO, Ho, Wo) * L.coutp * 2;     // one partial per 4x8 patch
+    L.wpk = alloc_fill(wn, 0.05f);
     a.scale = alloc_fill(Cout, 1.0f);
     a.bias = alloc_fill(Cout, 1.0f);
-    a.out = alloc_fill((size_t)B * a.Hout * a.Wout * Cout, 0.0f);
-    if (!a.wpk || !a.scale || !a.bias || !a.out) return fail(h, "mc_bench_conv: out of memory");
+    a.out = alloc_fill(on, 0.0f);
+    if (!L.wpk || !a.scale || !a.bias || !a.out) return fail(h, "mc_bench_conv: out of memory");
     a.out_ld = Cout; a.relu = 1; a.cfg = cfg;
     // MONOCON_BENCH_STATS=1: the train-mode forward's statistics partials; MONOCON_BENCH_BM=1 / 2: the backward-statistics
     // epilogue (mask recomputed from y / read from a stored activation), =3: the latter with an accumulated gradient
     if (const char *e = std::getenv("MONOCON_BENCH_STATS")) {
-        if (std::atoi(e)) a.stats = alloc_fill((size_t)B * ((a.Hout + 3) / 4) * ((a.Wout + 7) / 8) * a.CoutP * 2, 0.f);
+        if (std::atoi(e)) a.stats = alloc_fill(stats_n, 0.f);
     }
     if (const char *e = std::getenv("MONOCON_BENCH_BM")) {
         const int m = std::atoi(e);
         if (m) {
-            const size_t on = (size_t)B * a.Hout * a.Wout * Cout;
             a.relu = 0;
-            a.stats = alloc_fill((size_t)B * ((a.Hout + 3) / 4) * ((a.Wout + 7) / 8) * a.CoutP * 2, 0.f);
+            a.stats = alloc_fill(stats_n, 0.f);
             a.bm_y = alloc_fill(on, 1.0f);
             a.bm_a = a.scale; a.bm_b = a.bias; a.bm_relu = m == 1 ? 2 : 1;
             if (m >= 2) a.bm_z = alloc_fill(on, 1.0f);
@@ -1167,8 +1146,7 @@ int mc_bench_conv(mc_handle *h, int B, int Hin, int Win, int nsrc, const int src
             if (!a.stats || !a.bm_y || (m >= 2 && !a.bm_z) || (m >= 3 && !a.res)) return fail(h, "mc_bench_conv: out of memory");
         }
     }
-    if (h->prec >= 1 && cin % 32 == 0) {        // bf16 / fp16 pipe: piece panels (random finite bit patterns) + unit maxima
-        const size_t wn = (size_t)ksize * ksize * cin * a.CoutP;
+    if (h->prec >= 1 && L.cin % 32 == 0) {        // bf16 / fp16 pipe: piece panels (random finite bit patterns) + unit maxima
         std::vector<unsigned short> hw(wn * 3);
         unsigned s16 = 777u;
         for (auto &v : hw) { s16 = s16 * 1664525u + 1013904223u; v = zero_data ? 0 : (unsigned short)(0x2c00u + ((s16 >> 12) & 0x3ffu) + ((s16 >> 31) << 15)); }
@@ -1176,14 +1154,15 @@ int mc_bench_conv(mc_handle *h, int B, int Hin, int Win, int nsrc, const int src
         if (hipMalloc(&q, hw.size() * 2) != hipSuccess) return fail(h, "mc_bench_conv: out of memory");
         bufs.push_back(q);
         (void)hipMemcpy(q, hw.data(), hw.size() * 2, hipMemcpyHostToDevice);
-        a.wpk16 = q; a.prec = h->prec;
+        L.wpk16 = q;
         std::vector<unsigned> one((size_t)5 * AMAX_WORDS, 0x3f800000u);
         if (hipMalloc(&q, one.size() * 4) != hipSuccess) return fail(h, "mc_bench_conv: out of memory");
         bufs.push_back(q);
         (void)hipMemcpy(q, one.data(), one.size() * 4, hipMemcpyHostToDevice);
-        for (int i = 0; i < nsrc; ++i) a.amax_in[i] = static_cast<unsigned *>(q) + (size_t)i * AMAX_WORDS;
-        a.amax_w = static_cast<unsigned *>(q) + (size_t)4 * AMAX_WORDS;
+        for (int i = 0; i < nsrc; ++i) x[i].amax = static_cast<unsigned *>(q) + (size_t)i * AMAX_WORDS;
+        L.w_amax = static_cast<unsigned *>(q) + (size_t)4 * AMAX_WORDS;
     }
+    conv_fwd_args(a, L, xs, h->prec);
 #ifdef MC_PHASE_TIMERS
     const size_t prof_n = (size_t)1 << 22;          // (workgroups x waves x 5) upper bound
     {

@@ -46,8 +46,19 @@ struct Tensor {   // NHWC activation
     float *p = nullptr;
     int B = 0, H = 0, W = 0, C = 0;
     unsigned *amax = nullptr;   // slot receiving max |x| of the tensor (precision mode 3: operand scale of its consumers)
+    // LAZY activation (train plans of precision mode 3; always null in eval plans): the post-BatchNorm map
+    // z = act(la[c] * y + lb[c]) is never written -- p is the producing layer's raw conv output y, and every consumer forms z
+    // while it loads its operand (ConvSrc::la in conv_mfma.h; act = ReLU when lrelu).  null: p holds the values.
+    const float *la = nullptr, *lb = nullptr;
+    bool lrelu = true;
     size_t numel() const { return (size_t)B * H * W * C; }
 };
+// a caller's (B, H, W, C) map as an operand of a launch description (the op-level entry points; such a tensor is only read)
+inline Tensor operand_tensor(const float *p, int B, int H, int W, int C) {
+    Tensor t;
+    t.p = const_cast<float *>(p); t.B = B; t.H = H; t.W = W; t.C = C;
+    return t;
+}
 
 struct ConvLayer {
     std::string conv, bn;   // state_dict prefixes ("" bn => bias-only / raw)
@@ -58,6 +69,49 @@ struct ConvLayer {
     unsigned *w_amax = nullptr;   // max |w| of the master weight(s) (mode 3: the panel's power-of-two scale)
 };
 
+// The operands and geometry of the forward conv of layer L over the virtual concat of srcs (1..4 maps of one size) in precision
+// mode prec: every field of `a` that follows from them -- sources, sizes, panels, a.prec (the mode where L has piece planes, 0
+// otherwise) and in mode 3 the max-|x| slots of the operands.  Everything else is left as it is: the shape id and the epilogue
+// (scale, bias, res, relu, out, stats, amax_out, cfg) are the caller's, and a caller that has changed a source (TB::materialise)
+// calls again.  false: the sources do not add up to L.cin channels.  (The data gradient's counterpart: dgrad_conv_args, train.h.)
+inline bool conv_fwd_args(ConvArgs &a, const ConvLayer &L, const std::vector<const Tensor *> &srcs, int prec) {
+    const Tensor &s0 = *srcs[0];
+    a.nsrc = (int)srcs.size();
+    a.Cin = 0;
+    for (int i = 0; i < a.nsrc; ++i) {
+        a.src[i] = ConvSrc{srcs[i]->p, srcs[i]->C, srcs[i]->la, srcs[i]->lb};
+        a.Cin += srcs[i]->C;
+    }
+    a.B = s0.B; a.Hin = s0.H; a.Win = s0.W;
+    a.Hout = conv_out_dim(s0.H, L.ks, L.stride); a.Wout = conv_out_dim(s0.W, L.ks, L.stride);
+    a.Cout = L.cout; a.CoutP = L.coutp; a.wpk = L.wpk;
+    a.wpk16 = L.wpk16; a.prec = L.wpk16 ? prec : 0;
+    if (a.prec == 3) {
+        for (int i = 0; i < a.nsrc; ++i) a.amax_in[i] = srcs[i]->amax;
+        a.amax_w = L.w_amax;
+    }
+    return a.Cin == L.cin;
+}
+// The weight gradient of a ks x ks conv of the given stride in precision mode prec: X = the virtual concat of srcs, dY = the
+// first Cout of dy's dy_ld channels.  Fills sources, sizes and max-|x| slots and plans the tiling (wgrad_plan); `partial` stays
+// the caller's.  A caller that has changed a source calls again (the tiling does not depend on what a source holds).
+inline void wgrad_args(WgradArgs &a, const std::vector<const Tensor *> &srcs, const Tensor &dy, int dy_ld, int Cout, int ks,
+                       int stride, int prec) {
+    const Tensor &s0 = *srcs[0];
+    a.nsrc = (int)srcs.size();
+    a.Cin = 0;
+    for (int i = 0; i < a.nsrc; ++i) {
+        a.src[i] = ConvSrc{srcs[i]->p, srcs[i]->C, srcs[i]->la, srcs[i]->lb};
+        a.amax_x[i] = srcs[i]->amax;
+        a.Cin += srcs[i]->C;
+    }
+    a.amax_dy = dy.amax;
+    a.B = s0.B; a.Hin = s0.H; a.Win = s0.W; a.Hout = dy.H; a.Wout = dy.W; a.Cout = Cout;
+    a.dy = dy.p; a.dy_ld = dy_ld;
+    a.prec = prec;
+    wgrad_plan(a, ks, stride);
+}
+
 struct DeconvLayer {
     std::string name;
     int C = 0;
@@ -67,6 +121,17 @@ struct DeconvLayer {
 constexpr const char *HEAD_NAMES[NUM_HEADS] = {"heatmap_head", "wh_head", "offset_head", "center2kpt_offset_head",
                                                "kpt_heatmap_head", "kpt_heatmap_offset_head", "dim_head", "depth_head",
                                                "dir_feat"};
+// The state_dict prefixes of head hd: its 3x3 conv, its AttnBN, and its 1x1 output layers with their rows of the fused
+// [NUM_OUT_ROWS][HEAD_CH] table (head_row_begin()) -- one layer, or for the last head (dir_feat) dir_cls and dir_reg, half each
+struct HeadOutLayer { std::string layer; int row0, rows; };
+struct HeadKeys { std::string conv3, attn; std::vector<HeadOutLayer> out; };
+inline HeadKeys mc_head_keys(int hd) {
+    const std::string pre = std::string("head.") + HEAD_NAMES[hd];
+    const int r0 = head_row_begin()[hd], nr = head_row_begin()[hd + 1] - r0;
+    HeadKeys k{pre + ".0", pre + ".1", {{pre + ".3", r0, nr}}};
+    if (hd == NUM_HEADS - 1) k.out = {{"head.dir_cls.0", r0, nr / 2}, {"head.dir_reg.0", r0 + nr / 2, nr / 2}};
+    return k;
+}
 
 // The backbone (DLA-34) and neck (DLAUp) as one list of steps in forward order, from the stem's output (node 0) to `feat`.
 // Built once per handle (build_layers): the layer table, the eval plan and the train plan are all derived from it.  Every
@@ -121,8 +186,14 @@ struct PlanAlloc {
 // A bound tensor checked against what a plan reads: `dtype` (MC_F32; MC_I64 for num_batches_tracked) and `numel`
 // elements, also for "<key>#grad" buffers.  Missing or mismatched: h->err names the key, null is returned.
 void *mc_param(mc_handle *h, const std::string &name, int64_t numel, int dtype = MC_F32);
+// The layer-table entry `name`.  Missing: h->err names it, `ok` is cleared and an empty layer is returned.
+ConvLayer &mc_conv_layer(mc_handle *h, const std::string &name, bool &ok);
+// The fused head conv (64 -> 9 x 64, 3x3) of a plan on `feat` into `hidden`: head3's panels and shape id, head_bias, and the
+// per-patch statistics of (v - head_rm), whose buffer it takes from `mem`: [B][patches per image][head3.coutp][2] (a.stats).
+// Returns the patches per image.
+int mc_head_conv_args(mc_handle *h, PlanAlloc &mem, const Tensor &feat, float *hidden, ConvArgs &a);
 
-enum OpKind { OP_STEM, OP_CONV, OP_POOL, OP_DECONV, OP_HEAD_ATTN, OP_HEAD_APPLY, OP_TO_NCHW };
+enum OpKind { OP_STEM, OP_CONV, OP_POOL, OP_DECONV, OP_HEAD_ATTN, OP_HEAD_APPLY };
 
 struct Op {
     OpKind kind;
@@ -131,7 +202,7 @@ struct Op {
     int ks = 0, stride = 0;
     // generic
     const float *in = nullptr;
-    float *out = nullptr;
+    float *out = nullptr, *out2 = nullptr;   // out2: OP_HEAD_ATTN's second output (the AttnBN shift beside the scale)
     const float *w = nullptr, *scale = nullptr, *shift = nullptr;
     int B = 0, H = 0, W = 0, C = 0;
     int chunks = 0;

@@ -169,27 +169,24 @@ int mc_op_conv_wgrad(mc_handle *h, const float *const src[], const int src_chann
     if (Cout % 4) return fail(h, "mc_op_conv_wgrad: Cout must be a multiple of 4");
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    mc::WgradArgs a{};
-    int cin = 0;
+    Tensor x[4];
+    std::vector<const Tensor *> xs;
     for (int i = 0; i < nsrc; ++i) {
         if (!src[i] || src_channels[i] % 16) return fail(h, "mc_op_conv_wgrad: source %d needs C %% 16 == 0", i);
-        a.src[i].p = src[i]; a.src[i].C = src_channels[i];
-        cin += src_channels[i];
+        x[i] = operand_tensor(src[i], B, Hin, Win, src_channels[i]);
+        xs.push_back(&x[i]);
     }
-    a.nsrc = nsrc; a.B = B; a.Hin = Hin; a.Win = Win;
-    a.Hout = mc::conv_out_dim(Hin, ksize, stride);
-    a.Wout = mc::conv_out_dim(Win, ksize, stride);
-    a.Cin = cin; a.Cout = Cout; a.dy = dy; a.dy_ld = Cout;
-    a.prec = h->prec;
+    Tensor dyt = operand_tensor(dy, B, mc::conv_out_dim(Hin, ksize, stride), mc::conv_out_dim(Win, ksize, stride), Cout);
     ScratchBuf slots;       // mode 3: max |x| of every source and of dY
     if (h->prec == 3) {
         size_t n[4];
-        for (int i = 0; i < nsrc; ++i) n[i] = (size_t)B * Hin * Win * src_channels[i];
-        HIPCHK(h, op_amax_slots(slots, src, n, nsrc, dy, (size_t)B * a.Hout * a.Wout * Cout, false, st));
-        for (int i = 0; i < nsrc; ++i) a.amax_x[i] = slots.as<unsigned>() + i * mc::AMAX_WORDS;
-        a.amax_dy = slots.as<unsigned>() + 4 * mc::AMAX_WORDS;
+        for (int i = 0; i < nsrc; ++i) n[i] = x[i].numel();
+        HIPCHK(h, op_amax_slots(slots, src, n, nsrc, dy, dyt.numel(), false, st));
+        for (int i = 0; i < nsrc; ++i) x[i].amax = slots.as<unsigned>() + i * mc::AMAX_WORDS;
+        dyt.amax = slots.as<unsigned>() + 4 * mc::AMAX_WORDS;
     }
-    mc::wgrad_plan(a, ksize, stride);
+    mc::WgradArgs a{};
+    wgrad_args(a, xs, dyt, Cout, Cout, ksize, stride, h->prec);
     void *part = nullptr;
     HIPCHK(h, hipMalloc(&part, mc::wgrad_partial_floats(a, ksize) * sizeof(float)));
     a.partial = static_cast<float *>(part);

@@ -98,12 +98,8 @@ struct TNode {
     float *g = nullptr;
     bool ginit = false, needs_grad = true;
     LastWriter last;
-    // LAZY activation (precision mode 3): the post-BatchNorm map z = act(la[c] * y + lb[c]) is never written --
-    // t.p is the producing layer's raw conv output y, and every consumer forms z while it loads its operand (ConvSrc::la
-    // in conv_mfma.h; act = ReLU when lrelu).  null: t.p holds the values.  TB::materialise() turns a lazy node into a
-    // stored one (an affine_act pass appended to the forward) for a consumer that cannot form it.
-    const float *la = nullptr, *lb = nullptr;
-    bool lrelu = true;
+    // (t may be a LAZY activation, Tensor::la: TB::materialise() turns such a node into a stored one -- an affine_act pass
+    // appended to the forward -- for a consumer that cannot form it)
 };
 
 enum RecKind { REC_STEM, REC_CONV, REC_POOL, REC_DECONV, REC_HEAD };
@@ -276,10 +272,10 @@ struct TB {   // train plan builder
     // here on; earlier consumers keep reading y).  Its max-|z| slot already holds bn_finalize's bound.
     void materialise(int node_i) {
         TNode &n = ts->nodes[node_i];
-        if (!n.la) return;
+        if (!n.t.la) return;
         float *z = alloc(n.t.numel());
-        const float *y = n.t.p, *la = n.la, *lb = n.lb;
-        const int B = n.t.B, C = n.t.C, rl = n.lrelu ? 1 : 0;
+        const float *y = n.t.p, *la = n.t.la, *lb = n.t.lb;
+        const int B = n.t.B, C = n.t.C, rl = n.t.lrelu ? 1 : 0;
         const size_t rows = (size_t)n.t.H * n.t.W;
         ts->fwd.push_back([=](mc_handle *hh, hipStream_t st) {
             HIPCHK(hh, launch_affine_act(y, la, lb, nullptr, B, rows, C, 0, rl, z, st, nullptr));
@@ -287,12 +283,18 @@ struct TB {   // train plan builder
         });
         if (sw.plan_debug)
             fprintf(stderr, "[plan] lazy node %d (%d ch %dx%d) materialised for a consumer that cannot form it on load\n", node_i, C, n.t.H, n.t.W);
-        n.t.p = z; n.la = n.lb = nullptr;
+        n.t.p = z; n.t.la = n.t.lb = nullptr;
         ++n_materialised;
     }
-    void fill_src(ConvSrc &s, int node_i) {
-        const TNode &n = ts->nodes[node_i];
-        s.p = n.t.p; s.C = n.t.C; s.la = n.la; s.lb = n.lb;
+    // a conv (or its weight gradient) forms ReLU'd lazy maps only: any other lazy source is stored first.  Returns the
+    // sources as the launch descriptions take them (valid until the next node() call)
+    std::vector<const Tensor *> conv_sources(const std::vector<int> &srcs) {
+        std::vector<const Tensor *> t;
+        for (int s_ : srcs) {
+            if (ts->nodes[s_].t.la && !ts->nodes[s_].t.lrelu) materialise(s_);
+            t.push_back(&ts->nodes[s_].t);
+        }
+        return t;
     }
     int node(int B, int H, int W, int C, bool needs_grad = true, bool storage = true) {
         TNode n;
@@ -313,11 +315,6 @@ struct TB {   // train plan builder
     float *P(const std::string &name, int64_t numel) { return static_cast<float *>(bound(name, numel, MC_F32)); }
     float *G(const std::string &name, int64_t numel) { return P(name + "#grad", numel); }
     long long *NBT(const std::string &name) { return static_cast<long long *>(bound(name, 1, MC_I64)); }
-    ConvLayer &L(const std::string &n) {
-        auto it = h->convs.find(n);
-        if (it == h->convs.end()) { ts->ok = false; h->err = "no layer " + n; static ConvLayer d; return d; }
-        return it->second;
-    }
 
     double *fold_scratch(int nb, int C) {
         const size_t nd = partial_fold_doubles(nb, C);
@@ -375,13 +372,13 @@ struct TB {   // train plan builder
         bn_train_ops(r.y, stats, nb, cstride, r.bn, 1e-5f, 0.1f, ca, cb, r.mean, r.rstd, ymax, lazy ? ts->nodes[r.z].t.amax : nullptr, rl);
         if (lazy) {
             TNode &zn = ts->nodes[r.z];
-            zn.t.p = r.y.p; zn.la = ca; zn.lb = cb; zn.lrelu = r.relu;
+            zn.t.p = r.y.p; zn.t.la = ca; zn.t.lb = cb; zn.t.lrelu = r.relu;
             ++n_lazy;
         } else if (!r.dead) {
             const TNode &rn = ts->nodes[res >= 0 ? res : 0];
             const float *yp = r.y.p, *rp = res >= 0 ? rn.t.p : nullptr;
-            const float *ra = res >= 0 ? rn.la : nullptr, *rb = res >= 0 ? rn.lb : nullptr;     // the residual may be lazy
-            const int rrelu = (res >= 0 && rn.lrelu) ? 1 : 0;
+            const float *ra = res >= 0 ? rn.t.la : nullptr, *rb = res >= 0 ? rn.t.lb : nullptr;     // the residual may be lazy
+            const int rrelu = (res >= 0 && rn.t.lrelu) ? 1 : 0;
             float *zp = ts->nodes[r.z].t.p;
             unsigned *zmax = ts->nodes[r.z].t.amax;
             const size_t rows = (size_t)r.y.H * r.y.W;
@@ -433,7 +430,7 @@ struct TB {   // train plan builder
     }
 
     int conv_bn(const NetStep &s) {
-        ConvLayer &Lr = L(s.name);
+        ConvLayer &Lr = mc_conv_layer(h, s.name, ts->ok);
         const std::vector<int> &srcs = s.srcs;
         const int res = s.res;
         // the neck's LAST node is `feat` (NetStep::never_lazy): its consumers are the fused 64 -> 576 head conv and that conv's
@@ -462,24 +459,13 @@ struct TB {   // train plan builder
                           (!relu || s.elementwise_consumers || (long long)Ho * Wo * Lr.cout >= sw.lazy_min);
         r.z = dead ? -1 : node(B, Ho, Wo, Lr.cout, true, !lazy);
         ConvArgs a{};
-        a.nsrc = (int)srcs.size();
-        int cin = 0;
-        for (int i = 0; i < a.nsrc; ++i) {
-            if (ts->nodes[srcs[i]].la && !ts->nodes[srcs[i]].lrelu) materialise(srcs[i]);     // (a conv forms ReLU'd maps only)
-            fill_src(a.src[i], srcs[i]);
-            cin += a.src[i].C;
-        }
-        if (cin != Lr.cin) { ts->ok = false; h->err = "train plan: channel mismatch at " + Lr.conv; }
-        a.B = B; a.Hin = s0.H; a.Win = s0.W; a.Hout = Ho; a.Wout = Wo; a.Cin = cin; a.Cout = Lr.cout; a.CoutP = Lr.coutp;
-        a.wpk = Lr.wpk; a.out = r.y.p; a.out_ld = Lr.cout;
-        a.wpk16 = Lr.wpk16; a.prec = h->prec;
-        if (h->prec == 3) {
-            for (int i = 0; i < a.nsrc; ++i) a.amax_in[i] = ts->nodes[srcs[i]].t.amax;
-            a.amax_w = Lr.w_amax;
-        }
+        const std::vector<const Tensor *> xs = conv_sources(srcs);
+        if (!conv_fwd_args(a, Lr, xs, h->prec)) { ts->ok = false; h->err = "train plan: channel mismatch at " + Lr.conv; }
         if (conv_any_lazy(a) && !conv_lazy_capable(a, Lr.ks, Lr.stride)) {
-            for (int i = 0; i < a.nsrc; ++i) { materialise(srcs[i]); fill_src(a.src[i], srcs[i]); }
+            for (int s_ : srcs) materialise(s_);
+            conv_fwd_args(a, Lr, xs, h->prec);
         }
+        a.out = r.y.p; a.out_ld = Lr.cout;
         unsigned *yslot = lazy ? slot() : nullptr;      // max |y|, left by the conv's epilogue: bn_finalize bounds max |z| with it
         a.amax_out = yslot;
         a.cfg = ts->ok ? mc_choose_conv_cfg(h, a, Lr.ks, Lr.stride) : CFG_128x32;
@@ -496,11 +482,11 @@ struct TB {   // train plan builder
 
     int pool(int x) {
         const Tensor t = ts->nodes[x].t;           // by value (see conv_bn)
-        if (ts->nodes[x].la && !ts->nodes[x].lrelu) materialise(x);
+        if (ts->nodes[x].t.la && !ts->nodes[x].t.lrelu) materialise(x);
         const Tensor tx = ts->nodes[x].t;
         const int o = node(t.B, t.H / 2, t.W / 2, t.C, true);
         ts->nodes[o].t.amax = t.amax;          // max |pool(x)| <= max |x|: the input's slot serves
-        const float *ip = tx.p, *la = ts->nodes[x].la, *lb = ts->nodes[x].lb;      // (lazy x: pooled over relu(la * y + lb))
+        const float *ip = tx.p, *la = tx.la, *lb = tx.lb;      // (lazy x: pooled over relu(la * y + lb))
         float *op = ts->nodes[o].t.p;
         const int B = t.B, H = t.H, W = t.W, C = t.C;
         ts->fwd.push_back([=](mc_handle *hh, hipStream_t st) {
@@ -514,10 +500,10 @@ struct TB {   // train plan builder
     }
 
     int deconv(DeconvLayer &D, int x) {
-        if (ts->nodes[x].la && !ts->nodes[x].lrelu) materialise(x);
+        if (ts->nodes[x].t.la && !ts->nodes[x].t.lrelu) materialise(x);
         const Tensor t = ts->nodes[x].t;           // by value (see conv_bn)
         const int o = node(t.B, t.H * 2, t.W * 2, t.C, true);
-        const float *ip = t.p, *w = D.wpk, *la = ts->nodes[x].la, *lb = ts->nodes[x].lb;
+        const float *ip = t.p, *w = D.wpk, *la = t.la, *lb = t.lb;
         float *op = ts->nodes[o].t.p;
         unsigned *omax = ts->nodes[o].t.amax;
         const int B = t.B, H = t.H, W = t.W, C = t.C;
@@ -603,28 +589,11 @@ struct TB {   // train plan builder
     // the weight gradient of a conv, on the weight-gradient stream: dy is not written again in this step.  Returns its step.
     int emit_wgrad(const std::vector<int> &srcs, const Tensor &dy, int dy_ld, int Cout, int ks, int stride, float *dw) {
         WgradArgs a{};
-        a.nsrc = (int)srcs.size();
-        auto fill = [&] {
-            int cin = 0;
-            for (int i = 0; i < a.nsrc; ++i) {
-                fill_src(a.src[i], srcs[i]);
-                a.amax_x[i] = ts->nodes[srcs[i]].t.amax;
-                cin += a.src[i].C;
-            }
-            return cin;
-        };
-        for (int s_ : srcs)
-            if (ts->nodes[s_].la && !ts->nodes[s_].lrelu) materialise(s_);
-        int cin = fill();
-        a.amax_dy = dy.amax;
-        const Tensor &s0 = ts->nodes[srcs[0]].t;
-        a.B = s0.B; a.Hin = s0.H; a.Win = s0.W; a.Hout = dy.H; a.Wout = dy.W; a.Cin = cin; a.Cout = Cout;
-        a.dy = dy.p; a.dy_ld = dy_ld;
-        a.prec = h->prec;
-        wgrad_plan(a, ks, stride);
+        const std::vector<const Tensor *> xs = conv_sources(srcs);
+        wgrad_args(a, xs, dy, dy_ld, Cout, ks, stride, h->prec);
         if (wgrad_any_lazy(a) && !wgrad_lazy_capable(a, ks, stride)) {      // X is read by a kernel that cannot form it: store it after all
             for (int s_ : srcs) materialise(s_);
-            fill();
+            wgrad_args(a, xs, dy, dy_ld, Cout, ks, stride, h->prec);
         }
         a.partial = alloc(wgrad_partial_floats(a, ks));
         return push_bwd([=](mc_handle *hh, hipStream_t st) { HIPCHK(hh, launch_wgrad(a, ks, stride, dw, st)); return 0; }, ON_SIDE);
@@ -714,7 +683,7 @@ struct TB {   // train plan builder
         }
         // ... or by the fused backward of the depthwise deconv that is its only consumer (neck proj -> up): same contract
         float **ds = last.kind == LastWriter::DECONV_BWD ? last.deconv_stats : nullptr;
-        if (ds && relu == 2 && zn.la == fa && zn.lb == fb && !*ds && !caller_forms_dy && !gres) {
+        if (ds && relu == 2 && zn.t.la == fa && zn.t.lb == fb && !*ds && !caller_forms_dy && !gres) {
             const int nbp = B * r.y.H;            // one workgroup per (image, row) of the deconv's input
             float *partial = alloc((size_t)nbp * C * 2);
             *ds = partial;
@@ -740,7 +709,7 @@ struct TB {   // train plan builder
         Tensor raw; raw.B = B; raw.H = fh; raw.W = fw; raw.C = LD; raw.p = alloc(raw.numel());
         raw_numel = raw.numel();
         for (int hd = 0; hd < NUM_HEADS; ++hd) {
-            const std::string an = std::string("head.") + HEAD_NAMES[hd] + ".1";
+            const std::string an = mc_head_keys(hd).attn;
             const int A = NUM_AFFINE, AC = NUM_AFFINE * HEAD_CH;
             at.rm[hd] = P(an + ".running_mean", HEAD_CH); at.rv[hd] = P(an + ".running_var", HEAD_CH);
             at.nbt[hd] = NBT(an + ".num_batches_tracked");
@@ -757,22 +726,13 @@ struct TB {   // train plan builder
             gp.d_att_b[hd] = G(an + ".attn_weights.attention.1.bias", A);
         }
         ConvArgs c3{};
-        c3.nsrc = 1;
-        fill_src(c3.src[0], feat);
-        const TNode &fn = ts->nodes[feat];
-        c3.B = B; c3.Hin = fh; c3.Win = fw; c3.Hout = fh; c3.Wout = fw; c3.Cin = 64; c3.Cout = CP; c3.CoutP = h->head3.coutp;
-        c3.wpk = h->head3.wpk; c3.bias = h->head_bias; c3.out = xh.p; c3.out_ld = CP; c3.cfg = h->head3.cfg;
-        c3.wpk16 = h->head3.wpk16; c3.prec = h->prec;
-        if (h->prec == 3) { c3.amax_in[0] = fn.t.amax; c3.amax_w = h->head3.w_amax; }
-        if (c3.src[0].la && (!fn.lrelu || !conv_lazy_capable(c3, 3, 1))) {
+        at.chunks = mc_head_conv_args(h, mem, ts->nodes[feat].t, xh.p, c3);
+        if (conv_any_lazy(c3) && (!ts->nodes[feat].t.lrelu || !conv_lazy_capable(c3, 3, 1))) {
             materialise(feat);
-            fill_src(c3.src[0], feat);
+            conv_fwd_args(c3, h->head3, {&ts->nodes[feat].t}, h->prec);
         }
-        at.chunks = conv_chunks_per_image(c3.cfg, fh, fw);
         at.stat_ld = h->head3.coutp;
-        float *stats = alloc((size_t)B * at.chunks * at.stat_ld * 2);
-        c3.stats = stats; c3.stat_shift = h->head_rm;
-        at.stats = stats; at.B = B; at.HW = HW;
+        at.stats = c3.stats; at.B = B; at.HW = HW;
         at.stats64 = reinterpret_cast<double *>(alloc((size_t)B * at.stat_ld * 4));   // [B][stat_ld][2] doubles
         at.sv_inst = alloc((size_t)B * CP * 3); at.mu_r = alloc((size_t)CP * 2); at.bn10 = alloc(NUM_HEADS * NUM_AFFINE * 2);
         at.that = alloc((size_t)B * NUM_HEADS * NUM_AFFINE); at.yatt = alloc((size_t)B * NUM_HEADS * NUM_AFFINE);
@@ -870,16 +830,14 @@ struct TB {   // train plan builder
         float *partial = alloc((size_t)nbr * CP * 2), *coef = alloc((size_t)B * CP * 4);
         float *dx = dh;        // the AttnBN backward (an elementwise affine pass) runs in place on the masked gradient
         // scatter dw1 / db1 rows to the parameter gradient tensors (rows are in concatenation order)
-        const int *rb = head_row_begin();
         CopyBatch segcb;
         auto seg = [&](const std::string &layer, int r0, int nr) {
             if (!segcb.add(dw1 + (size_t)r0 * HEAD_CH, G(layer + ".weight", nr * HEAD_CH), (size_t)nr * HEAD_CH) ||
                 !segcb.add(db1 + r0, G(layer + ".bias", nr), nr))
                 ts->ok = false;
         };
-        for (int hd = 0; hd < 8; ++hd) seg(std::string("head.") + HEAD_NAMES[hd] + ".3", rb[hd], rb[hd + 1] - rb[hd]);
-        seg("head.dir_cls.0", rb[8], 12);
-        seg("head.dir_reg.0", rb[8] + 12, 12);
+        for (int hd = 0; hd < NUM_HEADS; ++hd)
+            for (const HeadOutLayer &o : mc_head_keys(hd).out) seg(o.layer, o.row0, o.rows);
         const float *xp = xh.p, *w1 = h->head_w1, *zsc = at.scale, *zsh = at.shift;
         push_bwd([=, B = B, HW = HW](mc_handle *hh, hipStream_t st) {
             HIPCHK(hh, launch_head_bwd(draw, LD, nullptr, xp, w1, B, HW, nbr, dx_fuse ? nullptr : dh, dw1p, partial, st, zsc, zsh, nz_bwd));
@@ -908,7 +866,7 @@ struct TB {   // train plan builder
         emit_wgrad({feat}, dxT, CP, CP, 3, 1, dw3);
         CopyBatch g3cb;
         for (int hd = 0; hd < NUM_HEADS; ++hd) {
-            const std::string layer = std::string("head.") + HEAD_NAMES[hd] + ".0";
+            const std::string layer = mc_head_keys(hd).conv3;
             if (!g3cb.add(dw3 + (size_t)hd * 64 * 64 * 9, G(layer + ".weight", 9 * HEAD_CH * HEAD_CH), (size_t)64 * 64 * 9) ||
                 !g3cb.add(db3 + hd * 64, G(layer + ".bias", HEAD_CH), 64))
                 ts->ok = false;
@@ -916,7 +874,7 @@ struct TB {   // train plan builder
         push_bwd([=](mc_handle *hh, hipStream_t st) { HIPCHK(hh, launch_copy_batch(g3cb, st)); return 0; }, ON_SIDE);
         CopyBatch w3cb;
         for (int hd = 0; hd < NUM_HEADS; ++hd)
-            if (!w3cb.add(P(std::string("head.") + HEAD_NAMES[hd] + ".0.weight", 9 * HEAD_CH * HEAD_CH), w3dense + (size_t)hd * 64 * 64 * 9,
+            if (!w3cb.add(P(mc_head_keys(hd).conv3 + ".weight", 9 * HEAD_CH * HEAD_CH), w3dense + (size_t)hd * 64 * 64 * 9,
                           (size_t)64 * 64 * 9))
                 ts->ok = false;
         ts->pack_fns.push_back([=](mc_handle *hh, hipStream_t st) { HIPCHK(hh, launch_copy_batch(w3cb, st)); return 0; });
@@ -931,7 +889,7 @@ struct TB {   // train plan builder
         const TNode &o = ts->nodes[r.z];
         if (!o.ginit || !in.needs_grad) return;
         float *gi = g_acquire(r.in);
-        PoolBwdArgs pa{in.t.p, o.g, in.la, in.lb, gi, nullptr, in.t.B, in.t.H, in.t.W, in.t.C, in.ginit ? 1 : 0};     // (lazy x: its ReLU'd values are compared)
+        PoolBwdArgs pa{in.t.p, o.g, in.t.la, in.t.lb, gi, nullptr, in.t.B, in.t.H, in.t.W, in.t.C, in.ginit ? 1 : 0};     // (lazy x: its ReLU'd values are compared)
         ts->pool_bwds.push_back(pa);
         PoolBwdArgs *pp = &ts->pool_bwds.back();
         push_bwd([=](mc_handle *hh, hipStream_t st) {
@@ -948,7 +906,7 @@ struct TB {   // train plan builder
         const TNode &o = ts->nodes[r.z];
         if (!o.ginit) return;
         if (in.ginit) { ts->ok = false; h->err = "train plan: deconv input has more than one consumer"; }
-        const float *xp = in.t.p, *go = o.g, *wp = r.D->wpk, *xla = in.la, *xlb = in.lb;
+        const float *xp = in.t.p, *go = o.g, *wp = r.D->wpk, *xla = in.t.la, *xlb = in.t.lb;
         float *gi = g_acquire(r.in), *dw = G(r.D->name + ".weight", (int64_t)r.D->C * 16);
         const int Bq = in.t.B, Hq = in.t.H, Wq = in.t.W, Cq = in.t.C;
         float *part = alloc(deconv4_bwd_w_partial_floats(Bq, Hq, Cq));
@@ -1207,10 +1165,10 @@ int mc_train_debug_node(mc_handle *h, int node, int which, float *out_nchw, int 
     const float *src = which ? n.g : n.t.p;
     if (!src) return fail(h, "mc_train_debug_node: node has no such buffer");
     hipStream_t dst_st = static_cast<hipStream_t>(stream);
-    if (!which && n.la) {       // a lazy activation exists nowhere in memory: form it for the caller
+    if (!which && n.t.la) {       // a lazy activation exists nowhere in memory: form it for the caller
         ScratchBuf tmp;
         HIPCHK(h, tmp.alloc(n.t.numel() * sizeof(float)));
-        HIPCHK(h, launch_affine_act(n.t.p, n.la, n.lb, nullptr, n.t.B, (size_t)n.t.H * n.t.W, n.t.C, 0, n.lrelu ? 1 : 0, tmp.as<float>(),
+        HIPCHK(h, launch_affine_act(n.t.p, n.t.la, n.t.lb, nullptr, n.t.B, (size_t)n.t.H * n.t.W, n.t.C, 0, n.t.lrelu ? 1 : 0, tmp.as<float>(),
                                     dst_st, nullptr));
         HIPCHK(h, launch_nhwc_to_nchw(tmp.as<float>(), n.t.B, n.t.C, n.t.H, n.t.W, out_nchw, dst_st));
         HIPCHK(h, hipStreamSynchronize(dst_st));

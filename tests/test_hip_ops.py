@@ -286,3 +286,24 @@ def test_master_weight_four_bytes_off_alignment(eng, mode):
             assert torch.equal(eng.op_conv_dgrad(dy, w_off, (H, W), 0, C, 1), want)
     finally:
         eng.set_precision(0)
+
+
+@pytest.mark.parametrize("mode,stats", [(0, False), (3, False), (3, True)], ids=["fp32", "f16x2", "f16x2_stats"])
+def test_bench_conv_runs_on_the_shared_launch_description(eng, mode, stats, monkeypatch):
+    """mc_bench_conv (the tuning aid) describes its launch with the plans' conv_fwd_args: one 32-channel source, B = 1,
+    8 x 16, 32 output channels, 3x3 stride 1 -- the smallest map of whole 4x8 patches whose panel has piece planes -- runs and
+    reports a time; MONOCON_BENCH_STATS=1 adds the statistics partials of the train-mode forward."""
+    import ctypes as C
+    import math
+    if stats:
+        monkeypatch.setenv("MONOCON_BENCH_STATS", "1")
+    else:
+        monkeypatch.delenv("MONOCON_BENCH_STATS", raising=False)
+    ms = C.c_float(-1.0)
+    try:
+        eng.set_precision(mode)
+        rc = eng.lib.mc_bench_conv(eng.h, 1, 8, 16, 1, (C.c_int * 1)(32), 32, 3, 1, 0, 1, C.byref(ms))
+    finally:
+        eng.set_precision(0)
+    assert rc == 0
+    assert math.isfinite(ms.value) and ms.value > 0.0
