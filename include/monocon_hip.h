@@ -268,6 +268,40 @@ int mc_optim_bind(mc_handle *h, int n, float *const params[], float *const grads
 int mc_clip_adamw_step(mc_handle *h, double lr, double beta1, double beta2, double eps,
                        double weight_decay, double max_norm, int step, float *out_norm, void *stream);
 
+/* Parameter groups, per-tensor step counts, amsgrad / maximize and any clip norm: the rest of
+ * torch.optim.AdamW (torch/optim/adamw.py, _single_tensor_adam) and of
+ * torch.nn.utils.clip_grad_norm_(parameters, max_norm, norm_type) (torch/nn/utils/clip_grad.py).
+ * A class is one distinct (lr, beta1, beta2, eps, weight_decay, step, amsgrad, maximize): the
+ * caller folds its (param_group, state[p]['step']) pairs into at most MC_OPT_MAX_CLASSES of them.
+ * mc_optim_bind_classes is mc_optim_bind with a class index per tensor and max_exp_avg_sq, the
+ * amsgrad state (entries may be NULL for tensors of non-amsgrad classes; the array itself may be
+ * NULL).  mc_clip_adamw_step_classes computes the global norm_type-norm of the bound gradients
+ * (norm_type > 0, INFINITY allowed: max |g|), the clip coefficient min(1, max_norm/(norm+1e-6))
+ * (max_norm <= 0: no clipping) and one AdamW update per tensor with its class's hyper-parameters;
+ * maximize negates the gradient after clipping, amsgrad keeps vmax = max(vmax, v) and divides by
+ * sqrt(vmax).  One class without flags at norm_type 2 is exactly mc_clip_adamw_step (which, on
+ * a table bound with classes, applies its one hyper-parameter set to every tensor).
+ * Every argument is checked before anything is launched: more than MC_OPT_MAX_CLASSES classes,
+ * a class index of the bound table >= ncls, step < 1, norm_type <= 0 or NaN, and an amsgrad
+ * class with a tensor bound without max_exp_avg_sq all fail the call. */
+#define MC_OPT_MAX_CLASSES 16
+typedef struct mc_optim_class {
+    double lr, beta1, beta2, eps, weight_decay;
+    int step, amsgrad, maximize;
+} mc_optim_class;
+int mc_optim_bind_classes(mc_handle *h, int n, float *const params[], float *const grads[],
+                          float *const exp_avg[], float *const exp_avg_sq[],
+                          float *const max_exp_avg_sq[], const int64_t numel[], const int cls[]);
+int mc_clip_adamw_step_classes(mc_handle *h, const mc_optim_class *classes, int ncls, double max_norm,
+                               double norm_type, float *out_norm, void *stream);
+/* Stand-alone torch.nn.utils.clip_grad_norm_ (the reference's loop as written calls it before
+ * optimizer.step(), engine/monocon_engine.py:94-100): mc_clip_bind registers n gradient tensors
+ * (a table of its own, beside the optimizer's), mc_clip_grad_norm computes their global norm and
+ * multiplies every one of them by the clip coefficient in place -- two launches and the
+ * one-wave final kernel.  out_norm (device float, optional) receives the pre-clip norm. */
+int mc_clip_bind(mc_handle *h, int n, float *const grads[], const int64_t numel[]);
+int mc_clip_grad_norm(mc_handle *h, double max_norm, double norm_type, float *out_norm, void *stream);
+
 /* ---- op-level entry points (unit parity tests; same kernels the forward uses) -------
  * Fused convolution, NHWC fp32: out = act(conv(cat(src...)) * scale + bias + residual).
  * Replaces nn.Conv2d + nn.BatchNorm2d(eval) + ReLU (+ torch.cat, + residual add) of

@@ -26,7 +26,10 @@ _DEFAULTS = {
         "HEAD": {"NUM_CLASSES": 3, "MAX_OBJS": 30},
     },
     "SOLVER": {
-        "OPTIM": {"LR": 2.25e-4, "WEIGHT_DECAY": 1e-5, "NUM_EPOCHS": 200},
+        # BACKBONE_LR_MULT / NO_DECAY_NORM_BIAS (not in the reference's tree; their defaults are its single parameter group):
+        # learning rate of the backbone.* parameters relative to LR (0.0 holds them still), and no weight decay on 1-D
+        # parameters (norm weights and biases, conv biases) -- solver/param_groups.py
+        "OPTIM": {"LR": 2.25e-4, "WEIGHT_DECAY": 1e-5, "NUM_EPOCHS": 200, "BACKBONE_LR_MULT": 1.0, "NO_DECAY_NORM_BIAS": False},
         "SCHEDULER": {"ENABLE": True},
         "CLIP_GRAD": {"ENABLE": True, "NORM_TYPE": 2.0, "MAX_NORM": 35},
     },

@@ -1,7 +1,12 @@
 // Fused gradient-norm clip + AdamW over a table of parameter tensors.
-// Replaces torch.nn.utils.clip_grad_norm_(35, L2) + torch.optim.AdamW.step of the reference's
+// Replaces torch.nn.utils.clip_grad_norm_(max_norm, norm_type) + torch.optim.AdamW.step of the reference's
 // train loop (engine/monocon_engine.py:94-102): two launches per step instead of several
-// hundred per-tensor kernels; 16 B/param of traffic (p, g, m, v read; p, m, v written).
+// hundred per-tensor kernels; 16 B/param of traffic (p, g, m, v read; p, m, v written), 20 B/param with amsgrad.
+//
+// Every kernel is a template whose all-default instantiation (L2 norm; one hyper-parameter set, no amsgrad) is the
+// reference recipe's path: launch_clip_adamw reaches only those, and their arithmetic, chunk walk and partial order are
+// the ones the committed goldens were recorded against.  The other instantiations add the norm kinds of
+// clip_grad_norm_ and torch.optim.AdamW's per-group options.
 #include <stdint.h>
 #include "conv_mfma.h"
 #include "train.h"
@@ -13,8 +18,23 @@ namespace mc {
 // float4 with a scalar tail: the passes run at the HBM roof instead of at the dword-load issue rate.
 __device__ __forceinline__ bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// ---- global gradient norm: sum |g|^p (NORM_L2: g*g) or max |g| per workgroup, then one wave over the partials
+enum { NORM_L2 = 0, NORM_L1 = 1, NORM_INF = 2, NORM_P = 3 };
+
+template <int KIND> __device__ __forceinline__ float norm_term(float x, float p) {
+    if constexpr (KIND == NORM_L2) return x * x;
+    else if constexpr (KIND == NORM_P) return powf(fabsf(x), p);
+    else return fabsf(x);
+}
+// NORM_INF: a maximum that keeps a NaN once it has seen one (torch's max does; fmax alone would drop it)
+template <int KIND, typename T> __device__ __forceinline__ T norm_join(T a, T b) {
+    if constexpr (KIND == NORM_INF) return a != a ? a : (b != b ? b : (a > b ? a : b));
+    else return a + b;
+}
+
+template <int KIND>
 __global__ __launch_bounds__(256) void gradnorm_partial_kernel(const OptTensor *tab, const OptChunk *chunks, int nchunks,
-                                                               float *partial) {
+                                                               float *partial, float p) {
     float s = 0.f;
     for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
         const OptChunk ck = chunks[c];
@@ -25,38 +45,82 @@ __global__ __launch_bounds__(256) void gradnorm_partial_kernel(const OptTensor *
             const f32x4 *g4 = reinterpret_cast<const f32x4 *>(g);
             for (int i = threadIdx.x; i < n4; i += 256) {
                 const f32x4 v = g4[i];
-                s += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
+                s = norm_join<KIND>(s, norm_join<KIND>(norm_join<KIND>(norm_join<KIND>(norm_term<KIND>(v[0], p), norm_term<KIND>(v[1], p)),
+                                                                       norm_term<KIND>(v[2], p)), norm_term<KIND>(v[3], p)));
             }
             i0 = n4 << 2;
         }
-        for (int i = i0 + threadIdx.x; i < ck.count; i += 256) s += g[i] * g[i];
+        for (int i = i0 + threadIdx.x; i < ck.count; i += 256) s = norm_join<KIND>(s, norm_term<KIND>(g[i], p));
     }
     __shared__ float red[4];
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    for (int o = 32; o > 0; o >>= 1) s = norm_join<KIND>(s, __shfl_xor(s, o));
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+    if (threadIdx.x == 0) partial[blockIdx.x] = norm_join<KIND>(norm_join<KIND>(norm_join<KIND>(red[0], red[1]), red[2]), red[3]);
 }
 
-__global__ void gradnorm_final_kernel(const float *partial, int n, float max_norm, float *out /*[2]: norm, coef*/) {
+// the root is taken in double; coef = max_norm / (norm + 1e-6) clamped to 1 is clip_grad_norm_'s formula
+template <int KIND>
+__global__ void gradnorm_final_kernel(const float *partial, int n, float max_norm, float *out /*[2]: norm, coef*/, double inv_p) {
     double s = 0;
-    for (int i = threadIdx.x; i < n; i += 64) s += partial[i];
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    for (int i = threadIdx.x; i < n; i += 64) s = norm_join<KIND>(s, (double)partial[i]);
+    for (int o = 32; o > 0; o >>= 1) s = norm_join<KIND>(s, __shfl_xor(s, o));
     if (threadIdx.x == 0) {
-        const float norm = (float)sqrt(s);
+        float norm;
+        if constexpr (KIND == NORM_L2) norm = (float)sqrt(s);
+        else if constexpr (KIND == NORM_P) norm = (float)pow(s, inv_p);
+        else norm = (float)s;
         out[0] = norm;
         const float coef = max_norm / (norm + 1e-6f);
         out[1] = (max_norm > 0.f && coef < 1.f) ? coef : 1.f;
     }
 }
 
-__device__ __forceinline__ void adamw_one(float &p, float g, float &m, float &v, float coef, const AdamHyper &hp) {
+// ---- the AdamW step.  AMS: torch's amsgrad (vmax = max(vmax, v); the denominator uses vmax)
+template <bool AMS>
+__device__ __forceinline__ void adamw_one(float &p, float g, float &m, float &v, float &vmax, float coef, const AdamHyper &hp) {
     g *= coef;
     p *= hp.decay;                               // p *= 1 - lr*wd   (decoupled weight decay)
     m = m * hp.beta1 + g * hp.one_minus_beta1;
     v = v * hp.beta2 + g * g * hp.one_minus_beta2;
-    const float denom = sqrtf(v) / hp.sqrt_bc2 + hp.eps;
+    float d = v;
+    if constexpr (AMS) { vmax = fmaxf(vmax, v); d = vmax; }
+    const float denom = sqrtf(d) / hp.sqrt_bc2 + hp.eps;
     p -= hp.step_size * (m / denom);
+}
+
+template <bool AMS>
+__device__ __forceinline__ void adamw_chunk(const OptTensor &t, const OptChunk &ck, float coef, const AdamHyper &hp) {
+    float *p = t.p + ck.begin, *m = t.m + ck.begin, *v = t.v + ck.begin;
+    const float *g = t.g + ck.begin;
+    float *x = AMS ? t.vmax + ck.begin : nullptr;
+    int i0 = 0;
+    if (aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && (!AMS || aligned16(x))) {
+        const int n4 = ck.count >> 2;
+        for (int i = threadIdx.x; i < n4; i += 256) {
+            f32x4 p4 = reinterpret_cast<f32x4 *>(p)[i], m4 = reinterpret_cast<f32x4 *>(m)[i], v4 = reinterpret_cast<f32x4 *>(v)[i];
+            const f32x4 g4 = reinterpret_cast<const f32x4 *>(g)[i];
+            f32x4 x4 = {0.f, 0.f, 0.f, 0.f};
+            if constexpr (AMS) x4 = reinterpret_cast<f32x4 *>(x)[i];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float pj = p4[j], mj = m4[j], vj = v4[j], xj = x4[j];
+                adamw_one<AMS>(pj, g4[j], mj, vj, xj, coef, hp);
+                p4[j] = pj; m4[j] = mj; v4[j] = vj; x4[j] = xj;
+            }
+            reinterpret_cast<f32x4 *>(p)[i] = p4;
+            reinterpret_cast<f32x4 *>(m)[i] = m4;
+            reinterpret_cast<f32x4 *>(v)[i] = v4;
+            if constexpr (AMS) reinterpret_cast<f32x4 *>(x)[i] = x4;
+        }
+        i0 = n4 << 2;
+    }
+    for (int i = i0 + threadIdx.x; i < ck.count; i += 256) {
+        float xi = 0.f;
+        if constexpr (AMS) xi = x[i];
+        adamw_one<AMS>(p[i], g[i], m[i], v[i], xi, coef, hp);
+        if constexpr (AMS) x[i] = xi;
+    }
 }
 
 __global__ __launch_bounds__(256) void adamw_kernel(const OptTensor *tab, const OptChunk *chunks, int nchunks,
@@ -65,37 +129,90 @@ __global__ __launch_bounds__(256) void adamw_kernel(const OptTensor *tab, const 
     for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
         const OptChunk ck = chunks[c];
         const OptTensor t = tab[ck.tensor];
-        float *p = t.p + ck.begin, *m = t.m + ck.begin, *v = t.v + ck.begin;
-        const float *g = t.g + ck.begin;
+        adamw_chunk<false>(t, ck, coef, hp);
+    }
+}
+
+// Per-class hyper-parameters.  A chunk belongs to one tensor, so its class is the same for the whole workgroup: it is
+// forced into a scalar register, and the row of the by-value table is then fetched with scalar loads from the
+// kernel-argument segment once per chunk -- never per element.  maximize flips the sign of g AFTER the clip coefficient
+// (as torch does), which is exactly the coefficient's sign.  AMSGRAD: some class of the launch is amsgrad.
+template <bool AMSGRAD>
+__global__ __launch_bounds__(256) void adamw_classes_kernel(const OptTensor *tab, const OptChunk *chunks, int nchunks,
+                                                            const float *normcoef, AdamTable tb) {
+    const float coef0 = normcoef[1];
+    for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+        const OptChunk ck = chunks[c];
+        const OptTensor t = tab[ck.tensor];
+        const int k = __builtin_amdgcn_readfirstlane(t.cls) & (OPT_MAX_CLASSES - 1);
+        const AdamHyper hp = tb.hp[k];
+        const float coef = ((tb.maximize >> k) & 1u) ? -coef0 : coef0;
+        if (AMSGRAD && ((tb.amsgrad >> k) & 1u)) adamw_chunk<true>(t, ck, coef, hp);
+        else adamw_chunk<false>(t, ck, coef, hp);
+    }
+}
+
+// stand-alone clip_grad_norm_: every bound gradient times the clip coefficient, in place
+__global__ __launch_bounds__(256) void grad_scale_kernel(const OptTensor *tab, const OptChunk *chunks, int nchunks,
+                                                         const float *normcoef) {
+    const float coef = normcoef[1];
+    if (coef == 1.f) return;                     // not clipped: x * 1 is x
+    for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+        const OptChunk ck = chunks[c];
+        float *g = tab[ck.tensor].g + ck.begin;
         int i0 = 0;
-        if (aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v)) {
+        if (aligned16(g)) {
             const int n4 = ck.count >> 2;
+            f32x4 *g4 = reinterpret_cast<f32x4 *>(g);
             for (int i = threadIdx.x; i < n4; i += 256) {
-                f32x4 p4 = reinterpret_cast<f32x4 *>(p)[i], m4 = reinterpret_cast<f32x4 *>(m)[i], v4 = reinterpret_cast<f32x4 *>(v)[i];
-                const f32x4 g4 = reinterpret_cast<const f32x4 *>(g)[i];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float pj = p4[j], mj = m4[j], vj = v4[j];
-                    adamw_one(pj, g4[j], mj, vj, coef, hp);
-                    p4[j] = pj; m4[j] = mj; v4[j] = vj;
-                }
-                reinterpret_cast<f32x4 *>(p)[i] = p4;
-                reinterpret_cast<f32x4 *>(m)[i] = m4;
-                reinterpret_cast<f32x4 *>(v)[i] = v4;
+                f32x4 v = g4[i];
+                v[0] *= coef; v[1] *= coef; v[2] *= coef; v[3] *= coef;
+                g4[i] = v;
             }
             i0 = n4 << 2;
         }
-        for (int i = i0 + threadIdx.x; i < ck.count; i += 256) adamw_one(p[i], g[i], m[i], v[i], coef, hp);
+        for (int i = i0 + threadIdx.x; i < ck.count; i += 256) g[i] *= coef;
     }
 }
 
 constexpr int OPT_BLOCKS = 2048;
+static int opt_blocks(int nchunks) { return nchunks < OPT_BLOCKS ? nchunks : OPT_BLOCKS; }
+
+template <int KIND>
+static void launch_norm_kind(const OptTensor *tab, const OptChunk *chunks, int nchunks, float *partial, float *normcoef,
+                             float max_norm, double norm_type, hipStream_t st) {
+    const int blocks = opt_blocks(nchunks);
+    hipLaunchKernelGGL(gradnorm_partial_kernel<KIND>, dim3(blocks), dim3(256), 0, st, tab, chunks, nchunks, partial, (float)norm_type);
+    hipLaunchKernelGGL(gradnorm_final_kernel<KIND>, dim3(1), dim3(64), 0, st, partial, blocks, max_norm, normcoef, 1.0 / norm_type);
+}
+
+hipError_t launch_grad_norm(const OptTensor *tab, const OptChunk *chunks, int nchunks, float *partial, float *normcoef,
+                            float max_norm, double norm_type, hipStream_t st) {
+    if (norm_type == 2.0) launch_norm_kind<NORM_L2>(tab, chunks, nchunks, partial, normcoef, max_norm, norm_type, st);
+    else if (norm_type == 1.0) launch_norm_kind<NORM_L1>(tab, chunks, nchunks, partial, normcoef, max_norm, norm_type, st);
+    else if (norm_type == INFINITY) launch_norm_kind<NORM_INF>(tab, chunks, nchunks, partial, normcoef, max_norm, norm_type, st);
+    else if (norm_type > 0.0) launch_norm_kind<NORM_P>(tab, chunks, nchunks, partial, normcoef, max_norm, norm_type, st);
+    else return hipErrorInvalidValue;            // p <= 0 or NaN (the entry points reject it before this)
+    return hipGetLastError();
+}
+
 hipError_t launch_clip_adamw(const OptTensor *tab, const OptChunk *chunks, int nchunks, float *partial, float *normcoef,
                              float max_norm, const AdamHyper &hp, hipStream_t st) {
-    const int blocks = nchunks < OPT_BLOCKS ? nchunks : OPT_BLOCKS;
-    hipLaunchKernelGGL(gradnorm_partial_kernel, dim3(blocks), dim3(256), 0, st, tab, chunks, nchunks, partial);
-    hipLaunchKernelGGL(gradnorm_final_kernel, dim3(1), dim3(64), 0, st, partial, blocks, max_norm, normcoef);
-    hipLaunchKernelGGL(adamw_kernel, dim3(blocks), dim3(256), 0, st, tab, chunks, nchunks, normcoef, hp);
+    launch_norm_kind<NORM_L2>(tab, chunks, nchunks, partial, normcoef, max_norm, 2.0, st);
+    hipLaunchKernelGGL(adamw_kernel, dim3(opt_blocks(nchunks)), dim3(256), 0, st, tab, chunks, nchunks, normcoef, hp);
+    return hipGetLastError();
+}
+
+hipError_t launch_adamw_classes(const OptTensor *tab, const OptChunk *chunks, int nchunks, const float *normcoef,
+                                const AdamTable &tb, hipStream_t st) {
+    const int blocks = opt_blocks(nchunks);
+    if (tb.amsgrad) hipLaunchKernelGGL(adamw_classes_kernel<true>, dim3(blocks), dim3(256), 0, st, tab, chunks, nchunks, normcoef, tb);
+    else hipLaunchKernelGGL(adamw_classes_kernel<false>, dim3(blocks), dim3(256), 0, st, tab, chunks, nchunks, normcoef, tb);
+    return hipGetLastError();
+}
+
+hipError_t launch_grad_scale(const OptTensor *tab, const OptChunk *chunks, int nchunks, const float *normcoef, hipStream_t st) {
+    hipLaunchKernelGGL(grad_scale_kernel, dim3(opt_blocks(nchunks)), dim3(256), 0, st, tab, chunks, nchunks, normcoef);
     return hipGetLastError();
 }
 int opt_partial_floats() { return OPT_BLOCKS; }

@@ -593,6 +593,8 @@ int mc_destroy(mc_handle *h) {
     if (h->comm && h->comm_free) h->comm_free(h->comm);
     if (h->opt_tab) (void)hipFree(h->opt_tab);
     if (h->opt_chunks) (void)hipFree(h->opt_chunks);
+    if (h->clip_tab) (void)hipFree(h->clip_tab);
+    if (h->clip_chunks) (void)hipFree(h->clip_chunks);
     if (h->opt_ws) (void)hipFree(h->opt_ws);
     delete h;
     return 0;

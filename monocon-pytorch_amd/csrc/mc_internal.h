@@ -262,7 +262,13 @@ struct mc_handle {
     mc::OptTensor *opt_tab = nullptr;
     mc::OptChunk *opt_chunks = nullptr;
     int opt_nchunks = 0, opt_ntensors = 0;
+    int opt_max_cls = 0;        // largest class index of the bound table
+    unsigned opt_novmax = 0;    // bit c: some tensor of class c was bound without max_exp_avg_sq
     float *opt_ws = nullptr;    // partials + [norm, coef]
+    // gradient-only table of the stand-alone clip (mc_clip_bind)
+    mc::OptTensor *clip_tab = nullptr;
+    mc::OptChunk *clip_chunks = nullptr;
+    int clip_nchunks = 0;
     // train-step plan (mc_train_plan.hip)
     TrainState *train = nullptr;
     size_t train_bytes = 0;   // device memory owned by the train plan

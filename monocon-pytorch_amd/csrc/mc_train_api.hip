@@ -247,38 +247,79 @@ int mc_op_conv_dgrad(mc_handle *h, const float *dy, const float *weight_oihw, in
     return 0;
 }
 
-int mc_optim_bind(mc_handle *h, int n, float *const params[], float *const grads[], float *const exp_avg[],
-                  float *const exp_avg_sq[], const int64_t numel[]) {
-    if (!h) return -1;
-    if (n < 1 || !params || !grads || !exp_avg || !exp_avg_sq || !numel) return fail(h, "mc_optim_bind: bad argument");
-    HIPCHK(h, hipSetDevice(h->device));
-    std::vector<mc::OptTensor> tab(n);
+// uploads a tensor table with its 65536-element chunk list (replacing the one *dtab / *dchunks hold)
+static int upload_opt_table(mc_handle *h, const std::vector<mc::OptTensor> &tab, const int64_t numel[], mc::OptTensor **dtab,
+                            mc::OptChunk **dchunks, int *nchunks) {
     std::vector<mc::OptChunk> chunks;
     const int CH = 1 << 16;
-    for (int i = 0; i < n; ++i) {
-        if (!params[i] || !grads[i] || !exp_avg[i] || !exp_avg_sq[i] || numel[i] < 1)
-            return fail(h, "mc_optim_bind: tensor %d has a null pointer / empty size", i);
-        tab[i] = mc::OptTensor{params[i], grads[i], exp_avg[i], exp_avg_sq[i]};
+    for (int i = 0; i < (int)tab.size(); ++i)
         for (int64_t b = 0; b < numel[i]; b += CH)
             chunks.push_back(mc::OptChunk{i, (int)b, (int)std::min<int64_t>(CH, numel[i] - b)});
-    }
-    if (h->opt_tab) (void)hipFree(h->opt_tab);
-    if (h->opt_chunks) (void)hipFree(h->opt_chunks);
-    h->opt_tab = nullptr; h->opt_chunks = nullptr;
+    if (*dtab) (void)hipFree(*dtab);
+    if (*dchunks) (void)hipFree(*dchunks);
+    *dtab = nullptr; *dchunks = nullptr; *nchunks = 0;
     void *q = nullptr;
     HIPCHK(h, hipMalloc(&q, tab.size() * sizeof(mc::OptTensor)));
-    h->opt_tab = static_cast<mc::OptTensor *>(q);
+    *dtab = static_cast<mc::OptTensor *>(q);
     HIPCHK(h, hipMalloc(&q, chunks.size() * sizeof(mc::OptChunk)));
-    h->opt_chunks = static_cast<mc::OptChunk *>(q);
-    HIPCHK(h, hipMemcpy(h->opt_tab, tab.data(), tab.size() * sizeof(mc::OptTensor), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(h->opt_chunks, chunks.data(), chunks.size() * sizeof(mc::OptChunk), hipMemcpyHostToDevice));
-    h->opt_nchunks = (int)chunks.size();
-    h->opt_ntensors = n;
+    *dchunks = static_cast<mc::OptChunk *>(q);
+    HIPCHK(h, hipMemcpy(*dtab, tab.data(), tab.size() * sizeof(mc::OptTensor), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(*dchunks, chunks.data(), chunks.size() * sizeof(mc::OptChunk), hipMemcpyHostToDevice));
+    *nchunks = (int)chunks.size();
     if (!h->opt_ws) {
         HIPCHK(h, hipMalloc(&q, (mc::opt_partial_floats() + 8) * sizeof(float)));
         h->opt_ws = static_cast<float *>(q);
     }
     return 0;
+}
+
+static int optim_bind(mc_handle *h, const char *who, int n, float *const params[], float *const grads[], float *const exp_avg[],
+                      float *const exp_avg_sq[], float *const max_exp_avg_sq[], const int64_t numel[], const int cls[]) {
+    if (!h) return -1;
+    if (n < 1 || !params || !grads || !exp_avg || !exp_avg_sq || !numel) return fail(h, "%s: bad argument", who);
+    HIPCHK(h, hipSetDevice(h->device));
+    std::vector<mc::OptTensor> tab(n);
+    int max_cls = 0;
+    unsigned novmax = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!params[i] || !grads[i] || !exp_avg[i] || !exp_avg_sq[i] || numel[i] < 1)
+            return fail(h, "%s: tensor %d has a null pointer / empty size", who, i);
+        if (numel[i] > INT32_MAX) return fail(h, "%s: tensor %d has more than 2^31-1 elements", who, i);
+        const int c = cls ? cls[i] : 0;
+        if (c < 0 || c >= MC_OPT_MAX_CLASSES)
+            return fail(h, "%s: tensor %d has class index %d, outside [0, %d)", who, i, c, MC_OPT_MAX_CLASSES);
+        float *vmax = max_exp_avg_sq ? max_exp_avg_sq[i] : nullptr;
+        tab[i] = mc::OptTensor{params[i], grads[i], exp_avg[i], exp_avg_sq[i], vmax, c};
+        max_cls = std::max(max_cls, c);
+        if (!vmax) novmax |= 1u << c;
+    }
+    h->opt_ntensors = 0;
+    if (upload_opt_table(h, tab, numel, &h->opt_tab, &h->opt_chunks, &h->opt_nchunks)) return -1;
+    h->opt_ntensors = n;
+    h->opt_max_cls = max_cls;
+    h->opt_novmax = novmax;
+    return 0;
+}
+
+int mc_optim_bind(mc_handle *h, int n, float *const params[], float *const grads[], float *const exp_avg[],
+                  float *const exp_avg_sq[], const int64_t numel[]) {
+    return optim_bind(h, "mc_optim_bind", n, params, grads, exp_avg, exp_avg_sq, nullptr, numel, nullptr);
+}
+
+int mc_optim_bind_classes(mc_handle *h, int n, float *const params[], float *const grads[], float *const exp_avg[],
+                          float *const exp_avg_sq[], float *const max_exp_avg_sq[], const int64_t numel[], const int cls[]) {
+    if (h && !cls) return fail(h, "mc_optim_bind_classes: bad argument");
+    return optim_bind(h, "mc_optim_bind_classes", n, params, grads, exp_avg, exp_avg_sq, max_exp_avg_sq, numel, cls);
+}
+
+static void fold_hyper(mc::AdamHyper &hp, double lr, double beta1, double beta2, double eps, double weight_decay, int step) {
+    const double bc1 = 1.0 - std::pow(beta1, (double)step), bc2 = 1.0 - std::pow(beta2, (double)step);
+    hp.decay = (float)(1.0 - lr * weight_decay);
+    hp.beta1 = (float)beta1; hp.one_minus_beta1 = (float)(1.0 - beta1);
+    hp.beta2 = (float)beta2; hp.one_minus_beta2 = (float)(1.0 - beta2);
+    hp.sqrt_bc2 = (float)std::sqrt(bc2);
+    hp.eps = (float)eps;
+    hp.step_size = (float)(lr / bc1);
 }
 
 int mc_clip_adamw_step(mc_handle *h, double lr, double beta1, double beta2, double eps, double weight_decay,
@@ -289,17 +330,78 @@ int mc_clip_adamw_step(mc_handle *h, double lr, double beta1, double beta2, doub
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     mc::AdamHyper hp;
-    const double bc1 = 1.0 - std::pow(beta1, (double)step), bc2 = 1.0 - std::pow(beta2, (double)step);
-    hp.decay = (float)(1.0 - lr * weight_decay);
-    hp.beta1 = (float)beta1; hp.one_minus_beta1 = (float)(1.0 - beta1);
-    hp.beta2 = (float)beta2; hp.one_minus_beta2 = (float)(1.0 - beta2);
-    hp.sqrt_bc2 = (float)std::sqrt(bc2);
-    hp.eps = (float)eps;
-    hp.step_size = (float)(lr / bc1);
+    fold_hyper(hp, lr, beta1, beta2, eps, weight_decay, step);
     float *normcoef = h->opt_ws + mc::opt_partial_floats();
     HIPCHK(h, mc::launch_clip_adamw(h->opt_tab, h->opt_chunks, h->opt_nchunks, h->opt_ws, normcoef, (float)max_norm, hp, st));
     if (out_norm) HIPCHK(h, hipMemcpyAsync(out_norm, normcoef, sizeof(float), hipMemcpyDeviceToDevice, st));
     h->pack_clean = false;   // parameters changed: the packed panels are stale
+    return 0;
+}
+
+static bool bad_norm_type(double p) { return !(p > 0.0); }   // p <= 0 and NaN
+
+int mc_clip_adamw_step_classes(mc_handle *h, const mc_optim_class *classes, int ncls, double max_norm, double norm_type,
+                               float *out_norm, void *stream) {
+    const char *who = "mc_clip_adamw_step_classes";
+    if (!h) return -1;
+    if (!h->opt_tab) return fail(h, "%s: call mc_optim_bind_classes first", who);
+    if (!classes || ncls < 1) return fail(h, "%s: bad argument", who);
+    if (ncls > MC_OPT_MAX_CLASSES)
+        return fail(h, "%s: %d hyper-parameter classes (distinct lr / betas / eps / weight_decay / step / amsgrad / maximize), "
+                       "at most %d fit one launch", who, ncls, MC_OPT_MAX_CLASSES);
+    if (bad_norm_type(norm_type)) return fail(h, "%s: norm_type must be > 0 (inf allowed), got %g", who, norm_type);
+    if (max_norm != max_norm) return fail(h, "%s: max_norm is NaN", who);
+    if (h->opt_max_cls >= ncls)
+        return fail(h, "%s: the bound table uses class index %d but only %d classes were given", who, h->opt_max_cls, ncls);
+    mc::AdamTable tb{};
+    for (int c = 0; c < ncls; ++c) {
+        const mc_optim_class &k = classes[c];
+        if (k.step < 1) return fail(h, "%s: class %d: step must be >= 1 (1-based, as torch.optim counts)", who, c);
+        if (k.amsgrad && ((h->opt_novmax >> c) & 1u))
+            return fail(h, "%s: class %d is amsgrad but one of its tensors was bound without max_exp_avg_sq", who, c);
+        fold_hyper(tb.hp[c], k.lr, k.beta1, k.beta2, k.eps, k.weight_decay, k.step);
+        if (k.amsgrad) tb.amsgrad |= 1u << c;
+        if (k.maximize) tb.maximize |= 1u << c;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float *normcoef = h->opt_ws + mc::opt_partial_floats();
+    if (ncls == 1 && !tb.amsgrad && !tb.maximize && norm_type == 2.0) {
+        // the reference recipe: the very launch mc_clip_adamw_step makes
+        HIPCHK(h, mc::launch_clip_adamw(h->opt_tab, h->opt_chunks, h->opt_nchunks, h->opt_ws, normcoef, (float)max_norm, tb.hp[0], st));
+    } else {
+        HIPCHK(h, mc::launch_grad_norm(h->opt_tab, h->opt_chunks, h->opt_nchunks, h->opt_ws, normcoef, (float)max_norm, norm_type, st));
+        HIPCHK(h, mc::launch_adamw_classes(h->opt_tab, h->opt_chunks, h->opt_nchunks, normcoef, tb, st));
+    }
+    if (out_norm) HIPCHK(h, hipMemcpyAsync(out_norm, normcoef, sizeof(float), hipMemcpyDeviceToDevice, st));
+    h->pack_clean = false;   // parameters changed: the packed panels are stale
+    return 0;
+}
+
+int mc_clip_bind(mc_handle *h, int n, float *const grads[], const int64_t numel[]) {
+    if (!h) return -1;
+    if (n < 1 || !grads || !numel) return fail(h, "mc_clip_bind: bad argument");
+    HIPCHK(h, hipSetDevice(h->device));
+    std::vector<mc::OptTensor> tab(n);
+    for (int i = 0; i < n; ++i) {
+        if (!grads[i] || numel[i] < 1) return fail(h, "mc_clip_bind: tensor %d has a null pointer / empty size", i);
+        if (numel[i] > INT32_MAX) return fail(h, "mc_clip_bind: tensor %d has more than 2^31-1 elements", i);
+        tab[i] = mc::OptTensor{nullptr, grads[i], nullptr, nullptr, nullptr, 0};
+    }
+    return upload_opt_table(h, tab, numel, &h->clip_tab, &h->clip_chunks, &h->clip_nchunks);
+}
+
+int mc_clip_grad_norm(mc_handle *h, double max_norm, double norm_type, float *out_norm, void *stream) {
+    if (!h) return -1;
+    if (!h->clip_tab) return fail(h, "mc_clip_grad_norm: call mc_clip_bind first");
+    if (bad_norm_type(norm_type)) return fail(h, "mc_clip_grad_norm: norm_type must be > 0 (inf allowed), got %g", norm_type);
+    if (max_norm != max_norm) return fail(h, "mc_clip_grad_norm: max_norm is NaN");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float *normcoef = h->opt_ws + mc::opt_partial_floats();
+    HIPCHK(h, mc::launch_grad_norm(h->clip_tab, h->clip_chunks, h->clip_nchunks, h->opt_ws, normcoef, (float)max_norm, norm_type, st));
+    if (max_norm > 0.0) HIPCHK(h, mc::launch_grad_scale(h->clip_tab, h->clip_chunks, h->clip_nchunks, normcoef, st));
+    if (out_norm) HIPCHK(h, hipMemcpyAsync(out_norm, normcoef, sizeof(float), hipMemcpyDeviceToDevice, st));
     return 0;
 }
 

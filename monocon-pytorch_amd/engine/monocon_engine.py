@@ -19,7 +19,7 @@ from torch.utils.data.distributed import DistributedSampler
 
 from engine.base_engine import BaseEngine
 from model import MonoConDetector
-from solver import AdamW, CyclicScheduler
+from solver import AdamW, CyclicScheduler, build_param_groups
 from utils.decorators import decorator_timer
 from hipmonocon.feed import WORKER_CONTEXT, DeferredScalars, DevicePrefetcher, RingLoader, prepare_worker_context
 from utils.engine_utils import move_data_device, progress_to_string_bar, reduce_loss_dict, tprint
@@ -49,12 +49,16 @@ class MonoconEngine(BaseEngine):
 
     def build_solver(self):
         assert self.model is not None and self.train_loader is not None
-        clip = self.cfg.SOLVER.CLIP_GRAD
-        if clip.ENABLE and float(clip.NORM_TYPE) != 2.0:
-            raise NotImplementedError("the fused optimizer clips the global L2 norm (reference default)")
-        optimizer = AdamW(self.model.parameters(), lr=self.cfg.SOLVER.OPTIM.LR,
-                          weight_decay=self.cfg.SOLVER.OPTIM.WEIGHT_DECAY, betas=(0.95, 0.99),
-                          max_grad_norm=float(clip.MAX_NORM) if clip.ENABLE else None)
+        clip, optim = self.cfg.SOLVER.CLIP_GRAD, self.cfg.SOLVER.OPTIM
+        # group 0 is the base group (current_lr and the log line read it); BACKBONE_LR_MULT 1.0 and NO_DECAY_NORM_BIAS
+        # False give the reference's single group.  BACKBONE_LR_MULT 0.0 freezes the backbone through the optimizer
+        # only: its backward and its BatchNorm running statistics still run (solver/param_groups.py)
+        groups = build_param_groups(self.model.named_parameters(), lr=optim.LR, weight_decay=optim.WEIGHT_DECAY,
+                                    backbone_lr_mult=float(optim.get('BACKBONE_LR_MULT', 1.0)),
+                                    no_decay_norm_bias=bool(optim.get('NO_DECAY_NORM_BIAS', False)))
+        optimizer = AdamW(groups, lr=optim.LR, weight_decay=optim.WEIGHT_DECAY, betas=(0.95, 0.99),
+                          max_grad_norm=float(clip.MAX_NORM) if clip.ENABLE else None,
+                          norm_type=float(clip.NORM_TYPE) if clip.ENABLE else 2.0)
         scheduler = None
         if self.cfg.SOLVER.SCHEDULER.ENABLE:
             total_steps = len(self.train_loader) * self.cfg.SOLVER.OPTIM.NUM_EPOCHS

@@ -3,10 +3,17 @@
 Drop-in for ``torch.optim.AdamW`` in the reference train loop (engine/monocon_engine.py:35-55,
 94-102).  The class is deliberately named ``AdamW`` (CyclicScheduler asserts on the class name,
 solver/cyclic_scheduler.py:16-17).  ``step()`` launches libmonocon_hip's multi-tensor kernels:
-global L2 gradient norm, clip coefficient and the decoupled-weight-decay Adam update in two passes
-over the parameters instead of hundreds of per-tensor launches.  Parameters without a gradient
-(the six tensors the reference never back-propagates into, SURVEY §8a quirk i) are skipped, as
-torch does.
+global gradient norm (any ``norm_type`` of ``clip_grad_norm_``), clip coefficient and the
+decoupled-weight-decay Adam update in two passes over the parameters instead of hundreds of
+per-tensor launches.  Parameters without a gradient (the six tensors the reference never
+back-propagates into, SURVEY §8a quirk i) are skipped, as torch does.
+
+Any number of parameter groups, each with its own ``lr``, ``betas``, ``eps``, ``weight_decay``,
+``amsgrad`` and ``maximize``, and a step count per parameter, as ``torch.optim.AdamW`` keeps them: the
+distinct (hyper-parameters, step) sets of one ``step()`` -- its *classes* -- go to the kernel as a
+table of at most ``MC_OPT_MAX_CLASSES`` rows, every bound tensor carries the index of its row.
+``clip_grad_norm_`` is ``torch.nn.utils.clip_grad_norm_`` as three launches for the loop that clips
+by itself.
 """
 import ctypes as C
 
@@ -15,18 +22,77 @@ from torch.optim.optimizer import Optimizer
 
 from hipmonocon import lib as _lib
 
+MAX_CLASSES = _lib.OPT_MAX_CLASSES
+_TORCH_DEFAULTS = None
+
+
+def _torch_defaults():
+    """torch.optim.AdamW's own ``defaults`` (foreach, capturable, differentiable, fused, ...): carried in every group so that
+    ``state_dict()`` has torch's keys; the fused step reads none of the extra ones"""
+    global _TORCH_DEFAULTS
+    if _TORCH_DEFAULTS is None:
+        _TORCH_DEFAULTS = dict(torch.optim.AdamW([torch.nn.Parameter(torch.zeros(1))]).defaults)
+    return _TORCH_DEFAULTS
+
+
+def check_norm_type(norm_type):
+    p = float(norm_type)
+    if not p > 0.0:                                  # p <= 0 and NaN
+        raise ValueError("norm_type must be > 0 (inf allowed), got %r" % (norm_type,))
+    return p
+
+
+def class_key(group, step):
+    """the tuple that makes two (group, step) pairs one class of the kernel's table"""
+    b1, b2 = group['betas']
+    return (float(group['lr']), float(b1), float(b2), float(group['eps']), float(group['weight_decay']), int(step),
+            bool(group.get('amsgrad', False)), bool(group.get('maximize', False)))
+
+
+def fold_classes(param_groups, pairs):
+    """``pairs``: (group index, 1-based step) per bound tensor, in table order.  Returns (classes, cls): the distinct
+    ``class_key`` tuples in order of first appearance and each tensor's index into them.  More than ``MAX_CLASSES``
+    distinct classes raise."""
+    index, classes, by_key = {}, [], {}
+    for pair in dict.fromkeys(pairs):
+        key = class_key(param_groups[pair[0]], pair[1])
+        k = by_key.get(key)
+        if k is None:
+            k = by_key[key] = len(classes)
+            classes.append(key)
+            if k >= MAX_CLASSES:
+                raise _lib.MonoconHipError(
+                    "fused AdamW: this step needs more than %d hyper-parameter classes (distinct lr / betas / eps / "
+                    "weight_decay / amsgrad / maximize of the groups times distinct step counts of their parameters)"
+                    % MAX_CLASSES)
+        index[pair] = k
+    return classes, tuple(map(index.__getitem__, pairs))
+
+
+def _check_tensor(t, like, what):
+    if t.dtype != torch.float32 or t.device != like.device or not t.is_contiguous():
+        raise _lib.MonoconHipError("fused AdamW: %s must be a contiguous float32 tensor on the parameter's device" % what)
+
 
 class AdamW(Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None,
-                 engine=None):
-        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, maximize=False,
+                 max_grad_norm=None, norm_type=2.0, engine=None):
+        if not 0.0 <= lr:
+            raise ValueError("Invalid learning rate: %r" % (lr,))
+        if not 0.0 <= eps:
+            raise ValueError("Invalid epsilon value: %r" % (eps,))
+        if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+            raise ValueError("Invalid beta parameters: %r" % (betas,))
+        if not 0.0 <= weight_decay:
+            raise ValueError("Invalid weight_decay value: %r" % (weight_decay,))
+        defaults = dict(_torch_defaults())
+        defaults.update(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize)
         super().__init__(params, defaults)
-        if len(self.param_groups) != 1:
-            raise NotImplementedError("the fused optimizer handles one parameter group")
         self.max_grad_norm = max_grad_norm
+        self.norm_type = check_norm_type(norm_type)
         self._engine = engine
         self._bound_sig = None
-        self._step_cache = None         # host-side copy of the common step count (None: re-read from the state)
+        self._step_cache = None         # (key, host-side copies of the bound tensors' step counts); None: re-read the state
         self.last_grad_norm = None      # device scalar of the most recent pre-clip norm
 
     def set_engine(self, engine):
@@ -43,12 +109,15 @@ class AdamW(Optimizer):
         # torch hands the caller's own 'step' (and same-device moment) tensors through uncopied; step() updates
         # them in place, so take private copies -- loading one checkpoint dict into two optimizers stays safe
         for st in self.state.values():
-            for key in ('step', 'exp_avg', 'exp_avg_sq'):
+            for key in ('step', 'exp_avg', 'exp_avg_sq', 'max_exp_avg_sq'):
                 if key in st and torch.is_tensor(st[key]):
                     st[key] = st[key].clone()
 
     def __setstate__(self, state):
         super().__setstate__(state)
+        for group in self.param_groups:
+            for k, v in _torch_defaults().items():
+                group.setdefault(k, v)
         self._bound_sig = None
         self._step_cache = None
 
@@ -63,54 +132,53 @@ class AdamW(Optimizer):
         self._bound_sig = None
         self._step_cache = None
 
-    def _common_step(self, plist):
-        """The bias-correction step lives in ``state[p]['step']`` only (so it survives state_dict round trips);
-        the fused kernel applies one step number to all tensors, as they always share it in this train loop.  Reading
+    def _init_state(self, p, amsgrad):
+        """torch.optim.AdamW's lazy state of one parameter"""
+        st = self.state[p]
+        if len(st) == 0:
+            st['step'] = torch.tensor(0.0)
+            st['exp_avg'] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            st['exp_avg_sq'] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        if amsgrad and 'max_exp_avg_sq' not in st:
+            st['max_exp_avg_sq'] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        return st
+
+    def _steps(self, plist, states):
+        """The bias-correction step lives in ``state[p]['step']`` only (so it survives state_dict round trips).  Reading
         it back is one ``int()`` per tensor -- a host sync each if a resumed checkpoint left the step tensors on the
-        device -- so it is read once (after construction / load_state_dict / a change of the parameter list) and
-        tracked on the host from then on."""
+        device -- so the counts are read once (after construction / load_state_dict / a change of the parameter list) and
+        tracked on the host, one per tensor, from then on."""
         # keyed on the IDENTITY of the stepped tensors and of their step objects (ADVICE r3: the length alone let a changed
         # parameter set of equal size, a reset state or a user-edited state[p]['step'] reuse a stale host copy)
-        key = tuple((id(p), id(self.state[p].get('step'))) for p in plist)
-        if self._step_cache is not None and self._step_cache[0] == key:
-            return self._step_cache[1]
-        steps = {int(self.state[p]['step']) for p in plist}
-        if len(steps) != 1:
-            raise NotImplementedError("fused AdamW: parameters at different step counts %s" % sorted(steps))
-        self._step_cache = (key, steps.pop())
+        key = tuple([(id(p), id(st['step'])) for p, st in zip(plist, states)])
+        if self._step_cache is None or self._step_cache[0] != key:
+            self._step_cache = (key, [int(st['step']) for st in states])
         return self._step_cache[1]
 
-    def _bind(self, plist):
+    def _bind(self, plist, states, ams, cls):
         eng = self._engine
         if eng is None:
             from hipmonocon.engine import Engine
             eng = self._engine = Engine(plist[0].device.index)
-        for p in plist:
-            st = self.state[p]
-            if len(st) == 0:
-                st['step'] = torch.tensor(0.0)
-                st['exp_avg'] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                st['exp_avg_sq'] = torch.zeros_like(p, memory_format=torch.preserve_format)
-        sig = tuple((p.data_ptr(), p.grad.data_ptr(), self.state[p]['exp_avg'].data_ptr(),
-                     self.state[p]['exp_avg_sq'].data_ptr()) for p in plist)
-        if sig == self._bound_sig:
+        # re-bound only when a pointer or a class index changes: lr moves every step, the class assignment does not
+        sig = (tuple([(p.data_ptr(), p.grad.data_ptr(), st['exp_avg'].data_ptr(), st['exp_avg_sq'].data_ptr(),
+                       st['max_exp_avg_sq'].data_ptr() if a else 0) for p, st, a in zip(plist, states, ams)]), cls)
+        if sig == self._bound_sig and getattr(eng, '_optim_sig', None) is self._bound_sig:
             return eng
         n = len(plist)
-        P, G, M, V = ((C.c_void_p * n)() for _ in range(4))
+        P, G, M, V, X = ((C.c_void_p * n)() for _ in range(5))
         N = (C.c_int64 * n)()
-        for i, p in enumerate(plist):
-            if p.dtype != torch.float32 or not p.is_cuda or not p.is_contiguous() or not p.grad.is_contiguous():
+        K = (C.c_int * n)(*cls)
+        for i, (p, st, a) in enumerate(zip(plist, states, ams)):
+            if p.dtype != torch.float32 or not p.is_cuda or not p.is_contiguous() or not p.grad.is_contiguous() or \
+                    p.grad.dtype != torch.float32 or p.grad.device != p.device:
                 raise _lib.MonoconHipError("fused AdamW needs contiguous float32 HIP parameters and gradients")
-            st = self.state[p]
-            for key in ('exp_avg', 'exp_avg_sq'):
-                m = st[key]
-                if m.dtype != torch.float32 or m.device != p.device or not m.is_contiguous():
-                    raise _lib.MonoconHipError("fused AdamW: state['%s'] must be a contiguous float32 tensor on the "
-                                               "parameter's device" % key)
-            P[i], G[i], M[i], V[i] = p.data_ptr(), p.grad.data_ptr(), st['exp_avg'].data_ptr(), st['exp_avg_sq'].data_ptr()
+            for key in ('exp_avg', 'exp_avg_sq') + (('max_exp_avg_sq',) if a else ()):
+                _check_tensor(st[key], p, "state['%s']" % key)
+            P[i], G[i], M[i], V[i], X[i] = sig[0][i]
             N[i] = p.numel()
-        _lib.check(eng.h, eng.lib.mc_optim_bind(eng.h, n, P, G, M, V, N), "mc_optim_bind")
-        self._bound_sig = sig
+        _lib.check(eng.h, eng.lib.mc_optim_bind_classes(eng.h, n, P, G, M, V, X, N, K), "mc_optim_bind_classes")
+        self._bound_sig = eng._optim_sig = sig
         return eng
 
     @torch.no_grad()
@@ -119,26 +187,79 @@ class AdamW(Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        group = self.param_groups[0]
-        plist = [p for p in group['params'] if p.grad is not None]
+        # the bound table: the groups in order, each in parameter order, restricted to parameters with a gradient
+        plist, gis, ams = [], [], []
+        for gi, group in enumerate(self.param_groups):
+            a = bool(group.get('amsgrad', False))
+            for p in group['params']:
+                if p.grad is not None:
+                    plist.append(p)
+                    gis.append(gi)
+                    ams.append(a)
         if not plist:
             return loss
-        eng = self._bind(plist)
-        step = self._common_step(plist) + 1
-        for p in plist:
-            self.state[p]['step'] += 1          # in place: the tensors' identities (the cache key) survive
-        self._step_cache = (tuple((id(p), id(self.state[p]['step'])) for p in plist), step)
+        states = [self._init_state(p, a) for p, a in zip(plist, ams)]
+        steps = self._steps(plist, states)
+        for i in range(len(steps)):
+            steps[i] += 1
+        try:
+            classes, cls = fold_classes(self.param_groups, list(zip(gis, steps)))
+            eng = self._bind(plist, states, ams, cls)
+        except Exception:
+            self._step_cache = None             # nothing was stepped: the state's own counts are the truth again
+            raise
+        torch._foreach_add_([st['step'] for st in states], 1)   # in place: the tensors' identities (the cache key) survive
         if self.last_grad_norm is None:
             self.last_grad_norm = torch.zeros(1, dtype=torch.float32, device=plist[0].device)
-        beta1, beta2 = group['betas']
+        table = (_lib.OptimClass * len(classes))(*classes)
         with torch.cuda.device(plist[0].device):
-            rc = eng.lib.mc_clip_adamw_step(eng.h, float(group['lr']), float(beta1), float(beta2), float(group['eps']),
-                                            float(group['weight_decay']),
-                                            float(self.max_grad_norm) if self.max_grad_norm else 0.0, step,
-                                            C.c_void_p(self.last_grad_norm.data_ptr()),
-                                            C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _lib.check(eng.h, rc, "mc_clip_adamw_step")
+            rc = eng.lib.mc_clip_adamw_step_classes(eng.h, table, len(classes),
+                                                    float(self.max_grad_norm) if self.max_grad_norm else 0.0,
+                                                    self.norm_type, C.c_void_p(self.last_grad_norm.data_ptr()),
+                                                    C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _lib.check(eng.h, rc, "mc_clip_adamw_step_classes")
         # the kernels updated the parameters behind torch's back: advance their version counters
         # (host-only bookkeeping) so autograd and the engine's packed-weight cache see the change
         torch.autograd.graph.increment_version(plist)
         return loss
+
+
+_CLIP_ENGINES = {}
+
+
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, engine=None):
+    """``torch.nn.utils.clip_grad_norm_`` for contiguous float32 HIP gradients, as two multi-tensor launches and the
+    one-wave final kernel: the total ``norm_type``-norm of all gradients (returned as a device scalar), every gradient
+    scaled in place by ``min(1, max_norm / (norm + 1e-6))``.  The gradient table is bound to the engine's handle once
+    and re-bound only when a gradient moved."""
+    if torch.is_tensor(parameters):
+        parameters = [parameters]
+    grads = [p.grad for p in parameters if p.grad is not None and p.grad.numel() > 0]
+    p_norm = check_norm_type(norm_type)
+    if not grads:
+        return torch.tensor(0.0)
+    dev = grads[0].device
+    for g in grads:
+        if g.dtype != torch.float32 or not g.is_cuda or g.device != dev or not g.is_contiguous():
+            raise _lib.MonoconHipError("clip_grad_norm_ needs contiguous float32 HIP gradients on one device")
+    eng = engine
+    if eng is None:
+        eng = _CLIP_ENGINES.get(dev.index)
+        if eng is None:
+            from hipmonocon.engine import Engine
+            eng = _CLIP_ENGINES[dev.index] = Engine(dev.index)
+    sig = tuple([(g.data_ptr(), g.numel()) for g in grads])
+    if getattr(eng, '_clip_sig', None) != sig:
+        n = len(grads)
+        G, N = (C.c_void_p * n)(), (C.c_int64 * n)()
+        for i, (ptr, numel) in enumerate(sig):
+            G[i], N[i] = ptr, numel
+        _lib.check(eng.h, eng.lib.mc_clip_bind(eng.h, n, G, N), "mc_clip_bind")
+        eng._clip_sig = sig
+    total = torch.zeros((), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = eng.lib.mc_clip_grad_norm(eng.h, float(max_norm), p_norm, C.c_void_p(total.data_ptr()),
+                                       C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    _lib.check(eng.h, rc, "mc_clip_grad_norm")
+    torch.autograd.graph.increment_version(grads)
+    return total
