@@ -409,6 +409,42 @@ int mc_kitti_format(mc_handle *h, const float *box2d, const float *box3d, const 
                     const float *P2, const float *img_hw_scale, int B, int K, float *rows3d, int *n3d, float *rows2d,
                     int *n2d, void *stream);
 
+/* ---- 3D-box NMS (opt-in; the reference has no counterpart: it ships every box above the score threshold) ----------
+ * Greedy non-maximum suppression of decoded 3D boxes, per image, on the device, between mc_decode and mc_kitti_format.
+ * mode 0: rotated bird's-eye-view IoU, mode 1: 3D IoU.
+ * Inputs are mc_decode's outputs: box2d (B,K,5), the score is box2d[...,4]; box3d (B,K,7) = x, y (bottom face), z, dim0,
+ * dim1 (height), dim2, rot_y; cls (B,K) int64; keep_in (B,K) u8, normally keep_thr.
+ *
+ * Participants and order: the participants of image b are the slots t with keep_in[b,t] != 0, ordered by score descending,
+ * ties by slot ascending.  Scores are compared through the order-preserving integer image of the float (as the decode
+ * does), so the order is total for any bit pattern.
+ * Greedy pass: walk the participants in that order.  A participant that is still alive when it is reached is kept; it then
+ * suppresses every later participant j that is still alive and satisfies both (class_agnostic != 0 or cls[j] == cls[i])
+ * and ov(i,j) > iou_thr.  The comparison is strict, a NaN overlap never suppresses, and a box that was itself suppressed
+ * suppresses nothing.
+ * Overlap ov(i,j): mode 0 is the float32 value mc_rotate_iou_eval writes at criterion -1 for box = (x, z, dim0, dim2, rot_y)
+ * of i and query = the same of j; mode 1 is the value mc_box3d_overlap writes at criterion -1 for the two box3d rows cast to
+ * double.  Both come from the device functions those kernels use.  Two additions, where that formulation's value is round-off:
+ *   - a participant whose footprint has no area (dim0 or dim2 not greater than 0, NaN included) has overlap 0 with
+ *     everything: it is kept and suppresses nothing.  (The IoU expression is a / (a - a) or 0 / 0 there and reaches far
+ *     beyond 1 in either sign.)
+ *   - two participants with the same footprint (x, z, dim0, dim2, rot_y equal: a pixel that peaks in two class channels)
+ *     intersect in the footprint's own area dim0 * dim2, which then enters the mode's expression as usual: mode 0 gives 1.
+ *     (Every vertex test of the clipping is a tie for such a pair; the formulation gives anything from 0 to 1.)
+ * Outputs: keep_out[b,t] is 1 for a kept participant and 0 for everything else, non-participants included; keep_out may be
+ * the same pointer as keep_in.  suppressed_by (B,K) int32 is optional (NULL): -1 for a kept box, -2 for a non-participant,
+ * otherwise the slot of the box that suppressed it.
+ * Every argument is checked before anything is launched: B < 1, K < 1, K > 1024 (the decode's own limit), mode outside
+ * {0,1}, iou_thr NaN or outside [0,1] and a NULL required pointer fail with a message.  One launch, no host
+ * synchronisation, asynchronous on `stream`.  The one exception is the handle's workspace for K > 128 (the suppression
+ * matrices, B * K * ceil(K / 64) 8-byte words): the call that first needs it, or needs more of it, frees and allocates, which
+ * synchronises the device; every later call of that size or less does not.  That workspace is one per handle: at most one
+ * mc_nms3d call with K > 128 may be in flight on a handle -- two on different streams would zero and set each other's rows.
+ * Calls with K <= 128 use no workspace and may overlap freely. */
+int mc_nms3d(mc_handle *h, const float *box2d, const float *box3d, const int64_t *cls, const uint8_t *keep_in,
+             int B, int K, int mode, float iou_thr, int class_agnostic,
+             uint8_t *keep_out, int *suppressed_by, void *stream);
+
 /* ---- KITTI AP evaluation (last row) -------------------------------------------------------------
  * Device part: pairwise overlaps of rotated boxes.  All pointers are device pointers; results are row-major (N, K).
  *

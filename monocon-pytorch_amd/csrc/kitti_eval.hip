@@ -35,122 +35,19 @@
 #include <vector>
 
 #include "mc_internal.h"
+#include "rotated_overlap.h"    // corners, intersection area, criteria -- shared with nms3d.hip
 
 #pragma clang fp contract(off)
 
 namespace mc {
 
 constexpr int RT = 64;          // tile edge (boxes and queries per workgroup)
-constexpr int RTHREADS = 256;
+constexpr int RTHREADS = 256;   // = the stride of a lane's vertex stripes
 constexpr int MAXV = 16;        // vertex slots: at most 8 corners inside the other box + 8 edge crossings.  (The reference's
                                 // buffer holds 8 points; nearly coincident boxes produce more and overrun it there --
                                 // undefined in the reference, computed properly here.  Measured on the golden's 11 700
                                 // pairs: at most 10 candidates, 12 pairs past 8, none near 16.)
-
-struct RBox { float cx, cy, dx, dy, ang; };
-
-__device__ __forceinline__ void rbox_corners(const RBox b, float *c /* [8] in LDS or registers */, int stride) {
-    const float a_cos = (float)cos((double)b.ang), a_sin = (float)sin((double)b.ang);
-    const float hx = b.dx / 2, hy = b.dy / 2;
-    const float px[4] = {-hx, -hx, hx, hx};
-    const float py[4] = {-hy, hy, hy, -hy};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        c[(2 * i) * stride] = a_cos * px[i] + a_sin * py[i] + b.cx;
-        c[(2 * i + 1) * stride] = -a_sin * px[i] + a_cos * py[i] + b.cy;
-    }
-}
-
-__device__ __forceinline__ bool point_in_quad(float x, float y, const float (&q)[8]) {
-    const float ab0 = q[2] - q[0], ab1 = q[3] - q[1];
-    const float ad0 = q[6] - q[0], ad1 = q[7] - q[1];
-    const float ap0 = x - q[0], ap1 = y - q[1];
-    const float abab = ab0 * ab0 + ab1 * ab1, abap = ab0 * ap0 + ab1 * ap1;
-    const float adad = ad0 * ad0 + ad1 * ad1, adap = ad0 * ap0 + ad1 * ap1;
-    return abab >= abap && abap >= 0.f && adad >= adap && adap >= 0.f;
-}
-
-// edge i of quadrilateral p against edge j of quadrilateral q
-__device__ __forceinline__ bool edge_cross(const float (&p)[8], const float (&q)[8], int i, int j, float &ox, float &oy) {
-    const float A0 = p[2 * i], A1 = p[2 * i + 1], B0 = p[2 * ((i + 1) & 3)], B1 = p[2 * ((i + 1) & 3) + 1];
-    const float C0 = q[2 * j], C1 = q[2 * j + 1], D0 = q[2 * ((j + 1) & 3)], D1 = q[2 * ((j + 1) & 3) + 1];
-    const float BA0 = B0 - A0, BA1 = B1 - A1, DA0 = D0 - A0, CA0 = C0 - A0, DA1 = D1 - A1, CA1 = C1 - A1;
-    const bool acd = DA1 * CA0 > CA1 * DA0;
-    const bool bcd = (D1 - B1) * (C0 - B0) > (C1 - B1) * (D0 - B0);
-    if (acd == bcd) return false;
-    const bool abc = CA1 * BA0 > BA1 * CA0;
-    const bool abd = DA1 * BA0 > BA1 * DA0;
-    if (abc == abd) return false;
-    const float DC0 = D0 - C0, DC1 = D1 - C1;
-    const float ABBA = A0 * B1 - B0 * A1, CDDC = C0 * D1 - D0 * C1;
-    const float DH = BA1 * DC0 - BA0 * DC1;
-    ox = (ABBA * DC0 - BA0 * CDDC) / DH;
-    oy = (ABBA * DC1 - BA1 * CDDC) / DH;
-    return true;
-}
-
-// area of the intersection of quadrilaterals p (the query) and q (the box); vx / vy / vs: this lane's LDS stripes
-__device__ double quad_intersection_area(const float (&p)[8], const float (&q)[8], float *vx, float *vy, float *vs) {
-    int n = 0;
-    auto push = [&](float x, float y) {
-        if (n < MAXV) {
-            vx[n * RTHREADS] = x;
-            vy[n * RTHREADS] = y;
-            ++n;
-        }
-    };
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        if (point_in_quad(p[2 * i], p[2 * i + 1], q)) push(p[2 * i], p[2 * i + 1]);
-        if (point_in_quad(q[2 * i], q[2 * i + 1], p)) push(q[2 * i], q[2 * i + 1]);
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float x, y;
-            if (edge_cross(p, q, i, j, x, y)) push(x, y);
-        }
-    if (n == 0) return 0.0;
-    // order the vertices by the angle around their centroid (key: cosine, mirrored for the lower half plane)
-    float c0 = 0.f, c1 = 0.f;
-    for (int i = 0; i < n; ++i) { c0 += vx[i * RTHREADS]; c1 += vy[i * RTHREADS]; }
-    c0 = (float)((double)c0 / (double)n);
-    c1 = (float)((double)c1 / (double)n);
-    for (int i = 0; i < n; ++i) {
-        float v0 = vx[i * RTHREADS] - c0, v1 = vy[i * RTHREADS] - c1;
-        const float d = sqrtf(v0 * v0 + v1 * v1);
-        v0 = v0 / d;
-        v1 = v1 / d;
-        if (v1 < 0.f) v0 = -2.f - v0;
-        vs[i * RTHREADS] = v0;
-    }
-    for (int i = 1; i < n; ++i) {
-        if (vs[(i - 1) * RTHREADS] > vs[i * RTHREADS]) {
-            const float key = vs[i * RTHREADS], tx = vx[i * RTHREADS], ty = vy[i * RTHREADS];
-            int j = i;
-            while (j > 0 && vs[(j - 1) * RTHREADS] > key) {
-                vs[j * RTHREADS] = vs[(j - 1) * RTHREADS];
-                vx[j * RTHREADS] = vx[(j - 1) * RTHREADS];
-                vy[j * RTHREADS] = vy[(j - 1) * RTHREADS];
-                --j;
-            }
-            vs[j * RTHREADS] = key;
-            vx[j * RTHREADS] = tx;
-            vy[j * RTHREADS] = ty;
-        }
-    }
-    // triangle fan from vertex 0; each triangle's area in float32, the sum in double (the reference's typing)
-    double area = 0.0;
-    const float a0 = vx[0], a1 = vy[0];
-    for (int i = 0; i < n - 2; ++i) {
-        const float b0 = vx[(i + 1) * RTHREADS], b1 = vy[(i + 1) * RTHREADS];
-        const float e0 = vx[(i + 2) * RTHREADS], e1 = vy[(i + 2) * RTHREADS];
-        const float cr = (a0 - e0) * (b1 - e1) - (a1 - e1) * (b0 - e0);
-        area += fabs((double)cr / 2.0);
-    }
-    return area;
-}
+static_assert(MAXV == OVERLAP_MAXV, "the stripes below hold what quad_intersection_area keeps");
 
 // MODE 0: boxes (N,5) float32 [cx, cy, dx, dy, angle] -> out float32 (N,K), criterion -1 / 0 / 1 / other as in
 //         rotate_iou.py:252-277 (rbox1 = the QUERY box).
@@ -193,36 +90,15 @@ __global__ __launch_bounds__(RTHREADS) void rotate_overlap_kernel(const void *bo
         float p[8];
 #pragma unroll
         for (int c = 0; c < 8; ++c) p[c] = corners[1][c][col];
-        const double ai = quad_intersection_area(p, q, vx, vy, vs);
+        const double ai = quad_intersection_area<RTHREADS>(p, q, vx, vy, vs);
         if (MODE == 0) {
             const float *bb = static_cast<const float *>(boxes_) + n * 5, *qq = static_cast<const float *>(qboxes_) + k * 5;
-            const float area1 = qq[2] * qq[3], area2 = bb[2] * bb[3];
             // (the intersection area is a double in the reference's expression, the box areas float32)
-            double r;
-            if (criterion == -1) r = ai / ((double)(area1 + area2) - ai);
-            else if (criterion == 0) r = ai / (double)area1;
-            else if (criterion == 1) r = ai / (double)area2;
-            else r = ai;
-            static_cast<float *>(out_)[n * K + k] = (float)r;
+            static_cast<float *>(out_)[n * K + k] = bev_overlap_value(ai, qq[2] * qq[3], bb[2] * bb[3], criterion);
         } else {
             const double *bb = static_cast<const double *>(boxes_) + n * 7, *qq = static_cast<const double *>(qboxes_) + k * 7;
-            const float inter = (float)ai;       // the reference passes the bare area through a float32 array
-            double r = 0.0;
-            if (inter > 0.f) {
-                // camera frame: y points down, a box spans [y - h, y]
-                const double iw = fmin(bb[1], qq[1]) - fmax(bb[1] - bb[4], qq[1] - qq[4]);
-                if (iw > 0.0) {
-                    const double area1 = bb[3] * bb[4] * bb[5], area2 = qq[3] * qq[4] * qq[5];
-                    const double inc = iw * (double)inter;
-                    double ua;
-                    if (criterion == -1) ua = area1 + area2 - inc;
-                    else if (criterion == 0) ua = area1;
-                    else if (criterion == 1) ua = area2;
-                    else ua = inc;
-                    r = inc / ua;
-                }
-            }
-            static_cast<double *>(out_)[n * K + k] = r;
+            static_cast<double *>(out_)[n * K + k] =
+                box3d_overlap_value(ai, bb[1], bb[3], bb[4], bb[5], qq[1], qq[3], qq[4], qq[5], criterion);
         }
     }
 }

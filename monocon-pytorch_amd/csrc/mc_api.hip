@@ -588,6 +588,7 @@ int mc_destroy(mc_handle *h) {
     for (auto &kv : h->plans) kv.second->mem.release();
     h->params.release();
     if (h->decode_filt) (void)hipFree(h->decode_filt);
+    if (h->nms_ws) (void)hipFree(h->nms_ws);
     if (h->loss_ws) (void)hipFree(h->loss_ws);
     if (h->train && h->train_free) h->train_free(h->train);
     if (h->comm && h->comm_free) h->comm_free(h->comm);
@@ -1318,7 +1319,8 @@ int mc_query_workspace(mc_handle *h, int B, int H, int W, int mode, size_t *byte
 
 size_t mc_workspace_bytes(mc_handle *h) {
     if (!h) return 0;
-    size_t n = h->params.bytes + (3 * h->decode_filt_n + h->decode_count_n) * sizeof(float) + h->train_bytes;
+    size_t n = h->params.bytes + (3 * h->decode_filt_n + h->decode_count_n) * sizeof(float) + h->train_bytes +
+               h->nms_ws_words * sizeof(unsigned long long);
     for (auto &kv : h->plans) n += kv.second->mem.bytes;
     return n;
 }

@@ -249,6 +249,8 @@ struct mc_handle {
     float *decode_filt = nullptr;
     size_t decode_filt_n = 0;
     size_t decode_count_n = 0;
+    unsigned long long *nms_ws = nullptr;   // mc_nms3d: the suppression bit matrices of a batch with K > 128 (nms3d.hip)
+    size_t nms_ws_words = 0;
     int force_cfg = 0;   // tuning aid (mc_bench_conv)
     int lm_kernel = 3;   // mc_set_local_maximum_kernel: window of the decode's local-maximum filter (test_config['local_maximum_kernel'])
     int prec = 0;        // mc_set_precision: 0 fp32 MFMA, 1 bf16 operands, 2 three-way bf16 split, 3 two-way fp16 split

@@ -33,6 +33,16 @@ def _need_cuda(t, what):
     return t
 
 
+NMS_MODES = {"bev": 0, "3d": 1}
+
+
+def nms_mode_id(mode):
+    """mc_nms3d's mode of 'bev' / '3d'; anything else is a ValueError (raised before any launch)"""
+    if mode not in NMS_MODES:
+        raise ValueError("nms mode %r: expected 'bev' (rotated bird's-eye-view IoU) or '3d' (3D IoU)" % (mode,))
+    return NMS_MODES[mode]
+
+
 class Engine:
     """One handle per process per GPU (SURVEY §8b threading rules)."""
 
@@ -221,9 +231,17 @@ class Engine:
         return out
 
     # ------------------------------------------------------------------ decode
-    def decode(self, pred, P2, P2inv, pad_hw, topk, thres, want_keep=False, local_maximum_kernel=3):
+    def decode(self, pred, P2, P2inv, pad_hw, topk, thres, want_keep=False, local_maximum_kernel=3, nms=None):
         """Dense decode.  pred: dict of NCHW CUDA maps; P2 (B,3,4), P2inv (B,4,4) CUDA fp32.
-        local_maximum_kernel: window of the peak filter (odd; test_config['local_maximum_kernel'])."""
+        local_maximum_kernel: window of the peak filter (odd; test_config['local_maximum_kernel']).
+        nms: None (the reference's behaviour, and exactly the keys and values below) or dict(thres=, mode='bev'|'3d',
+        class_agnostic=False): ``nms3d`` of the boxes above the score threshold follows the decode on the stream; the dict
+        gains keep_nms and suppressed_by, box_mask becomes keep_nms.bool(), keep_thr stays the threshold mask alone."""
+        if nms is not None:         # checked before anything is launched
+            unknown = set(nms) - {"thres", "mode", "class_agnostic"}
+            if unknown or "thres" not in nms:
+                raise ValueError("decode: nms must be dict(thres=, mode=, class_agnostic=), got keys %s" % sorted(nms))
+            nms_mode_id(nms.get("mode", "bev"))
         heat = _need_cuda(pred["center_heatmap_pred"], "center_heatmap_pred")
         if int(local_maximum_kernel) != self._lm_kernel:
             _lib.check(self.h, self.lib.mc_set_local_maximum_kernel(self.h, int(local_maximum_kernel)), "mc_set_local_maximum_kernel")
@@ -248,15 +266,46 @@ class Engine:
                                     float(pad_hw[0]), float(pad_hw[1]), _ptr(scores), _ptr(flat), _ptr(cls),
                                     _ptr(box2d), _ptr(box3d), _ptr(keep), _ptr(kthr), _stream())
         _lib.check(self.h, rc, "mc_decode")
-        return dict(scores=scores, flat_index=flat, cls=cls, box2d=box2d, box3d=box3d, keep=keep,
-                    box_mask=kthr.bool(), keep_thr=kthr)
+        R = dict(scores=scores, flat_index=flat, cls=cls, box2d=box2d, box3d=box3d, keep=keep,
+                 box_mask=kthr.bool(), keep_thr=kthr)
+        if nms is not None:
+            R.update(self.nms3d(R, nms["thres"], mode=nms.get("mode", "bev"),
+                                class_agnostic=nms.get("class_agnostic", False)))
+            R["box_mask"] = R["keep_nms"].bool()
+        return R
+
+    def nms3d(self, decoded, iou_thr, mode="bev", class_agnostic=False, keep=None):
+        """Greedy 3D-box NMS of a decoded batch in one launch (mc_nms3d; the reference has none).  decoded: ``decode``'s
+        dict; mode 'bev' (rotated bird's-eye-view IoU) or '3d' (3D IoU); keep (B,K) uint8: the participants, by default
+        decoded['keep_thr'].  Returns dict(keep_nms=uint8 (B,K), suppressed_by=int32 (B,K)): suppressed_by is -1 for a kept
+        box, -2 for a non-participant, else the slot of the suppressor."""
+        mode_id = nms_mode_id(mode)
+        box2d, box3d = _need_cuda(decoded["box2d"], "box2d"), _need_cuda(decoded["box3d"], "box3d")
+        cls = _need_cuda(decoded["cls"], "cls")
+        keep = _need_cuda(decoded["keep_thr"] if keep is None else keep, "keep")
+        B, K = int(box2d.shape[0]), int(box2d.shape[1]) if box2d.dim() > 1 else 0
+        if (tuple(box2d.shape) != (B, K, 5) or tuple(box3d.shape) != (B, K, 7) or tuple(cls.shape) != (B, K)
+                or tuple(keep.shape) != (B, K)):
+            raise _lib.MonoconHipError("nms3d: shapes box2d %s box3d %s cls %s keep %s"
+                                       % tuple(tuple(t.shape) for t in (box2d, box3d, cls, keep)))
+        if (box2d.dtype, box3d.dtype, cls.dtype, keep.dtype) != (torch.float32, torch.float32, torch.int64, torch.uint8):
+            raise _lib.MonoconHipError("nms3d: dtypes must be float32 / int64 cls / uint8 keep")
+        keep_nms = torch.empty((B, K), dtype=torch.uint8, device=box2d.device)
+        by = torch.empty((B, K), dtype=torch.int32, device=box2d.device)
+        with torch.cuda.device(box2d.device):
+            rc = self.lib.mc_nms3d(self.h, _ptr(box2d), _ptr(box3d), _ptr(cls), _ptr(keep), B, K, mode_id, float(iou_thr),
+                                   1 if class_agnostic else 0, _ptr(keep_nms), _ptr(by), _stream())
+        _lib.check(self.h, rc, "mc_nms3d")
+        return dict(keep_nms=keep_nms, suppressed_by=by)
 
     def kitti_format(self, decoded, P2, img_hw_scale):
-        """KITTI result rows of a decoded batch in one launch (mc_kitti_format).  decoded: ``decode``'s dict; P2 (B,3,4) and
+        """KITTI result rows of a decoded batch in one launch (mc_kitti_format).  decoded: ``decode``'s dict (its keep_nms
+        selects the rows when the decode ran with NMS, else keep_thr); P2 (B,3,4) and
         img_hw_scale (B,4) = ori_h, ori_w, inv_sx, inv_sy, CUDA fp32.  Returns rows3d (B,K,14), n3d (B) int32, rows2d (B,K,6),
         n2d (B) int32 -- views of ONE device buffer, ``packed``, so that a single copy brings all four to the host."""
         box2d, box3d = _need_cuda(decoded["box2d"], "box2d"), _need_cuda(decoded["box3d"], "box3d")
-        cls, kthr = _need_cuda(decoded["cls"], "cls"), _need_cuda(decoded["keep_thr"], "keep_thr")
+        kept = "keep_nms" if decoded.get("keep_nms") is not None else "keep_thr"
+        cls, kthr = _need_cuda(decoded["cls"], "cls"), _need_cuda(decoded[kept], kept)
         _need_cuda(P2, "P2"); _need_cuda(img_hw_scale, "img_hw_scale")
         B, K = int(box2d.shape[0]), int(box2d.shape[1])
         if (tuple(box2d.shape) != (B, K, 5) or tuple(box3d.shape) != (B, K, 7) or tuple(cls.shape) != (B, K)

@@ -20,7 +20,7 @@ EXPORTS = (
     "mc_comm_unique_id", "mc_comm_init", "mc_comm_destroy", "mc_comm_set_overlap", "mc_comm_info", "mc_comm_exposed_ms", "mc_allreduce_grads",
     "mc_build_train_plan", "mc_tune_export", "mc_tune_import",
     "mc_rotate_iou_eval", "mc_box3d_overlap", "mc_kitti_image_overlap", "mc_kitti_statistics_part",
-    "mc_kitti_format",
+    "mc_kitti_format", "mc_nms3d",
 )
 
 
@@ -143,6 +143,7 @@ def load():
     lib.mc_kitti_image_overlap.argtypes = [dp, ll, dp, ll, i, dp]
     lib.mc_kitti_statistics_part.argtypes = [i, dp, ll, llp, llp, llp, dp, dp, dp, llp, llp, i, C.c_double, dp, ll, i, dp, dp, llp]
     lib.mc_kitti_format.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, vp, vp, vp, vp, vp]
+    lib.mc_nms3d.argtypes = [vp, vp, vp, vp, vp, i, i, i, f, i, vp, vp, vp]
     lib.mc_set_precision.argtypes = [vp, i]
     lib.mc_set_local_maximum_kernel.argtypes = [vp, i]
     lib.mc_set_conv_cfg.argtypes = [vp, i]

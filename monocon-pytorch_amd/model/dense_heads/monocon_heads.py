@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 
 from hipmonocon.params import ConvParams, Holders, HipRuntime, module_state
-from hipmonocon.engine import p2_inverse
+from hipmonocon.engine import nms_mode_id, p2_inverse
 from model.norm import AttnBatchNorm2d
 
 EPS = 1e-12
@@ -150,6 +150,7 @@ class MonoConDenseHeads(nn.Module):
             # the reference fails here too: max_pool2d(heat, k, 1, (k - 1) // 2) of an even k is one pixel smaller than
             # the heat map and `hmax == heat` does not broadcast (utils/tensor_ops.py:17-21)
             raise RuntimeError("local_maximum_kernel=%r: the peak filter needs an odd window" % self.local_maximum_kernel)
+        nms = self._nms_config()
         if calib_dev is None:
             calib = data_dict['calib']
             if not isinstance(calib, (list, tuple)):
@@ -158,7 +159,19 @@ class MonoConDenseHeads(nn.Module):
         P2, P2inv = calib_dev
         eng = engine if engine is not None else self._engine()
         return eng.decode({k: v.contiguous() for k, v in pred_dict.items()}, P2, P2inv, (img_h, img_w),
-                          self.topk, self.test_thres, local_maximum_kernel=k)
+                          self.topk, self.test_thres, local_maximum_kernel=k, nms=nms)
+
+    def _nms_config(self):
+        """the decode's ``nms`` argument from test_config: None unless 'nms_thres' is set (the reference has no NMS, so
+        absent keys mean off); 'nms_mode' is 'bev' (default) or '3d', 'nms_class_agnostic' False by default.  A bad mode
+        string raises ValueError here, when the decode is reached and before anything is launched."""
+        cfg = self.test_config
+        thres = cfg.get('nms_thres')
+        if thres is None:
+            return None
+        mode = cfg.get('nms_mode', 'bev')
+        nms_mode_id(mode)
+        return dict(thres=float(thres), mode=mode, class_agnostic=bool(cfg.get('nms_class_agnostic', False)))
 
     def decode_heatmap(self, data_dict: Dict[str, Any], pred_dict: Dict[str, torch.Tensor],
                        engine=None) -> Tuple[List[torch.Tensor]]:

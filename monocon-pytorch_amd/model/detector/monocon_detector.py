@@ -82,7 +82,8 @@ class MonoConDetector(nn.Module):
     def detect(self, data_dict: Dict[str, Any], get_vis_format: bool = False):
         """what ``batch_eval`` returns -- the KITTI annotation dicts {'img_bbox': [...], 'img_bbox2d': [...]} with
         ``sample_idx``, or the visualiser's list (get_vis_format=True) -- with the per-image host tail moved to the device:
-        forward, mc_decode, mc_kitti_format (the KITTI rows of the whole batch in one launch), then ONE copy to page-locked
+        forward, mc_decode, mc_nms3d when test_config['nms_thres'] is set, mc_kitti_format (the KITTI rows of the whole batch in
+        one launch), then ONE copy to page-locked
         host memory and one wait for it.  The annotation dicts are built from the packed rows (utils/kitti_convert_utils.py
         kitti_annos_from_rows); the visualiser's list from the decode's outputs (it wants every kept box, visible or not)."""
         kitti, vis = self._detect(data_dict, want_kitti=not get_vis_format, want_vis=bool(get_vis_format))
@@ -124,8 +125,8 @@ class MonoConDetector(nn.Module):
         R = self.head._decode_dense(data_dict, pred_dict, eng, calib_dev=(P2_d, P2inv_d))
         K = int(R['box2d'].shape[1])
         parts = []                                  # device tensors -> byte ranges of one page-locked buffer
-        if want_vis:
-            parts += [R['cls'], R['box2d'], R['box3d'], R['keep_thr']]
+        if want_vis:                                # the mask of the boxes to ship: after NMS when test_config turns it on
+            parts += [R['cls'], R['box2d'], R['box3d'], R['keep_nms'] if 'keep_nms' in R else R['keep_thr']]
         if want_kitti:
             parts.insert(0, eng.kitti_format(R, P2_d, hws_d)['packed'])
         nbytes = [t.numel() * t.element_size() for t in parts]
