@@ -733,6 +733,34 @@ def head_output_stress(sd, heat_gain=12.0, depth_gain=3.0):
     return out
 
 
+def head_attention_stress(sd, gain=4.0):
+    """the state with the gamma of every head's attention BatchNorm (head.*.1.attn_weights.attention.1.weight) scaled by `gain`:
+    the hard sigmoid relu6(t + 3) / 6 of the AttnBN attention then sees inputs in all three of its regimes (t <= -3, the
+    linear branch, t >= 3) instead of the linear one almost alone"""
+    out = {k: v.clone() for k, v in sd.items()}
+    n = 0
+    for k in sd:
+        if k.startswith("head.") and k.endswith(".1.attn_weights.attention.1.weight"):
+            out[k] = (sd[k].double() * gain).float()
+            n += 1
+    assert n == len(HEADS), n
+    return out
+
+
+def head_decided_pixels(sd, hidden, tau=1e-4):
+    """{head: (B, h, w) bool} from the heads' hidden maps (hidden[head]: the output of head.<head>.0, bias included): True
+    where none of the head's 64 ReLU decisions after the train-mode AttnBN lies within tau of the channel's standard deviation
+    of its threshold, by the oracle's own `_attn_bn` in the precision of `sd` and `hidden`"""
+    from oracle import monocon_oracle as O
+    out = {}
+    with torch.no_grad():
+        cx = O._Ctx(sd, True)
+        for br, x in hidden.items():
+            a = O._attn_bn(cx, x, "head.%s.1" % br)
+            out[br] = (a.abs() / a.std(dim=(0, 2, 3), keepdim=True)).amin(dim=1) >= tau
+    return out
+
+
 # ---- reading the eval plan
 def read_infer(eng, node, which=0):
     """mc_infer_debug_node on the engine's last eval plan: NCHW float32 on the host"""

@@ -54,15 +54,13 @@ def decided_pixels(sd, batch, tau=1e-4):
     a dense term on the maps puts a full one, and the decision then moves a cancelling sum such as an AttnBN bias
     gradient by ~1e-3.  Those pixels (<= 11 of the B h w per head) are left out of the term."""
     from oracle import monocon_oracle as O
+    from plan_graph import head_decided_pixels
     sd64 = {k: (v.double() if v.dtype == torch.float32 else v) for k, v in sd.items()}
     with torch.no_grad():
         _, feat, _ = O.forward(sd64, batch["img"].double(), train=True)
         cx = O._Ctx(sd64, True)
-        out = {}
-        for br in list(O.HEAD_BRANCHES) + ["dir_feat"]:
-            a = O._attn_bn(cx, cx.conv(feat, "head.%s.0" % br, 1, 1), "head.%s.1" % br)
-            out[br] = (a.abs() / a.std(dim=(0, 2, 3), keepdim=True)).amin(dim=1) >= tau
-    return out
+        hidden = {br: cx.conv(feat, "head.%s.0" % br, 1, 1) for br in list(O.HEAD_BRANCHES) + ["dir_feat"]}
+    return head_decided_pixels(sd64, hidden, tau)
 
 
 def map_weights(seed, B, fh, fw, keys=PRED_KEYS, keep=None):

@@ -86,11 +86,10 @@ def test_losses_vs_reference_golden(eng):
         assert abs(float(L[i]) - float(Lref[k])) <= 1e-4 * abs(float(Lref[k])) + 1e-6, k
 
 
-def test_loss_gradients_vs_autograd(eng):
-    """d(sum w_i loss_i)/d(raw head outputs) vs torch autograd through the oracle's loss code."""
-    from oracle import monocon_oracle as O
-    batch, preds, Tref, _ = _train_case(GOLDEN_SEED + 9)
-    # raw (pre-activation) maps as autograd leaves
+def _raw_leaves(preds):
+    """the raw (pre-activation) maps behind `preds` as autograd leaves, and the activated maps formed from them again"""
+    from plan_graph import heat_clamps
+    lo, hi = (float(c) for c in heat_clamps())          # what a float32 heat map saturates at
     raw = {}
     for k, v in preds.items():
         if k in ("center_heatmap_pred", "kpt_heatmap_pred"):
@@ -98,7 +97,7 @@ def test_loss_gradients_vs_autograd(eng):
             # entries sitting on the clamp were produced by logits strictly beyond it: rebuild them
             # that way (a logit that lands exactly ON the boundary is a measure-zero case where
             # torch.clamp's inclusive mask and a mask derived from the clamped value differ)
-            x = torch.where(v <= 1e-4, x - 1.0, torch.where(v >= 1 - 1e-4, x + 1.0, x))
+            x = torch.where(v <= lo, x - 1.0, torch.where(v >= hi, x + 1.0, x))
             raw[k] = x.clone().requires_grad_(True)
         elif k == "depth_pred":
             x0 = torch.logit(1.0 / (v[:, 0:1] + 1.0))
@@ -113,8 +112,19 @@ def test_loss_gradients_vs_autograd(eng):
             act[k] = torch.cat([1.0 / (torch.sigmoid(v[:, 0:1]) + 1e-12) - 1.0, v[:, 1:2]], 1)
         else:
             act[k] = v
+    return raw, act
+
+
+LOSS_W = (1.0, 0.5, 2.0, 1.5, 1.0, 0.7, 1.0, 3.0, 1.0, 0.25)
+
+
+def test_loss_gradients_vs_autograd(eng):
+    """d(sum w_i loss_i)/d(raw head outputs) vs torch autograd through the oracle's loss code."""
+    from oracle import monocon_oracle as O
+    batch, preds, Tref, _ = _train_case(GOLDEN_SEED + 9)
+    raw, act = _raw_leaves(preds)
     L = O.losses(act, Tref)
-    w = torch.tensor([1.0, 0.5, 2.0, 1.5, 1.0, 0.7, 1.0, 3.0, 1.0, 0.25])
+    w = torch.tensor(LOSS_W)
     total = sum(w[i] * v for i, v in enumerate(L.values()))
     total.backward()
     label = {k: v.cuda() for k, v in batch["label"].items()}
@@ -123,6 +133,65 @@ def test_loss_gradients_vs_autograd(eng):
     for k in raw:
         ref = raw[k].grad
         assert rel_err(d[k].cpu(), ref) < 2e-4, (k, rel_err(d[k].cpu(), ref))
+
+
+def _random_maps(seed, B, fh, fw):
+    """ten float32 maps shaped like the oracle's: heat maps in [1e-4, 1 - 1e-4] with both clamps occupied, a positive depth
+    with its log-variance, positive dimensions, N(0, 1) elsewhere"""
+    from hipmonocon import netspec
+    gen = torch.Generator().manual_seed(seed)
+    out = {}
+    for k, c in netspec.PRED_KEYS:
+        z = torch.randn((B, c, fh, fw), generator=gen, dtype=torch.float32)
+        if k in ("center_heatmap_pred", "kpt_heatmap_pred"):
+            z = torch.clamp(torch.sigmoid(4.0 * z - 3.0), 1e-4, 1 - 1e-4)
+        elif k == "depth_pred":
+            z = torch.cat([1.0 / (torch.sigmoid(1.5 * z[:, 0:1] - 3.0) + 1e-12) - 1.0, 0.5 * z[:, 1:2]], 1)
+        elif k == "dim_pred":
+            z = z.abs() + 0.5
+        out[k] = z.contiguous()
+    return out
+
+
+@pytest.mark.parametrize("B", [9, 32])
+def test_losses_and_gradients_at_training_batches(eng, B):
+    """mc_losses and mc_losses_backward at B = 9 and at the batch the product trains at, on a 48x96 map (every other loss
+    comparison has B = 2): random maps shaped like the oracle's, labels of make_labels with two images' masks cleared, so
+    that object-free images sit inside a large batch; against O.losses and autograd in fp64 at the bounds of the B = 2 tests
+    (losses 1e-4 relative, gradients wrt the raw outputs 2e-4 norm-wise)."""
+    from oracle import monocon_oracle as O
+    from hipmonocon.netspec import LOSS_KEYS
+    H, W, fh, fw = 192, 384, 48, 96
+    lab = synth.make_labels(GOLDEN_SEED + 40 + B, B, H, W)
+    empty = (1, B - 3)
+    for b in empty:
+        lab["mask"][b] = 0.0
+    assert all(lab["mask"][b].sum() > 0 for b in range(B) if b not in empty)
+    label = {k: torch.from_numpy(v) for k, v in lab.items()}
+    preds = _random_maps(GOLDEN_SEED + 50 + B, B, fh, fw)
+    for k in ("center_heatmap_pred", "kpt_heatmap_pred"):
+        assert float(preds[k].min()) == np.float32(1e-4) and float(preds[k].max()) == np.float32(1 - 1e-4)
+    Tref = O.make_targets(label, (H, W), (B, 64, fh, fw))
+    T64 = {k: (v.double() if v.dtype == torch.float32 else v) for k, v in Tref.items()}
+    raw, act = _raw_leaves({k: v.double() for k, v in preds.items()})
+    Lref = O.losses(act, T64)
+    w = torch.tensor(LOSS_W, dtype=torch.float64)
+    sum(w[i] * v for i, v in enumerate(Lref.values())).backward()
+    T = eng.make_targets({k: v.cuda() for k, v in label.items()}, (H, W), (fh, fw))
+    dev = {k: v.cuda() for k, v in preds.items()}
+    L = eng.losses(dev, T).cpu()
+    for i, k in enumerate(LOSS_KEYS):
+        ref = float(torch.as_tensor(Lref[k]).detach())
+        print("B = %d %s: %.7g against %.7g" % (B, k, float(L[i]), ref))
+        assert abs(float(L[i]) - ref) <= 1e-4 * abs(ref) + 1e-7, (k, float(L[i]), ref)
+    d = eng.losses_backward(dev, T, w.float().cuda())
+    for k in raw:
+        e = rel_err(d[k].cpu(), raw[k].grad)
+        print("B = %d d %s: %.2e" % (B, k, e))
+        assert e < 2e-4, (k, e)
+        for b in empty:          # an image without objects takes a gradient from the two focal losses alone
+            if k not in ("center_heatmap_pred", "kpt_heatmap_pred"):
+                assert float(d[k][b].abs().max()) == 0.0 and float(raw[k].grad[b].abs().max()) == 0.0, (k, b)
 
 
 def test_fused_clip_adamw_vs_reference_golden(golden_sd):
