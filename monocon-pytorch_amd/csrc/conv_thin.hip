@@ -661,17 +661,17 @@ __global__ __launch_bounds__(256) void wgrad_thin16_kernel(const WgradArgs a) {
     }
 }
 
-bool wgrad_thin_ok(const WgradArgs &a, int ks, int stride) {
+bool wgrad_thin_ok(const WgradArgs &a, int ks, int stride) {      // (asked where wgrad_is_small(): that kernel's workgroup count)
 #ifdef MC_NO_WGRAD_THIN
     return false;
 #endif
-    return a.prec == 3 && a.small && ks == 3 && stride == 1 && a.nsrc == 1 && a.Cin == 16 && a.Cout == 16 && a.dy_ld == 16 &&
+    return a.prec == 3 && ks == 3 && stride == 1 && a.nsrc == 1 && a.Cin == 16 && a.Cout == 16 && a.dy_ld == 16 &&
            a.amax_x[0] && a.amax_dy && a.Wout % 4 == 0 && a.Hout == a.Hin && a.Wout == a.Win;
 }
 
-hipError_t launch_wgrad_thin(const WgradArgs &a, hipStream_t st) {
+hipError_t launch_wgrad_thin(const WgradPlan &p, hipStream_t st) {
     const size_t lds = 2 * WT_PLANE + 9 * 4 * 64 * sizeof(float);
-    return launch_dyn_lds<wgrad_thin16_kernel>(lds, dim3(a.ksplit), dim3(256), st, a);
+    return launch_dyn_lds<wgrad_thin16_kernel>(lds, dim3(p.a.ksplit), dim3(256), st, p.a);
 }
 
 }  // namespace mc

@@ -93,10 +93,11 @@ inline bool conv_fwd_args(ConvArgs &a, const ConvLayer &L, const std::vector<con
     return a.Cin == L.cin;
 }
 // The weight gradient of a ks x ks conv of the given stride in precision mode prec: X = the virtual concat of srcs, dY = the
-// first Cout of dy's dy_ld channels.  Fills sources, sizes and max-|x| slots and plans the tiling (wgrad_plan); `partial` stays
-// the caller's.  A caller that has changed a source calls again (the tiling does not depend on what a source holds).
-inline void wgrad_args(WgradArgs &a, const std::vector<const Tensor *> &srcs, const Tensor &dy, int dy_ld, int Cout, int ks,
+// first Cout of dy's dy_ld channels.  Fills sources, sizes and max-|x| slots, chooses the kernel and plans the tiling (wgrad_plan);
+// `p.a.partial` stays the caller's.  A caller that has changed a source calls again (the plan does not depend on what a source holds).
+inline void wgrad_args(WgradPlan &p, const std::vector<const Tensor *> &srcs, const Tensor &dy, int dy_ld, int Cout, int ks,
                        int stride, int prec) {
+    WgradArgs &a = p.a;
     const Tensor &s0 = *srcs[0];
     a.nsrc = (int)srcs.size();
     a.Cin = 0;
@@ -108,8 +109,8 @@ inline void wgrad_args(WgradArgs &a, const std::vector<const Tensor *> &srcs, co
     a.amax_dy = dy.amax;
     a.B = s0.B; a.Hin = s0.H; a.Win = s0.W; a.Hout = dy.H; a.Wout = dy.W; a.Cout = Cout;
     a.dy = dy.p; a.dy_ld = dy_ld;
-    a.prec = prec;
-    wgrad_plan(a, ks, stride);
+    a.prec = prec; p.ks = ks; p.stride = stride;
+    wgrad_plan(p);
 }
 
 struct DeconvLayer {

@@ -185,12 +185,12 @@ int mc_op_conv_wgrad(mc_handle *h, const float *const src[], const int src_chann
         for (int i = 0; i < nsrc; ++i) x[i].amax = slots.as<unsigned>() + i * mc::AMAX_WORDS;
         dyt.amax = slots.as<unsigned>() + 4 * mc::AMAX_WORDS;
     }
-    mc::WgradArgs a{};
-    wgrad_args(a, xs, dyt, Cout, Cout, ksize, stride, h->prec);
+    mc::WgradPlan p{};
+    wgrad_args(p, xs, dyt, Cout, Cout, ksize, stride, h->prec);
     void *part = nullptr;
-    HIPCHK(h, hipMalloc(&part, mc::wgrad_partial_floats(a, ksize) * sizeof(float)));
-    a.partial = static_cast<float *>(part);
-    hipError_t e = mc::launch_wgrad(a, ksize, stride, dw_oihw, st);
+    HIPCHK(h, hipMalloc(&part, mc::wgrad_partial_floats(p) * sizeof(float)));
+    p.a.partial = static_cast<float *>(part);
+    hipError_t e = mc::launch_wgrad(p, dw_oihw, st);
     hipError_t e2 = hipStreamSynchronize(st);
     (void)hipFree(part);
     HIPCHK(h, e);

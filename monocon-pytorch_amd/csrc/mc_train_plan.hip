@@ -588,15 +588,15 @@ struct TB {   // train plan builder
 
     // the weight gradient of a conv, on the weight-gradient stream: dy is not written again in this step.  Returns its step.
     int emit_wgrad(const std::vector<int> &srcs, const Tensor &dy, int dy_ld, int Cout, int ks, int stride, float *dw) {
-        WgradArgs a{};
+        WgradPlan p{};
         const std::vector<const Tensor *> xs = conv_sources(srcs);
-        wgrad_args(a, xs, dy, dy_ld, Cout, ks, stride, h->prec);
-        if (wgrad_any_lazy(a) && !wgrad_lazy_capable(a, ks, stride)) {      // X is read by a kernel that cannot form it: store it after all
+        wgrad_args(p, xs, dy, dy_ld, Cout, ks, stride, h->prec);
+        if (wgrad_any_lazy(p.a) && !wgrad_lazy_capable(p)) {      // X is read by a kernel that cannot form it: store it after all
             for (int s_ : srcs) materialise(s_);
-            wgrad_args(a, xs, dy, dy_ld, Cout, ks, stride, h->prec);
+            wgrad_args(p, xs, dy, dy_ld, Cout, ks, stride, h->prec);
         }
-        a.partial = alloc(wgrad_partial_floats(a, ks));
-        return push_bwd([=](mc_handle *hh, hipStream_t st) { HIPCHK(hh, launch_wgrad(a, ks, stride, dw, st)); return 0; }, ON_SIDE);
+        p.a.partial = alloc(wgrad_partial_floats(p));
+        return push_bwd([=](mc_handle *hh, hipStream_t st) { HIPCHK(hh, launch_wgrad(p, dw, st)); return 0; }, ON_SIDE);
     }
 
     // BN(+ReLU)(+residual) backward, ONE step.  dy: the gradient wrt the raw conv output.  caller_forms_dy: the caller

@@ -254,7 +254,10 @@ hipError_t launch_stem_wgrad(const float *img, const float *dy, int B, int H, in
 hipError_t launch_stem_dgrad(const float *dy, const float *w_oihw, int B, int H, int W, float *dx, hipStream_t st,
                              const float *y = nullptr, const float *coef = nullptr);
 
-// ---- conv weight gradient (wgrad_mfma.hip)
+// ---- conv weight gradient: wgrad_plan.hip chooses and launches; kernels in wgrad_mfma.hip (WG_FP32, WG_SMALL), wgrad_bf16.hip
+//      (WG_SPLIT: modes 1..3), wgrad_pipe.hip (WG_PIPE), conv_thin.hip (WG_THIN16).  WgradArgs is the kernels' parameter block:
+//      the hidden arguments (gridDim) lie behind it, so its layout is part of their machine code.  wgrad_plan() alone writes ksplit .. pipe.
+enum WgKernel { WG_FP32, WG_SPLIT, WG_PIPE, WG_SMALL, WG_THIN16 };
 struct WgradArgs {
     ConvSrc src[4];
     int nsrc;
@@ -263,11 +266,21 @@ struct WgradArgs {
     int dy_ld;
     float *partial;           // [ksplit][k*k][Cout][Cin]
     int ksplit, n_tiles, c_tiles, ppr, ppi, groups_per_img;
-    int small;                // 1: 16-input-channel layer on the LDS-free 16x16x4 kernel (ksplit = workgroups)
-    int prec;                 // 1: bf16 MFMA operands, 2: 3-way bf16 split, 3: 2-way fp16 split -- where wgrad_bf16_ok() (wgrad_bf16.hip)
+    int kernel;               // WgKernel (no kernel reads it).  WG_SMALL / WG_THIN16: ksplit = workgroups
+    int prec;                 // 1: bf16 MFMA operands, 2: 3-way bf16 split, 3: 2-way fp16 split -- where a kernel for the mode exists
     int pb;                   // 32-pixel patches per staged group (2, or 1 for the split kernels)
-    int pipe;                 // != 0: the software-pipelined fp16-split kernel (wgrad_pipe.hip) with this tile; ksplit = slices
+    int pipe;                 // WG_PIPE: the tile (wgrad_pipe_tile()); ksplit = slices
     const unsigned *amax_x[4], *amax_dy;   // prec 3: max |x| (bit patterns) of every source and of dY (see ConvArgs::amax_in)
+};
+static_assert(sizeof(WgradArgs) == 264, "WgradArgs is the kernels' parameter block: keep its layout");
+// One weight-gradient launch: the block and, host side, what wgrad_plan() decided.  wgrad_args() (mc_internal.h) fills one.
+struct WgradPlan {
+    WgradArgs a;
+    int ks, stride;
+    int WN, WC;               // wave grid of the workgroup, 32 channels of dY x 32 of X per wave (WG_FP32, WG_SPLIT, WG_PIPE)
+    bool lazy_ok;             // the chosen kernel forms lazy sources (ConvSrc::la) on load
+    bool ok;                  // false: no kernel runs these arguments -- launch_wgrad() returns hipErrorInvalidValue
+    size_t partial_floats;    // size of a.partial
 };
 // the patch grid of dY (WgradArgs::ppr / ppi) and the staged pixel groups per image of a kernel that stages pb patches
 inline void wgrad_set_patches(WgradArgs &a, int pb) {
@@ -296,19 +309,25 @@ inline size_t wgrad_lds_request(size_t need) {
     return need;
 #endif
 }
-void wgrad_plan(WgradArgs &a, int ks, int stride);            // fills the tiling fields
-size_t wgrad_partial_floats(const WgradArgs &a, int ks);
-hipError_t launch_wgrad(const WgradArgs &a, int ks, int stride, float *dw_oihw, hipStream_t st);
-// lazy X sources (ConvSrc::la in conv_mfma.h): does the kernel wgrad_plan() chose for `a` form them on load?  (mode 3:
-// wgrad_pipe_kernel's default tile, wgrad_bf16_kernel<SPL = 2>, wgrad_thin16_kernel; anything else fails such a launch)
-bool wgrad_lazy_capable(const WgradArgs &a, int ks, int stride);
-bool wgrad_bf16_ok(const WgradArgs &a, int ks, int stride);
-hipError_t launch_wgrad_bf16(const WgradArgs &a, int ks, int stride, int WN, int WC, hipStream_t st);
-int wgrad_bf16_patches(int prec);
+// wgrad_plan.hip.  wgrad_plan(): the operands, sizes and mode of p.a and p.ks / p.stride are set; chooses the kernel and fills
+// everything else (what a source holds does not enter the choice).  launch_wgrad(): that kernel + the split-K reduce.
+void wgrad_plan(WgradPlan &p);
+hipError_t launch_wgrad(const WgradPlan &p, float *dw_oihw, hipStream_t st);
+inline size_t wgrad_partial_floats(const WgradPlan &p) { return p.partial_floats; }
+// lazy X sources (ConvSrc::la in conv_mfma.h): does the chosen kernel form them on load?  (mode 3: wgrad_pipe_kernel's default
+// tile, wgrad_bf16_kernel<SPL = 2>, wgrad_thin16_kernel, wgrad_small_kernel<2, 2>; anything else fails such a launch)
+inline bool wgrad_lazy_capable(const WgradPlan &p) { return p.lazy_ok; }
+// What a kernel file says about its kernels (wgrad_plan() alone asks, in this order) and its launch (launch_wgrad() alone calls)
+bool wgrad_is_small(const WgradArgs &a, int ks, int stride);      // wgrad_mfma.hip: a 16-input-channel 3x3 layer
+bool wgrad_thin_ok(const WgradArgs &a, int ks, int stride);       // conv_thin.hip: the small 16 -> 16 layer on the fp16 pipe (mode 3)
 int wgrad_pipe_tile(const WgradArgs &a, int ks, int stride);      // wgrad_pipe.hip: 0 = not eligible
-void wgrad_pipe_plan(WgradArgs &a, int tile);
-hipError_t launch_wgrad_pipe(const WgradArgs &a, int ks, hipStream_t st);
-bool wgrad_thin_ok(const WgradArgs &a, int ks, int stride);        // conv_thin.hip: the 16 -> 16 layer on the fp16 pipe (mode 3)
-hipError_t launch_wgrad_thin(const WgradArgs &a, hipStream_t st);
+void wgrad_shape(const WgradArgs &a, int *WN, int *WC);           // wgrad_mfma.hip: the wave grid of WG_FP32 and WG_SPLIT
+bool wgrad_sources_ok(const WgradArgs &a);                        // ... and what both ask of the sources
+bool wgrad_bf16_ok(const WgradArgs &a, int ks, int stride);       // wgrad_bf16.hip (modes 1..3)
+hipError_t launch_wgrad_fp32(const WgradPlan &p, hipStream_t st);
+hipError_t launch_wgrad_small(const WgradPlan &p, hipStream_t st);
+hipError_t launch_wgrad_bf16(const WgradPlan &p, hipStream_t st);
+hipError_t launch_wgrad_pipe(const WgradPlan &p, hipStream_t st);
+hipError_t launch_wgrad_thin(const WgradPlan &p, hipStream_t st);
 
 }  // namespace mc

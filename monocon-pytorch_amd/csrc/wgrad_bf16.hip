@@ -20,8 +20,6 @@
 //     products per tap; the partial sums leave the kernel multiplied by the exact inverse of both scales.
 // Accumulation, split-K partials and the deterministic reduce stay fp32 (wgrad_reduce_kernel).
 // Stride-2 3x3 layers (round 3): template parameter S = 2, see WgB16Cfg.  The 16-channel layers keep their fp32 kernel.
-#include <algorithm>
-#include <cstdlib>
 #include "conv_mfma.h"
 #include "train.h"
 
@@ -80,10 +78,6 @@ __device__ __forceinline__ unsigned pack_bf16x2(float a, float b) {
     return __builtin_bit_cast(unsigned, v);
 }
 
-#ifdef MC_EXP_PHASE_DELAY
-__device__ int g_phase_delay = 0, g_phase_mode = 0;
-__device__ unsigned *g_lds_dbg = nullptr;
-#endif
 // LZ (SPL == 2): some source of X is a lazy tensor (ConvSrc::la in conv_mfma.h) -- see wgrad_pipe_kernel
 template <int KS, int S, int WN, int WC, int SPL, bool LZ = false>
 // stride 2 stages 2.7x the halo of stride 1 (6 instead of 2 float4 pairs per thread in flight across the MFMA phase): at
@@ -282,16 +276,6 @@ __global__ __launch_bounds__(64 * WN * WC, S == 2 ? MC_WG16_S2_OCC : 2) void wgr
     const unsigned char *a_base = dyt + (wn * 32 + lc) * DCH + lds_skew(wn * 32 + lc) + g * 16;
     const unsigned char *b_base = xt + (wc * 32 + lc) * XCH + lds_skew(wc * 32 + lc) + g * S * XROW;
 
-#ifdef MC_EXP_PHASE_DELAY
-    // experiment: the second workgroup of a CU (LDS base != 0) starts late, so that its staging phases fall into the other
-    // workgroup's MFMA phases instead of coinciding with its staging phases
-    {
-        const unsigned la = __builtin_amdgcn_s_getreg((31 << 11) | 6);   // HW_REG_LDS_ALLOC, all 32 bits
-        if (g_lds_dbg && threadIdx.x == 0) g_lds_dbg[blockIdx.x] = la;
-        if (g_phase_mode == 0 ? (la & 0xfff) != 0 : blockIdx.x >= gridDim.x / 2)
-            for (int i = 0; i < g_phase_delay; ++i) __builtin_amdgcn_s_sleep(8);      // 512 cycles each
-    }
-#endif
 #pragma unroll
     for (int d = 0; d < PD; ++d)
         if (g_begin + d < g_end) {
@@ -304,25 +288,13 @@ __global__ __launch_bounds__(64 * WN * WC, S == 2 ? MC_WG16_S2_OCC : 2) void wgr
         const int gi = g0 + d;
         if (gi >= g_end) break;       // (uniform over the workgroup)
         __syncthreads();   // fragment reads of the previous group are done
-#ifndef MC_EXP_NO_STORE
 #pragma unroll
         for (int p = 0; p < PB; ++p) store(p, d);
-#else
-#pragma unroll
-        for (int p = 0; p < PB; ++p) {      // the loads stay (and are waited for), the split + LDS writes go
-#pragma unroll
-            for (int i = 0; i < NIX; ++i) asm volatile("" ::"v"(xv[d][p][i][0]), "v"(xv[d][p][i][1]));
-#pragma unroll
-            for (int i = 0; i < NID; ++i) asm volatile("" ::"v"(dv[d][p][i][0]), "v"(dv[d][p][i][1]));
-        }
-#endif
         __syncthreads();
-#ifndef MC_EXP_NO_FETCH
         if (gi + PD < g_end) {
 #pragma unroll
             for (int p = 0; p < PB; ++p) fetch(gi + PD, p, d);
         }
-#endif
         // partial products (piece of dY, piece of X), smallest first; mode 1: the single (0, 0)
         constexpr int NP = SPL == 1 ? 1 : (SPL == 2 ? 3 : 6);
         constexpr int PA[6] = {SPL == 2 ? 1 : 0, SPL == 2 ? 0 : 2, SPL == 2 ? 0 : 1, 0, 1, 0};
@@ -367,11 +339,6 @@ __global__ __launch_bounds__(64 * WN * WC, S == 2 ? MC_WG16_S2_OCC : 2) void wgr
 #pragma unroll
                     for (int pp = 0; pp < NP; ++pp) {
                         const int za = SPL == 1 ? 0 : PA[pp], zx = SPL == 1 ? 0 : PX[pp];
-#ifdef MC_EXP_NO_MFMA
-                        asm volatile("" ::"v"(av[za]), "v"(b0[zx]), "v"(b1[zx]), "v"(b2[zx]));
-                        if (true) {
-                        } else
-#endif
                         if (KS == 1) {
                             acc[0] = wmfma_k16(av[za], __builtin_bit_cast(pc8, b0[zx]), acc[0]);
                         } else {
@@ -396,26 +363,25 @@ __global__ __launch_bounds__(64 * WN * WC, S == 2 ? MC_WG16_S2_OCC : 2) void wgr
     }
 }
 
-template <int KS, int S, int WN, int WC, int SPL, bool LZ = false>
+template <int KS, int S, int WN, int WC, int SPL>
 static hipError_t launch_wg16(const WgradArgs &a, hipStream_t st) {
     using Cfg = WgB16Cfg<KS, S, WN, WC, SPL>;
-    if (a.pb != Cfg::PB) return hipErrorInvalidValue;
-    if constexpr (!LZ) {
-        if (wgrad_any_lazy(a)) {
-            if constexpr (SPL == 2) return launch_wg16<KS, S, WN, WC, SPL, true>(a, st);
-            else return hipErrorInvalidValue;
-        }
+    const dim3 grid(a.ksplit * a.n_tiles * a.c_tiles);
+    if (a.pb != Cfg::PB) return hipErrorInvalidValue;      // (the groups wgrad_plan sized are not this build's)
+    if constexpr (SPL == 2) {      // (lazy sources: the LZ build, which only the fp16 split has -- WgradPlan::lazy_ok)
+        if (wgrad_any_lazy(a))
+            return launch_dyn_lds<wgrad_bf16_kernel<KS, S, WN, WC, SPL, true>>(wgrad_lds_request(Cfg::LDS_BYTES), grid, dim3(Cfg::NT), st, a);
     }
-    return launch_dyn_lds<wgrad_bf16_kernel<KS, S, WN, WC, SPL, LZ>>(wgrad_lds_request(Cfg::LDS_BYTES), dim3(a.ksplit * a.n_tiles * a.c_tiles),
-                                                                     dim3(Cfg::NT), st, a);
+    return launch_dyn_lds<wgrad_bf16_kernel<KS, S, WN, WC, SPL>>(wgrad_lds_request(Cfg::LDS_BYTES), grid, dim3(Cfg::NT), st, a);
 }
 
+// (asked after wgrad_is_small: the 16-channel layers keep their own kernels)
 bool wgrad_bf16_ok(const WgradArgs &a, int ks, int stride) {
-    if (a.small || (ks != 3 && ks != 1)) return false;
+    if (ks != 3 && ks != 1) return false;
 #ifdef MC_WG16_NO_S2
     if (stride == 2) return false;
 #endif
-    if (stride == 2) {        // the five stride-2 3x3 layers of DLA-34 (the 16-channel one keeps its own kernel: a.small)
+    if (stride == 2) {        // the five stride-2 3x3 layers of DLA-34
         if (ks != 3 || a.Hin != 2 * a.Hout || a.Win != 2 * a.Wout) return false;
     } else if (stride != 1 || a.Wout != a.Win || a.Hout != a.Hin) {
         return false;
@@ -431,22 +397,19 @@ bool wgrad_bf16_ok(const WgradArgs &a, int ks, int stride) {
     return a.dy_ld % 4 == 0;
 }
 
-// patches per staged pixel group of the kernel launch_wgrad_bf16 will run (wgrad_plan sizes the groups with it)
-int wgrad_bf16_patches(int prec) { return prec >= 2 ? 1 : 2; }
-
-// the main kernel of launch_wgrad in the bf16-pipe modes (the split-K reduce is shared); WN / WC as planned
+// the main kernel of launch_wgrad in the bf16-pipe modes (the split-K reduce is shared), on the planned wave grid
 template <int SPL>
-static hipError_t launch_wgrad_b16_spl(const WgradArgs &a, int ks, int stride, int WN, int WC, hipStream_t st) {
-    return with_wgrad_tile(WN, WC, [&](auto t) {
+static hipError_t launch_wgrad_b16_spl(const WgradPlan &p, hipStream_t st) {
+    return with_wgrad_tile(p.WN, p.WC, [&](auto t) {
         constexpr int N = decltype(t)::WN, C = decltype(t)::WC;
-        if (ks == 3 && stride == 2) return launch_wg16<3, 2, N, C, SPL>(a, st);
-        if (ks == 3) return launch_wg16<3, 1, N, C, SPL>(a, st);
-        return launch_wg16<1, 1, N, C, SPL>(a, st);
+        if (p.ks == 3 && p.stride == 2) return launch_wg16<3, 2, N, C, SPL>(p.a, st);
+        if (p.ks == 3) return launch_wg16<3, 1, N, C, SPL>(p.a, st);
+        return launch_wg16<1, 1, N, C, SPL>(p.a, st);
     });
 }
-hipError_t launch_wgrad_bf16(const WgradArgs &a, int ks, int stride, int WN, int WC, hipStream_t st) {
-    if (a.prec == 3) return launch_wgrad_b16_spl<2>(a, ks, stride, WN, WC, st);
-    return a.prec == 2 ? launch_wgrad_b16_spl<3>(a, ks, stride, WN, WC, st) : launch_wgrad_b16_spl<1>(a, ks, stride, WN, WC, st);
+hipError_t launch_wgrad_bf16(const WgradPlan &p, hipStream_t st) {
+    if (p.a.prec == 3) return launch_wgrad_b16_spl<2>(p, st);
+    return p.a.prec == 2 ? launch_wgrad_b16_spl<3>(p, st) : launch_wgrad_b16_spl<1>(p, st);
 }
 
 }  // namespace mc

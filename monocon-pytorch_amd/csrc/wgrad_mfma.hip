@@ -10,8 +10,6 @@
 // (split-K across workgroups); slices are written to a partial buffer and summed by a second,
 // deterministic pass that also converts to the OIHW layout of the master gradient.
 // Replaces autograd's conv2d weight backward for every Conv2d of the reference model.
-#include <algorithm>
-#include <cstdlib>
 #include "conv_mfma.h"
 #include "train.h"
 
@@ -364,21 +362,39 @@ __global__ __launch_bounds__(256) void wgrad_small_kernel(const WgradArgs a) {
     }
 }
 
-static bool wgrad_is_small(const WgradArgs &a, int ks, int stride) {
+// the 16-input-channel 3x3 layers wgrad_small_kernel (or, where wgrad_thin_ok(), wgrad_thin16_kernel) runs
+bool wgrad_is_small(const WgradArgs &a, int ks, int stride) {
     return ks == 3 && a.nsrc == 1 && a.Cin == 16 && (a.Cout == 16 || a.Cout == 32) && a.dy_ld == a.Cout &&
            (stride == 1 || stride == 2) && a.Wout % 4 == 0 && a.Wout >= 8 &&
            a.Hout == (a.Hin + 2 - 3) / stride + 1 && a.Wout == (a.Win + 2 - 3) / stride + 1;
 }
+hipError_t launch_wgrad_small(const WgradPlan &p, hipStream_t st) {
+    const WgradArgs &a = p.a;
+    if (a.src[0].la && !a.src[0].lb) return hipErrorInvalidValue;
+    auto *kern = p.stride == 1 ? (a.Cout == 16 ? wgrad_small_kernel<1, 1> : wgrad_small_kernel<1, 2>)
+                               : (a.Cout == 16 ? wgrad_small_kernel<2, 1> : wgrad_small_kernel<2, 2>);
+    if (a.src[0].la) kern = wgrad_small_kernel<2, 2, true>;      // lazy X (WgradPlan::lazy_ok: the stride-2 16 -> 32 layer)
+    hipLaunchKernelGGL(kern, dim3(a.ksplit), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
 
 template <int KS, int S, int WN, int WC>
-static hipError_t launch_wg(WgradArgs a, hipStream_t st) {
+static hipError_t launch_wg(const WgradArgs &a, hipStream_t st) {
     using Cfg = WgCfg<KS, S, WN, WC>;
     return launch_dyn_lds<wgrad_mfma_kernel<KS, S, WN, WC>>(wgrad_lds_request(Cfg::LDS_BYTES), dim3(a.ksplit * a.n_tiles * a.c_tiles),
                                                             dim3(Cfg::NT), st, a);
 }
+hipError_t launch_wgrad_fp32(const WgradPlan &p, hipStream_t st) {
+    return with_wgrad_tile(p.WN, p.WC, [&](auto t) {
+        constexpr int N = decltype(t)::WN, C = decltype(t)::WC;
+        if (p.ks == 3 && p.stride == 1) return launch_wg<3, 1, N, C>(p.a, st);
+        if (p.ks == 3) return launch_wg<3, 2, N, C>(p.a, st);
+        return launch_wg<1, 1, N, C>(p.a, st);
+    });
+}
 
 // shape choice: 64n x 64c (2x2 waves) wherever both dimensions allow, 128 x 32 for thin inputs, single-wave tiles for <= 32
-static void wgrad_shape(const WgradArgs &a, int *WN, int *WC) {
+void wgrad_shape(const WgradArgs &a, int *WN, int *WC) {
     bool src64 = true;   // a c-tile must lie inside one source of the virtual concat
     for (int i = 0; i < a.nsrc; ++i) src64 = src64 && (a.nsrc == 1 || a.src[i].C % 64 == 0);
     // measured on MI355X (scratch/wgexp): the 64n x 64c workgroup beats 128n x 32c by 3-8 %
@@ -387,86 +403,10 @@ static void wgrad_shape(const WgradArgs &a, int *WN, int *WC) {
     else if (a.Cout > 32) { *WN = 2; *WC = 1; }
     else { *WN = 1; *WC = 1; }
 }
-static bool wgrad_sources_ok(const WgradArgs &a) {
+bool wgrad_sources_ok(const WgradArgs &a) {
     for (int i = 0; i < a.nsrc; ++i)
         if (a.src[i].C % 4 || (a.nsrc > 1 && a.src[i].C % 32)) return false;
     return a.dy_ld % 4 == 0;
-}
-
-void wgrad_plan(WgradArgs &a, int ks, int stride) {
-    a.small = 0;
-    a.pipe = 0;
-    if (wgrad_is_small(a, ks, stride)) {
-        a.small = 1;
-        const int rows = a.B * a.Hout;
-        a.ksplit = std::min(rows / 4 > 0 ? rows / 4 : 1, 1024);   // >= 4 rows (one per wave) per workgroup
-        a.n_tiles = a.c_tiles = 1;
-        a.ppr = a.ppi = a.groups_per_img = 0;
-        return;
-    }
-    if (const int tile = wgrad_pipe_tile(a, ks, stride)) { wgrad_pipe_plan(a, tile); return; }
-    int WN, WC;
-    wgrad_shape(a, &WN, &WC);
-    a.n_tiles = (a.Cout + 32 * WN - 1) / (32 * WN);
-    a.c_tiles = (a.Cin + 32 * WC - 1) / (32 * WC);
-    a.pb = (a.prec >= 1 && wgrad_bf16_ok(a, ks, stride)) ? wgrad_bf16_patches(a.prec) : 2;
-    wgrad_set_patches(a, a.pb);
-    const long long G = (long long)a.B * a.groups_per_img;
-    // two resident 4-wave workgroups per CU (MONOCON_HIP_WGRAD_BLOCKS: experiment knob, e.g. 256 = one per CU, which
-    // leaves half of every SIMD's registers to whatever the main stream runs beside it)
-    const char *eb = std::getenv("MONOCON_HIP_WGRAD_BLOCKS");
-    const int target = eb ? std::atoi(eb) : 512;
-    int ks_ = target * 4 / (WN * WC) / (a.n_tiles * a.c_tiles);
-    if (ks_ < 1) ks_ = 1;
-    if (ks_ > G) ks_ = (int)G;
-    a.ksplit = ks_;
-}
-size_t wgrad_partial_floats(const WgradArgs &a, int ks) { return (size_t)a.ksplit * ks * ks * a.Cout * a.Cin; }
-
-bool wgrad_lazy_capable(const WgradArgs &a, int ks, int stride) {
-    if (a.prec != 3) return false;
-    if (a.pipe) return a.pipe == 4;
-    if (a.small) return wgrad_thin_ok(a, ks, stride) || (ks == 3 && stride == 2 && a.Cout == 32 && a.nsrc == 1);      // (wgrad_small_kernel<2, 2, LZ>)
-    return wgrad_sources_ok(a) && wgrad_bf16_ok(a, ks, stride);
-}
-
-hipError_t launch_wgrad(const WgradArgs &a, int ks, int stride, float *dw_oihw, hipStream_t st) {
-    if (wgrad_any_lazy(a) && !wgrad_lazy_capable(a, ks, stride)) return hipErrorInvalidValue;
-    prof_last = {2, 2.0 * a.B * a.Hout * a.Wout * (double)a.Cout * a.Cin * ks * ks,
-                 4.0 * ((double)a.B * a.Hin * a.Win * a.Cin + (double)a.B * a.Hout * a.Wout * a.Cout + (double)ks * ks * a.Cin * a.Cout)};
-    hipError_t e = hipErrorInvalidValue;
-    if (a.pipe) {
-        e = launch_wgrad_pipe(a, ks, st);
-    } else if (a.small && wgrad_thin_ok(a, ks, stride)) {
-        e = launch_wgrad_thin(a, st);
-    } else if (a.small && a.src[0].la) {      // lazy X: the stride-2 16 -> 32 layer (DLA level1) is the one that needs it
-        if (stride == 2 && a.Cout == 32 && a.src[0].lb) hipLaunchKernelGGL((wgrad_small_kernel<2, 2, true>), dim3(a.ksplit), dim3(256), 0, st, a);
-        else return hipErrorInvalidValue;
-        e = hipGetLastError();
-    } else if (a.small) {
-        if (stride == 1 && a.Cout == 16) hipLaunchKernelGGL((wgrad_small_kernel<1, 1>), dim3(a.ksplit), dim3(256), 0, st, a);
-        else if (stride == 1) hipLaunchKernelGGL((wgrad_small_kernel<1, 2>), dim3(a.ksplit), dim3(256), 0, st, a);
-        else if (a.Cout == 16) hipLaunchKernelGGL((wgrad_small_kernel<2, 1>), dim3(a.ksplit), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((wgrad_small_kernel<2, 2>), dim3(a.ksplit), dim3(256), 0, st, a);
-        e = hipGetLastError();
-    } else {
-        int WN, WC;
-        wgrad_shape(a, &WN, &WC);
-        if (!wgrad_sources_ok(a)) return hipErrorInvalidValue;
-        if (a.prec >= 1 && wgrad_bf16_ok(a, ks, stride)) {
-            e = launch_wgrad_bf16(a, ks, stride, WN, WC, st);
-        } else {
-            e = with_wgrad_tile(WN, WC, [&](auto t) {
-                constexpr int N = decltype(t)::WN, C = decltype(t)::WC;
-                if (ks == 3 && stride == 1) return launch_wg<3, 1, N, C>(a, st);
-                if (ks == 3 && stride == 2) return launch_wg<3, 2, N, C>(a, st);
-                if (ks == 1 && stride == 1) return launch_wg<1, 1, N, C>(a, st);
-                return hipErrorInvalidValue;
-            });
-        }
-    }
-    if (e != hipSuccess) return e;
-    return launch_splitk_reduce(a.partial, a.ksplit, ks * ks, a.Cout, a.Cin, dw_oihw, st);
 }
 
 // dw (Cout, Cin, T) = sum over `ksplit` slices of partial[slice][T][Cout][Cin]   (Cin % 4 == 0)

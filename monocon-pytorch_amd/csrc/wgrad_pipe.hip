@@ -16,7 +16,6 @@
 // for the 64 x 64 tile, that the two 16-pixel halves of a group go to different waves and slices (WK = 2).
 // Tiles (cout x cin): 128 x 64 (WN 4, WC 2), 64 x 128 (WN 2, WC 4), 64 x 64 (WN 2, WC 2, WK 2); 8 waves each.
 // Reference: what autograd computes for nn.Conv2d.weight.grad (model/backbone/dla.py:21-29, dla_neck.py:56-57).
-#include <algorithm>
 #include <cstdlib>
 #include "conv_mfma.h"
 #include "train.h"
@@ -326,14 +325,7 @@ __global__ __launch_bounds__(64 * WN * WC * WK, WN * WC * WK == 4 ? 2 : 1) void 
 template <int KS, int WN, int WC, int WK, bool LZ = false>
 static hipError_t launch_wp(const WgradArgs &a, hipStream_t st) {
     using Cfg = WgPipeCfg<KS, WN, WC, WK>;
-    if constexpr (!LZ) {
-        if (wgrad_any_lazy(a)) {
-            if constexpr (WN == 2 && WC == 2 && WK == 1) return launch_wp<KS, WN, WC, WK, true>(a, st);      // (the default tile)
-            else return hipErrorInvalidValue;
-        }
-    }
     constexpr size_t lds_bytes = Cfg::LDS_BYTES + (LZ ? 2 * (Cfg::CB / 4) * 16 : 0);      // (+ the lazy coefficient table)
-    if (a.ksplit % WK) return hipErrorInvalidValue;
     return launch_dyn_lds<wgrad_pipe_kernel<KS, WN, WC, WK, LZ>>(lds_bytes, dim3((a.ksplit / WK) * a.n_tiles * a.c_tiles), dim3(Cfg::NT), st, a);
 }
 
@@ -349,7 +341,7 @@ static hipError_t launch_wp(const WgradArgs &a, hipStream_t st) {
 int wgrad_pipe_tile(const WgradArgs &a, int ks, int stride) {
     const char *en = std::getenv("MONOCON_HIP_WGRAD_PIPE");
     const int enabled = en ? std::atoi(en) : 1;
-    if (!enabled || a.prec != 3 || stride != 1 || ks != 3 || a.small) return 0;
+    if (!enabled || a.prec != 3 || stride != 1 || ks != 3) return 0;      // (asked after wgrad_is_small)
     if (a.Wout != a.Win || a.Hout != a.Hin || a.dy_ld % 4 || !a.amax_dy) return 0;
     for (int i = 0; i < a.nsrc; ++i)
         if (!a.amax_x[i] || a.src[i].C % 4) return 0;
@@ -366,30 +358,13 @@ int wgrad_pipe_tile(const WgradArgs &a, int ks, int stride) {
     if (enabled >= 3 && a.Cout == 64 && a.Cin % 64 == 0 && src_mult(64)) return 3;
     return 0;
 }
-void wgrad_pipe_plan(WgradArgs &a, int tile) {
-    const int NB = tile == 1 ? 128 : 64, CB = tile == 2 ? 128 : 64, WK = tile == 3 ? 2 : 1;       // (tile 4: 64 x 64, 4 waves)
-    a.pipe = tile;
-    a.small = 0;
-    a.pb = 1;
-    a.n_tiles = (a.Cout + NB - 1) / NB;
-    a.c_tiles = (a.Cin + CB - 1) / CB;
-    wgrad_set_patches(a, a.pb);
-    const long long G = (long long)a.B * a.groups_per_img;
-    // (read per plan, not cached: the tests shrink it to run long pixel loops on small inputs)
-    const char *eb = std::getenv("MONOCON_HIP_WGRAD_PIPE_BLOCKS");
-    const int blocks = eb ? std::atoi(eb) : 256;
-    int kb = blocks / (a.n_tiles * a.c_tiles);        // one resident 8-wave workgroup per CU
-    if (kb < 1) kb = 1;
-    if (kb > G) kb = (int)G;
-    a.ksplit = kb * WK;
-}
-hipError_t launch_wgrad_pipe(const WgradArgs &a, int ks, hipStream_t st) {
-    if (ks != 3) return hipErrorInvalidValue;
-    switch (a.pipe) {
-    case 1: return launch_wp<3, 4, 2, 1>(a, st);
-    case 2: return launch_wp<3, 2, 4, 1>(a, st);
-    case 3: return launch_wp<3, 2, 2, 2>(a, st);
-    case 4: return launch_wp<3, 2, 2, 1>(a, st);
+// (the slices per tile: wgrad_plan, MONOCON_HIP_WGRAD_PIPE_BLOCKS.  Lazy sources: the default tile's LZ build, WgradPlan::lazy_ok)
+hipError_t launch_wgrad_pipe(const WgradPlan &p, hipStream_t st) {
+    switch (p.a.pipe) {
+    case 1: return launch_wp<3, 4, 2, 1>(p.a, st);
+    case 2: return launch_wp<3, 2, 4, 1>(p.a, st);
+    case 3: return launch_wp<3, 2, 2, 2>(p.a, st);
+    case 4: return wgrad_any_lazy(p.a) ? launch_wp<3, 2, 2, 1, true>(p.a, st) : launch_wp<3, 2, 2, 1>(p.a, st);
     default: return hipErrorInvalidValue;
     }
 }
