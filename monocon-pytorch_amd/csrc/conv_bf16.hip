@@ -417,31 +417,19 @@ __global__ __launch_bounds__(64 * WM * WN, SPL == 1 ? 3 : 2) void conv_bf16_kern
 #endif
 }
 
-// ---- dispatch
-template <int KS, int S, class Sh, int SPL, bool BM = false, bool LZ = false>
-static hipError_t launch_b16_one(ConvArgs a, hipStream_t st, ConvArgs *resolved) {
+// ---- launch: the build conv_plan() chose (p.shape, p.spl, p.bm, p.lz)
+template <int KS, int S, class Sh, int SPL>
+static hipError_t launch_b16_one(const ConvPlan &p, hipStream_t st) {
     using Cfg = ConvCfgB16<KS, S, Sh::WM, Sh::WN, Sh::WTM, Sh::WTN, SPL>;
     static_assert(Cfg::PB == Sh::PB && Cfg::BNT == Sh::BNT, "the shape table and the kernel agree on the tile");
-    if constexpr (!LZ) {
-        if (conv_any_lazy(a)) {      // lazy sources: forward launches of the fp16-split mode (3x3 stride 1 / 2 and 1x1), never a data gradient
-            if constexpr (SPL == 2 && !BM && (KS == 3 || KS == 1)) {
-                if (a.bm_y) return hipErrorInvalidValue;
-                return launch_b16_one<KS, S, Sh, SPL, false, true>(a, st, resolved);
-            } else {
-                return hipErrorInvalidValue;
-            }
-        }
-    }
-    if constexpr (!BM && S == 1 && (KS == 3 || KS == 1)) {      // backward-statistics epilogue: own instantiation
-        if (a.bm_y) return launch_b16_one<KS, S, Sh, SPL, true>(a, st, resolved);
-    } else if constexpr (!BM) {
-        if (a.bm_y) return hipErrorInvalidValue;
-    }
-    conv_set_patches(a, Cfg::PB);
-    if (a.CoutP % Cfg::BNT) return hipErrorInvalidValue;
-    if (resolved) *resolved = a;
-    return launch_dyn_lds<conv_bf16_kernel<KS, S, Sh::WM, Sh::WN, Sh::WTM, Sh::WTN, SPL, BM, LZ>>(
-        Cfg::LDS_BYTES, dim3((unsigned)(a.B * a.chunks * (a.CoutP / Cfg::BNT))), dim3(Cfg::NT), st, a);
+    const ConvArgs &a = p.a;
+    const dim3 grid((unsigned)(a.B * a.chunks * (a.CoutP / Cfg::BNT)));
+    // lazy sources: forward launches of the fp16-split mode (3x3 stride 1 / 2 and 1x1), never a data gradient
+    if constexpr (SPL == 2 && (KS == 3 || KS == 1))
+        if (p.lz) return launch_dyn_lds<conv_bf16_kernel<KS, S, Sh::WM, Sh::WN, Sh::WTM, Sh::WTN, SPL, false, true>>(Cfg::LDS_BYTES, grid, dim3(Cfg::NT), st, a);
+    if constexpr (S == 1 && (KS == 3 || KS == 1))      // backward-statistics epilogue: own instantiation
+        if (p.bm) return launch_dyn_lds<conv_bf16_kernel<KS, S, Sh::WM, Sh::WN, Sh::WTM, Sh::WTN, SPL, true, false>>(Cfg::LDS_BYTES, grid, dim3(Cfg::NT), st, a);
+    return launch_dyn_lds<conv_bf16_kernel<KS, S, Sh::WM, Sh::WN, Sh::WTM, Sh::WTN, SPL, false, false>>(Cfg::LDS_BYTES, grid, dim3(Cfg::NT), st, a);
 }
 
 bool conv_bf16_ok(const ConvArgs &a, int ks, int stride) {
@@ -458,18 +446,17 @@ bool conv_bf16_ok(const ConvArgs &a, int ks, int stride) {
 }
 
 template <int SPL>
-static hipError_t launch_conv_b16_spl(const ConvArgs &a, int ks, int stride, hipStream_t st, ConvArgs *resolved) {
-    return with_conv_window(ks, stride, [&](auto win) {
-        return with_conv_shape(a.cfg, [&](auto sh) {
-            return launch_b16_one<decltype(win)::KS, decltype(win)::S, decltype(sh), SPL>(a, st, resolved);
+static hipError_t launch_conv_b16_spl(const ConvPlan &p, hipStream_t st) {
+    return with_conv_window(p.ks, p.stride, [&](auto win) {
+        return with_conv_shape(p.shape, [&](auto sh) {
+            return launch_b16_one<decltype(win)::KS, decltype(win)::S, decltype(sh), SPL>(p, st);
         });
     });
 }
 
-hipError_t launch_conv_bf16(const ConvArgs &a, int ks, int stride, hipStream_t st, ConvArgs *resolved) {
-    if (!conv_bf16_ok(a, ks, stride)) return hipErrorInvalidValue;
-    if (a.prec == 3) return launch_conv_b16_spl<2>(a, ks, stride, st, resolved);
-    return a.prec == 2 ? launch_conv_b16_spl<3>(a, ks, stride, st, resolved) : launch_conv_b16_spl<1>(a, ks, stride, st, resolved);
+hipError_t launch_conv_bf16(const ConvPlan &p, hipStream_t st) {
+    if (p.spl == 2) return launch_conv_b16_spl<2>(p, st);
+    return p.spl == 3 ? launch_conv_b16_spl<3>(p, st) : launch_conv_b16_spl<1>(p, st);
 }
 
 }  // namespace mc

@@ -27,9 +27,11 @@
 //     wave-uniform SGPR offset per K-chunk / tap -- no vector address arithmetic in the K loop.
 // Family: conv_mfma_kernel (this tiling) and conv_mfma_ws_kernel (producer wave + double-buffered LDS), both in
 // conv_mfma.hip; conv_small_kernel (conv_small.hip: 16/32-channel layers on 16x16x4, no LDS), conv_bf16_kernel
-// (conv_bf16.hip: bf16 operands, or fp32 emulated by a 3-way bf16 split).  launch_conv() dispatches on
-// ConvArgs::cfg / ::prec; results of the fp32 variants are bit-identical across workgroup shapes.
-// This header is what the family shares: the contract (ConvArgs, the shape ids and their table CONV_SHAPES, the
+// (conv_bf16.hip: bf16 operands, or fp32 emulated by a bf16 / fp16 split), conv_wres_kernel (conv_wres.hip) and
+// conv_thin16_kernel (conv_thin.hip).  conv_plan() (conv_plan.hip) chooses among them once per launch description, from
+// ConvArgs::cfg / ::prec and what each kernel file says it can run; launch_conv() looks the choice up.  Results of the fp32
+// variants are bit-identical across workgroup shapes.
+// This header is what the family shares: the contract (ConvArgs, ConvPlan, the shape ids and their table CONV_SHAPES, the
 // prototypes), the host-side visitors and the one dynamic-LDS launcher (with_conv_shape, with_conv_window,
 // launch_dyn_lds), and the device helpers every kernel file uses (buffer access, max-|x| slots, xcd_order, conv_wg,
 // conv_epilogue).  No kernel is defined here.
@@ -553,17 +555,6 @@ inline int conv_ck(int ks, int stride, const int *src_c, int nsrc) {
 // stride (stride-2 halos are 9x17 pixels per patch, so fewer patches per workgroup keep several
 // workgroups resident per CU) and on how many workgroups the launch would have.
 int conv_pick_cfg(int Cout, int CoutP, int ks, int stride, int B, int Hout, int Wout);
-// statistics partials per image a launch with this shape writes (ConvArgs::chunks)
-inline int conv_chunks_per_image(int cfg, int Hout, int Wout) {
-    if (cfg == CFG_SMALL) return Hout;                    // the row kernel: one partial per output row
-    return ((Wout + 7) / 8) * ((Hout + 3) / 4);           // every tiling: one partial per 4x8 patch
-}
-// the patch grid of the output (ConvArgs::ppr / ppi) and the workgroup chunks per image of a kernel that owns PB patches
-inline void conv_set_patches(ConvArgs &a, int PB) {
-    a.ppr = (a.Wout + 7) / 8;
-    a.ppi = a.ppr * ((a.Hout + 3) / 4);
-    a.chunks = (a.ppi + PB - 1) / PB;
-}
 // does any source carry lazy coefficients (ConvSrc::la)?
 inline bool any_lazy_src(const ConvSrc *src, int nsrc) {
     for (int i = 0; i < nsrc; ++i)
@@ -571,30 +562,59 @@ inline bool any_lazy_src(const ConvSrc *src, int nsrc) {
     return false;
 }
 inline bool conv_any_lazy(const ConvArgs &a) { return any_lazy_src(a.src, a.nsrc); }
-bool conv_small_ok(const ConvArgs &a, int ks, int stride);
+
+// ---- one conv launch: the block and, host side, what conv_plan() decided (conv_plan.hip).  conv_fwd_args() (mc_internal.h) and
+//      dgrad_conv_args() (train.h) fill one.  ConvArgs is the kernels' parameter block: the hidden arguments (gridDim) lie
+//      behind it, so its layout is part of their machine code.
+static_assert(sizeof(ConvArgs) == 416, "ConvArgs is the kernels' parameter block: keep its layout");
+enum ConvKernel {
+    CONV_FP32,        // conv_mfma_kernel (conv_mfma.hip): the fp32 tilings
+    CONV_FP32_WS,     // conv_mfma_ws_kernel: the same tilings, wave-specialised
+    CONV_SPLIT,       // conv_bf16_kernel (conv_bf16.hip): the tilings on 16-bit pieces, modes 1..3
+    CONV_WRES,        // conv_wres_kernel (conv_wres.hip): weight-resident, persistent
+    CONV_ROW,         // conv_small_kernel (conv_small.hip): the 16 / 32-channel row kernel
+    CONV_ROW_LAZY,    // conv_small_kernel<2, 16, 2, true>: its build that forms a lazy source
+    CONV_THIN16       // conv_thin16_kernel (conv_thin.hip): the 16 -> 16 row kernel on the fp16 pipe
+};
+struct ConvPlan {
+    ConvArgs a;               // conv_plan() alone writes ppr / ppi / chunks and the dense pixel mapping (o_* / r_* given as 0)
+    int ks, stride;           // window code (win_h / win_w) and stride
+    int kernel;               // ConvKernel
+    int shape, ck, spl;       // the tilings: shape id (CFG_AUTO and the flags resolved), K-chunk (fp32), 16-bit pieces (CONV_SPLIT)
+    bool bm, lz;              // the build with the backward-statistics epilogue / that forms lazy sources (tilings, CONV_WRES)
+    bool ok;                  // false: no kernel runs this description -- launch_conv() returns hipErrorInvalidValue
+    bool lazy_ok;             // lazy sources (ConvSrc::la): a kernel that forms them on load exists for this layer once its id is chosen
+                              // (mode 3: conv_thin16, the lazy row build, conv_bf16<SPL = 2> for 3x3 stride 1 / 2 and 1x1, conv_wres;
+                              // independent of a.cfg); a launch with lazy sources that reaches any other kernel is not ok
+    bool bm_ok;               // the chosen kernel has a build with the backward-statistics epilogue (ConvArgs::bm_y) for this window
+    bool row_ok, b16;         // what the layer is eligible for whatever a.cfg says: the row family; the 16-bit tilings in this mode
+    int stat_rows;            // statistics partial rows per image (a.stats): one per output row (row family) or per 4x8 patch
+};
+// conv_plan.hip.  conv_plan(): the operands, sizes, mode, id and epilogue of p.a and p.ks / p.stride are set; chooses the kernel
+// and fills everything else.  What a source holds does not enter the choice; a caller that changes what does (a source's lazy
+// coefficients, a.cfg, a.stats, the bm_* fields, the pixel mapping) plans again.  launch_conv(): that kernel.
+void conv_plan(ConvPlan &p);
+hipError_t launch_conv(const ConvPlan &p, hipStream_t st);
+// What a kernel file says about its kernels (conv_plan() alone asks) and its launch (launch_conv() alone calls)
+bool conv_small_ok(const ConvArgs &a, int ks, int stride);          // conv_small.hip: the row family
 bool conv_small_lazy_ok(const ConvArgs &a, int ks, int stride);     // conv_small_kernel<2, 16, 2, LZ>: lazy source (ConvSrc::la)
-bool conv_bf16_ok(const ConvArgs &a, int ks, int stride);
-hipError_t launch_conv_bf16(const ConvArgs &a, int ks, int stride, hipStream_t st, ConvArgs *resolved);
+bool conv_thin_ok(const ConvArgs &a, int ks, int stride);           // conv_thin.hip
+bool conv_bf16_ok(const ConvArgs &a, int ks, int stride);           // conv_bf16.hip (modes 1..3)
+bool conv_wres_ok(const ConvArgs &a, int ks, int stride);           // conv_wres.hip: mode 3, 3x3 stride 1, one 64-channel source
+hipError_t launch_conv_fp32(const ConvPlan &p, hipStream_t st);     // CONV_FP32, CONV_FP32_WS
+hipError_t launch_conv_bf16(const ConvPlan &p, hipStream_t st);
+hipError_t launch_conv_wres(const ConvPlan &p, hipStream_t st);
+hipError_t launch_conv_small(const ConvPlan &p, hipStream_t st);    // CONV_ROW, CONV_ROW_LAZY
+hipError_t launch_conv_thin(const ConvPlan &p, hipStream_t st);
 // max |x| of a dense fp32 tensor folded into *slot (bit pattern; the caller zeroes the slot): for tensors that enter the
 // fp16-split mode from outside the plans' own producers (op-level entry points, stage-level forwards)
 // (single_word: a weight slot -- one word; otherwise a tensor slot of AMAX_WORDS words)
 hipError_t launch_absmax(const float *x, size_t n, unsigned *slot, hipStream_t st, bool single_word = false);
-bool conv_wres_ok(const ConvArgs &a, int ks, int stride);             // conv_wres.hip: mode 3, 3x3 stride 1, one 64-channel source
-hipError_t launch_conv_wres(const ConvArgs &a, int ks, int stride, hipStream_t st, ConvArgs *resolved);
-hipError_t launch_conv_small(const ConvArgs &a, int stride, hipStream_t st);
-bool conv_thin_ok(const ConvArgs &a, int ks, int stride);            // conv_thin.hip
-hipError_t launch_conv_thin(const ConvArgs &a, hipStream_t st);
 // the four parity classes of a thin stride-2 data gradient (dY 32 -> 16 or 64 -> 32 channels) in one pass (conv_thin.hip)
 bool dgrad_s2_thin_ok(int prec, int ks, int stride, int dyC, int srcC, int CinTotal, int c_off, const unsigned *amax_dy,
                       const unsigned *amax_w, int H, int W);
 hipError_t launch_dgrad_s2_thin(const float *dy, int B, int H, int W, int dyC, const float *w_master, int CinTotal, int c_off, float *out,
                                 int accumulate, const unsigned *amax_dy, const unsigned *amax_w, hipStream_t st);
-
-hipError_t launch_conv(const ConvArgs &a, int ks, int stride, hipStream_t st, ConvArgs *resolved = nullptr);
-// lazy sources (ConvSrc::la): does launch_conv() have a kernel for these arguments that forms them on load?  (The fp16-pipe
-// kernels of mode 3: conv_thin16, conv_bf16<SPL = 2> for 3x3 stride 1 / 2 and 1x1, conv_wres; a launch with lazy sources
-// that reaches any other kernel fails.)  Independent of ConvArgs::cfg among the tilings of conv_bf16 / conv_wres.
-bool conv_lazy_capable(const ConvArgs &a, int ks, int stride);
 
 // Measurement aid (mc_profile_train): the last launch_conv / launch_wgrad on this host thread notes
 // its kernel family (1 = fused conv incl. dgrad, 2 = wgrad) and algorithmic FLOPs here.

@@ -1,20 +1,8 @@
-// The fp32 kernels of the fused MFMA convolution (contract, helpers and epilogue: conv_mfma.h) and launch_conv(), the
-// dispatch of the whole family.
-#include <cstdlib>
+// The fp32 kernels of the fused MFMA convolution (contract, helpers and epilogue: conv_mfma.h) and their launch
+// (launch_conv_fp32; the choice among the family's kernels: conv_plan.hip).
 #include "conv_mfma.h"
 
 namespace mc {
-
-thread_local ProfLast prof_last = {0, 0.0, 0.0};
-static ProfLast conv_cost(const ConvArgs &a, int ks) {
-    const double px_in = (double)a.B * a.Hin * a.Win, px_out = (double)a.B * a.Hout * a.Wout;
-    const double taps = win_h(ks) * win_w(ks);
-    // algorithmic bytes: the input, the output (+ the residual / the gradient accumulated into), the weights, and for a
-    // backward-statistics launch the forward's y (and z where the ReLU mask is the stored activation's)
-    const int extra = (a.res ? 1 : 0) + (a.bm_y ? 1 : 0) + ((a.bm_y && a.bm_relu == 1 && !a.bm_zbits) ? 1 : 0);      // (a bit-packed mask is 1/32 of a map: not counted)
-    return {1, 2.0 * px_out * a.Cout * a.Cin * taps,
-            4.0 * (px_in * a.Cin + px_out * a.Cout * (1 + extra) + taps * a.Cin * a.Cout)};
-}
 
 template <int KS, int S, int CK, int WM, int WN, int WTM, int WTN, bool BM = false>
 __global__ __launch_bounds__(64 * WM * WN, 3) void conv_mfma_kernel(const ConvArgs a) {
@@ -331,44 +319,32 @@ __global__ __launch_bounds__(64 * (WM * WN + 1), 3) void conv_mfma_ws_kernel(con
     }
 }
 
-// ---- dispatch
-template <int KS, int S, int CK, class Sh, bool BM = false>
-static hipError_t launch_one(ConvArgs a, hipStream_t st, ConvArgs *resolved) {
-    using Cfg = ConvCfg<KS, S, CK, Sh::WM, Sh::WN, Sh::WTM, Sh::WTN>;
-    static_assert(Cfg::PB == Sh::PB && Cfg::BNT == Sh::BNT, "the shape table and the kernel agree on the tile");
-    if constexpr (!BM && S == 1 && (KS == 3 || KS == 1)) {
-        // backward-statistics epilogue (ConvArgs::bm_y): its own instantiation, so that every other launch keeps the
-        // lean epilogue (the y / z loads cost ~25 VGPRs)
-        if (a.bm_y) return launch_one<KS, S, CK, Sh, true>(a, st, resolved);
-    } else if constexpr (!BM) {
-        if (a.bm_y) return hipErrorInvalidValue;
-    }
-    conv_set_patches(a, Cfg::PB);
-    if (a.CoutP % Cfg::BNT) return hipErrorInvalidValue;
-    if (resolved) *resolved = a;
-    return launch_dyn_lds<conv_mfma_kernel<KS, S, CK, Sh::WM, Sh::WN, Sh::WTM, Sh::WTN, BM>>(
-        Cfg::LDS_BYTES, dim3((unsigned)(a.B * a.chunks * (a.CoutP / Cfg::BNT))), dim3(Cfg::NT), st, a);
-}
-
+// ---- launch: the build conv_plan() chose (p.shape, p.ck, p.bm; CONV_FP32_WS: the wave-specialised kernel)
 template <int KS, int S, int CK, class Sh>
-static hipError_t launch_one_ws(ConvArgs a, hipStream_t st, ConvArgs *resolved) {
-    using Cfg = ConvCfgWS<KS, S, CK, Sh::WM, Sh::WN, Sh::WTM, Sh::WTN>;
+static hipError_t launch_one(const ConvPlan &p, hipStream_t st) {
+    using Cfg = ConvCfg<KS, S, CK, Sh::WM, Sh::WN, Sh::WTM, Sh::WTN>;
+    using CfgWS = ConvCfgWS<KS, S, CK, Sh::WM, Sh::WN, Sh::WTM, Sh::WTN>;
     static_assert(Cfg::PB == Sh::PB && Cfg::BNT == Sh::BNT, "the shape table and the kernel agree on the tile");
-    conv_set_patches(a, Cfg::PB);
-    if (a.CoutP % Cfg::BNT) return hipErrorInvalidValue;
-    if (resolved) *resolved = a;
-    return launch_dyn_lds<conv_mfma_ws_kernel<KS, S, CK, Sh::WM, Sh::WN, Sh::WTM, Sh::WTN>>(
-        Cfg::LDS_BYTES, dim3((unsigned)(a.B * a.chunks * (a.CoutP / Cfg::BNT))), dim3(Cfg::NT), st, a);
+    const ConvArgs &a = p.a;
+    const dim3 grid((unsigned)(a.B * a.chunks * (a.CoutP / Cfg::BNT)));
+    if constexpr (KS == 3 || KS == 1)
+        if (p.kernel == CONV_FP32_WS)
+            return launch_dyn_lds<conv_mfma_ws_kernel<KS, S, CK, Sh::WM, Sh::WN, Sh::WTM, Sh::WTN>>(CfgWS::LDS_BYTES, grid, dim3(CfgWS::NT), st, a);
+    // backward-statistics epilogue (ConvArgs::bm_y): its own instantiation, so that every other launch keeps the lean
+    // epilogue (the y / z loads cost ~25 VGPRs)
+    if constexpr (S == 1 && (KS == 3 || KS == 1))
+        if (p.bm) return launch_dyn_lds<conv_mfma_kernel<KS, S, CK, Sh::WM, Sh::WN, Sh::WTM, Sh::WTN, true>>(Cfg::LDS_BYTES, grid, dim3(Cfg::NT), st, a);
+    return launch_dyn_lds<conv_mfma_kernel<KS, S, CK, Sh::WM, Sh::WN, Sh::WTM, Sh::WTN, false>>(Cfg::LDS_BYTES, grid, dim3(Cfg::NT), st, a);
 }
 
-template <int KS, int S, int CK>
-static hipError_t launch_shape(const ConvArgs &a, hipStream_t st, ConvArgs *resolved) {
-    if (a.cfg & ~(CFG_SHAPE_BITS | CFG_WS)) return hipErrorInvalidValue;
-    return with_conv_shape(a.cfg, [&](auto sh) {
-        using Sh = decltype(sh);
-        if constexpr (KS == 3 || KS == 1)
-            if ((a.cfg & CFG_WS) && !a.bm_y) return launch_one_ws<KS, S, CK, Sh>(a, st, resolved);   // (the WS variant has no bm epilogue)
-        return launch_one<KS, S, CK, Sh>(a, st, resolved);
+hipError_t launch_conv_fp32(const ConvPlan &p, hipStream_t st) {
+    return with_conv_window(p.ks, p.stride, [&](auto win) {
+        constexpr int KS = decltype(win)::KS, S = decltype(win)::S;
+        return with_conv_shape(p.shape, [&](auto sh) {
+            if constexpr (!(KS == 3 && S == 2))      // (conv_ck: a stride-2 3x3 always stages 16-channel chunks)
+                if (p.ck == 32) return launch_one<KS, S, 32, decltype(sh)>(p, st);
+            return launch_one<KS, S, 16, decltype(sh)>(p, st);
+        });
     });
 }
 
@@ -381,52 +357,6 @@ int conv_pick_cfg(int Cout, int CoutP, int ks, int stride, int B, int Hout, int 
     if (nt == 128) return ks == 1 ? CFG_64x128 : CFG_128x128;
     if (nt == 64) return (ks == 1 || stride == 2) ? CFG_64x64 : CFG_128x64m;
     return CFG_128x32;
-}
-
-bool conv_lazy_capable(const ConvArgs &a, int ks, int stride) {
-    if (a.prec != 3 || a.bm_y) return false;
-    if (conv_thin_ok(a, ks, stride) || conv_small_lazy_ok(a, ks, stride)) return true;
-    return conv_bf16_ok(a, ks, stride) && (ks == 3 || ks == 1);
-}
-
-hipError_t launch_conv(const ConvArgs &a_in, int ks, int stride, hipStream_t st, ConvArgs *resolved) {
-    ConvArgs a = a_in;
-    const bool lazy = conv_any_lazy(a);
-    const bool dense_out = a.o_px == 0;
-    if (dense_out) { a.o_px = a.out_ld; a.o_row = a.Wout * a.out_ld; a.o_img = a.Hout * a.Wout * a.out_ld; }
-    if (a.r_px == 0) { a.r_px = a.res_ld; a.r_row = a.Wout * a.res_ld; a.r_img = a.Hout * a.Wout * a.res_ld; }
-    if (a.cfg == CFG_SMALL && !dense_out) return hipErrorInvalidValue;
-    int sc[4];
-    for (int i = 0; i < a.nsrc; ++i) sc[i] = a.src[i].C;
-    const int ck = conv_ck(ks, stride, sc, a.nsrc);
-    for (int i = 0; i < a.nsrc; ++i)
-        if (sc[i] % ck) return hipErrorInvalidValue;
-    if (a.cfg == CFG_SMALL) {
-        if (!conv_small_ok(a, ks, stride)) return hipErrorInvalidValue;
-        if (lazy && !conv_thin_ok(a, ks, stride) && !conv_small_lazy_ok(a, ks, stride)) return hipErrorInvalidValue;
-        conv_set_patches(a, 1);
-        a.chunks = a.Hout;      // (the row kernel: one statistics partial per output row)
-        if (resolved) *resolved = a;
-        prof_last = conv_cost(a, ks);
-        return launch_conv_small(a, stride, st);
-    }
-    if (a.cfg == CFG_AUTO) a.cfg = conv_pick_cfg(a.Cout, a.CoutP, ks, stride, a.B, a.Hout, a.Wout);
-    prof_last = conv_cost(a, ks);
-    if (a.cfg & CFG_WRES) {
-        // MONOCON_HIP_WRES=0: A/B switch, every launch takes the tiling its shape bits name
-        static const bool wres_on = [] { const char *e = std::getenv("MONOCON_HIP_WRES"); return !e || std::atoi(e) != 0; }();
-        if (wres_on && conv_wres_ok(a, ks, stride)) return launch_conv_wres(a, ks, stride, st, resolved);
-        a.cfg &= ~CFG_WRES;
-    }
-    if (a.prec >= 1 && conv_bf16_ok(a, ks, stride)) return launch_conv_bf16(a, ks, stride, st, resolved);
-    if (lazy) return hipErrorInvalidValue;      // (nor do the fp32 MFMA kernels)
-    if (ks >= 10) a.cfg &= ~CFG_WS;      // the stride-2 data-gradient parity classes have no wave-specialised build
-    return with_conv_window(ks, stride, [&](auto win) {
-        constexpr int KS = decltype(win)::KS, S = decltype(win)::S;
-        if constexpr (!(KS == 3 && S == 2))      // (conv_ck: a stride-2 3x3 always stages 16-channel chunks)
-            if (ck == 32) return launch_shape<KS, S, 32>(a, st, resolved);
-        return launch_shape<KS, S, 16>(a, st, resolved);
-    });
 }
 
 }  // namespace mc

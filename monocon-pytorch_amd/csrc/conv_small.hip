@@ -245,10 +245,10 @@ bool conv_small_lazy_ok(const ConvArgs &a, int ks, int stride) {
     return conv_small_ok(a, ks, stride) && stride == 2 && a.Cin == 16 && a.Cout == 32 && a.src[0].la && a.src[0].lb;
 }
 
-hipError_t launch_conv_small(const ConvArgs &a, int stride, hipStream_t st) {
-    if (conv_thin_ok(a, 3, stride)) return launch_conv_thin(a, st);      // mode 3: the fp16-pipe kernel (conv_thin.hip)
-    if (a.src[0].la) {          // lazy source: the stride-2 16 -> 32 layer (DLA level1) is the one that needs it
-        if (!conv_small_lazy_ok(a, 3, stride)) return hipErrorInvalidValue;
+hipError_t launch_conv_small(const ConvPlan &p, hipStream_t st) {
+    const ConvArgs &a = p.a;
+    const int stride = p.stride;
+    if (p.kernel == CONV_ROW_LAZY) {      // lazy source: the stride-2 16 -> 32 layer (DLA level1) is the one that needs it
         int lblocks = (a.B * a.Hout + 3) / 4;
         if (lblocks > 2048) lblocks = 2048;
         hipLaunchKernelGGL((conv_small_kernel<2, 16, 2, true>), dim3(lblocks), dim3(256), 0, st, a);

@@ -308,7 +308,8 @@ bool conv_thin_ok(const ConvArgs &a, int ks, int stride) {
            a.Wout % 16 == 0 && a.Hout == a.Hin && a.Wout == a.Win && a.CoutP >= 16;
 }
 
-hipError_t launch_conv_thin(const ConvArgs &a, hipStream_t st) {
+hipError_t launch_conv_thin(const ConvPlan &p, hipStream_t st) {
+    const ConvArgs &a = p.a;
     const int tiles = a.B * ((a.Hout + TR - 1) / TR);
     hipLaunchKernelGGL((conv_thin16_kernel<1>), dim3(tiles < 4096 ? tiles : 4096), dim3(256), 0, st, a);
     return hipGetLastError();

@@ -480,11 +480,8 @@ static hipError_t launch_wres_one(const ConvArgs &a, int tpr, int tpi, int total
                                                                             a, tpr, tpi, total, per_wg, ngroups);
 }
 
-hipError_t launch_conv_wres(const ConvArgs &a_in, int ks, int stride, hipStream_t st, ConvArgs *resolved) {
-    if (!conv_wres_ok(a_in, ks, stride)) return hipErrorInvalidValue;
-    ConvArgs a = a_in;
-    conv_set_patches(a, 1);
-    if (resolved) *resolved = a;
+hipError_t launch_conv_wres(const ConvPlan &p, hipStream_t st) {
+    const ConvArgs &a = p.a;
     const int tpr = (a.Wout + 15) / 16, tpi = tpr * (a.Hout / 4), total = a.B * tpi, ngroups = a.CoutP / 64;
     // one workgroup per CU and column group where the work allows (>= 8 tiles each: the weight prologue is ~2 tiles of time)
     // (the CU count of the CURRENT device, remembered per device: handles on different GPUs share this process -- ADVICE r5)
@@ -514,13 +511,12 @@ hipError_t launch_conv_wres(const ConvArgs &a_in, int ks, int stride, hipStream_
     }
 #endif
     const bool res = a.res != nullptr, stats = a.stats != nullptr;
-    if (a.src[0].la) {       // lazy source: forward launches (no backward-statistics twin reads an activation)
-        if (a.bm_y || !a.src[0].lb) return hipErrorInvalidValue;
+    if (p.lz) {       // lazy source: forward launches (no backward-statistics twin reads an activation)
 #define WLZ(RES_, STATS_) launch_wres_one<false, RES_, STATS_, false, 0, true>(a, tpr, tpi, total, per_wg, ngroups, nwg, st)
         return res ? (stats ? WLZ(true, true) : WLZ(true, false)) : (stats ? WLZ(false, true) : WLZ(false, false));
 #undef WLZ
     }
-    if (a.bm_y) {
+    if (p.bm) {
         const bool zm = a.bm_relu == 1;
         return res ? (zm ? WL(true, true, true, true, 0) : WL(true, true, true, false, 0))
                    : (zm ? WL(true, false, true, true, 0) : WL(true, false, true, false, 0));

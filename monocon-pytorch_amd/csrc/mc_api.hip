@@ -79,15 +79,17 @@ ConvLayer &mc_conv_layer(mc_handle *h, const std::string &name, bool &ok) {
     return it->second;
 }
 
-int mc_head_conv_args(mc_handle *h, PlanAlloc &mem, const Tensor &feat, float *hidden, ConvArgs &a) {
+int mc_head_conv_args(mc_handle *h, PlanAlloc &mem, const Tensor &feat, float *hidden, ConvPlan &p) {
     const ConvLayer &L = h->head3;
-    conv_fwd_args(a, L, {&feat}, h->prec);
+    ConvArgs &a = p.a;
     a.bias = h->head_bias;
     a.out = hidden; a.out_ld = L.cout;
     a.cfg = L.cfg;
-    const int chunks = conv_chunks_per_image(a.cfg, a.Hout, a.Wout);
-    a.stats = mem.alloc((size_t)a.B * chunks * L.coutp * 2);
     a.stat_shift = h->head_rm;
+    conv_fwd_args(p, L, {&feat}, h->prec);
+    const int chunks = p.stat_rows;
+    a.stats = mem.alloc((size_t)a.B * chunks * L.coutp * 2);
+    conv_plan(p);
     return chunks;
 }
 
@@ -251,21 +253,21 @@ struct Builder {
         return t;
     }
 
-    // a conv launch whose arguments op.ca holds, with its algorithmic cost
+    // a conv launch whose arguments op.cp holds, planned once more here (its id and epilogue are set), with its algorithmic cost
     void push_conv(Op &op) {
-        const ConvArgs &a = op.ca;
+        conv_plan(op.cp);
+        const ConvArgs &a = op.cp.a;
         op.kind = OP_CONV;
         const double out_elems = (double)a.B * a.Hout * a.Wout * a.Cout;
-        op.flops = 2.0 * out_elems * a.Cin * op.ks * op.ks;
+        op.flops = 2.0 * out_elems * a.Cin * op.cp.ks * op.cp.ks;
         op.bytes = 4.0 * ((double)a.B * a.Hin * a.Win * a.Cin + out_elems * (a.res ? 2 : 1));
         pl->ops.push_back(op);
     }
 
     Tensor conv(const ConvLayer &L, const std::vector<const Tensor *> &srcs, const Tensor *res, bool relu) {
         Op op{};
-        op.ks = L.ks; op.stride = L.stride;
-        ConvArgs &a = op.ca;
-        if (!conv_fwd_args(a, L, srcs, h->prec)) { ok = false; h->err = "channel mismatch at " + L.conv; }
+        ConvArgs &a = op.cp.a;
+        if (!conv_fwd_args(op.cp, L, srcs, h->prec)) { ok = false; h->err = "channel mismatch at " + L.conv; }
         Tensor out = alloc(a.B, a.Hout, a.Wout, L.cout);
         a.amax_out = out.amax;
         a.scale = L.scale; a.bias = L.shift;
@@ -273,7 +275,7 @@ struct Builder {
         a.res_ld = res ? res->C : 0;
         a.out = out.p; a.out_ld = out.C;
         a.relu = relu ? 1 : 0;
-        a.cfg = L.cfg ? L.cfg : (ok ? mc_choose_conv_cfg(h, a, L.ks, L.stride) : CFG_128x32);
+        a.cfg = L.cfg ? L.cfg : (ok ? mc_choose_conv_cfg(h, op.cp) : CFG_128x32);
         push_conv(op);
         return out;
     }
@@ -283,9 +285,8 @@ struct Builder {
         const ConvLayer &L = h->head3;
         Tensor hidden = alloc(feat.B, feat.H, feat.W, L.cout);
         Op op{};
-        op.ks = L.ks; op.stride = L.stride;
-        ConvArgs &a = op.ca;
-        pl->head_chunks = mc_head_conv_args(h, mem, feat, hidden.p, a);
+        ConvArgs &a = op.cp.a;
+        pl->head_chunks = mc_head_conv_args(h, mem, feat, hidden.p, op.cp);
         pl->head_stats = a.stats;
         a.amax_out = hidden.amax;
         // per-patch centred second moments (head_attn_kernel combines them): whole 4x8 patches, no residual, and one partial
@@ -321,22 +322,27 @@ struct Builder {
 };
 }  // namespace
 
-int mc_choose_conv_cfg(mc_handle *h, const ConvArgs &a_in, int ks, int stride) {
-    const bool small_ok = conv_small_ok(a_in, ks, stride);
+// The shape id of a planned launch description (the id it carries is ignored).  conv_plan() is asked under CFG_AUTO for what
+// the layer is eligible for and for the default tiling, and under every candidate for whether it runs and on which family.
+int mc_choose_conv_cfg(mc_handle *h, const ConvPlan &p) {
+    ConvPlan t = p;
+    ConvArgs &a = t.a;
+    a.stats = nullptr;
+    auto plan_as = [&](int cfg) -> const ConvPlan & { a.cfg = cfg; conv_plan(t); return t; };
+    const int picked = plan_as(CFG_AUTO).shape;
+    const bool small_ok = t.row_ok, b16 = t.b16;
     if (h->dry_alloc)    // mc_query_workspace: nothing is launched; only row-kernel eligibility matters for buffer sizes
-        return (small_ok && !(a_in.prec >= 1 && conv_bf16_ok(a_in, ks, stride))) ? (int)CFG_SMALL
-                                                                               : conv_pick_cfg(a_in.Cout, a_in.CoutP, ks, stride, a_in.B, a_in.Hout, a_in.Wout);
+        return (small_ok && !b16) ? (int)CFG_SMALL : picked;
     // the 16x16x4 row kernel sums K in a different order than the 32x32x2 tilings: choosing it by eligibility, not by
     // timing, keeps results independent of the batch size / of autotuning noise (it is also the faster one)
-    if (small_ok && !(a_in.prec >= 1 && conv_bf16_ok(a_in, ks, stride))) return CFG_SMALL;
+    if (small_ok && !b16) return CFG_SMALL;
     if (h->force_cfg) return h->force_cfg;   // mc_set_conv_cfg: every other layer
-    int heuristic = small_ok ? (int)CFG_SMALL : conv_pick_cfg(a_in.Cout, a_in.CoutP, ks, stride, a_in.B, a_in.Hout, a_in.Wout);
+    const int heuristic = small_ok ? (int)CFG_SMALL : picked;
     if (!h->autotune) return heuristic;
-    const bool b16 = a_in.prec >= 1 && conv_bf16_ok(a_in, ks, stride);
-    const bool lazy = conv_any_lazy(a_in);      // lazy sources (ConvSrc::la) stage differently: their own entry
-    std::vector<int> key = {a_in.B, a_in.Hin, a_in.Win, ks, stride, a_in.Cout, a_in.CoutP, a_in.nsrc,
-                            (a_in.res ? 1 : 0) | (b16 ? 2 * a_in.prec : 0) | (lazy ? 64 : 0)};
-    for (int i = 0; i < a_in.nsrc; ++i) key.push_back(a_in.src[i].C);
+    const bool lazy = conv_any_lazy(a);      // lazy sources (ConvSrc::la) stage differently: their own entry
+    std::vector<int> key = {a.B, a.Hin, a.Win, t.ks, t.stride, a.Cout, a.CoutP, a.nsrc,
+                            (a.res ? 1 : 0) | (b16 ? 2 * a.prec : 0) | (lazy ? 64 : 0)};
+    for (int i = 0; i < a.nsrc; ++i) key.push_back(a.src[i].C);
     auto it = h->tuned.find(key);
     if (it != h->tuned.end()) return it->second;
     static const int cand[] = {CFG_128x128, CFG_128x64, CFG_128x64m, CFG_128x32, CFG_64x128, CFG_64x64,
@@ -344,20 +350,17 @@ int mc_choose_conv_cfg(mc_handle *h, const ConvArgs &a_in, int ks, int stride) {
                                CFG_WRES | CFG_128x64};
     hipEvent_t e0, e1;
     if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return heuristic;
-    ConvArgs a = a_in;
-    a.stats = nullptr;
     int best = heuristic;
     float best_ms = 1e30f;
     for (int c : cand) {
-        if (c == CFG_SMALL ? !small_ok : (a.CoutP % conv_shape(c).BNT()) != 0) continue;
-        if ((c & CFG_WS) && (ks >= 10 || b16)) continue;   // no wave-specialised build of these kernels
-        if ((c & CFG_WRES) && !conv_wres_ok(a, ks, stride)) continue;
-        a.cfg = c;
-        if (launch_conv(a, ks, stride, nullptr) != hipSuccess) { (void)hipGetLastError(); continue; }   // warm / unsupported
+        if (!plan_as(c).ok) continue;
+        // a flag that this launch would run without (no wave-specialised / weight-resident kernel for it) is no candidate of its own
+        if (((c & CFG_WS) && t.kernel != CONV_FP32_WS) || ((c & CFG_WRES) && t.kernel != CONV_WRES)) continue;
+        if (launch_conv(t, nullptr) != hipSuccess) { (void)hipGetLastError(); continue; }   // warm
         float t_min = 1e30f;
         for (int rep = 0; rep < 3; ++rep) {
             (void)hipEventRecord(e0, nullptr);
-            (void)launch_conv(a, ks, stride, nullptr);
+            (void)launch_conv(t, nullptr);
             (void)hipEventRecord(e1, nullptr);
             if (hipEventSynchronize(e1) != hipSuccess) { t_min = 1e30f; break; }
             float ms = 0.f;
@@ -505,7 +508,7 @@ static int run_op(mc_handle *h, const Op &op, hipStream_t st) {
             HIPCHK(h, launch_stem(op.in, op.B, op.H, op.W, op.w, op.scale, op.shift, op.out, st, 1, h->prec, op.amax));
             break;
         case OP_CONV:
-            HIPCHK(h, launch_conv(op.ca, op.ks, op.stride, st));
+            HIPCHK(h, launch_conv(op.cp, st));
             break;
         case OP_POOL:
             HIPCHK(h, launch_maxpool2(op.in, op.B, op.H, op.W, op.C, op.out, st));
@@ -951,12 +954,13 @@ int mc_op_conv(mc_handle *h, const float *const src[], const int src_channels[],
     PackBatch pack;         // the plans' packer, one job
     pack.add(pack_job_fwd(weight_oihw, Cout, L.cin, ksize, L.wpk, L.wpk16, L.cin, L.coutp, 0, h->prec, L.w_amax));
     HIPCHK(h, pack.launch(st, h->prec == 3));
-    ConvArgs a{};
-    conv_fwd_args(a, L, xs, h->prec);
+    ConvPlan cp{};
+    ConvArgs &a = cp.a;
     a.scale = scale; a.bias = bias; a.res = residual; a.res_ld = Cout;
     a.out = out; a.out_ld = Cout; a.relu = relu;
     a.cfg = h->force_cfg;
-    hipError_t e = launch_conv(a, ksize, stride, st);
+    conv_fwd_args(cp, L, xs, h->prec);
+    hipError_t e = launch_conv(cp, st);
     hipError_t e2 = hipStreamSynchronize(st);   // test entry point: the packed weights are a temporary
     HIPCHK(h, e);
     HIPCHK(h, e2);
@@ -1096,7 +1100,8 @@ int mc_bench_conv(mc_handle *h, int B, int Hin, int Win, int nsrc, const int src
                   int stride, int cfg, int iters, float *ms_avg) {
     if (!h || !src_channels || !ms_avg) return fail(h, "mc_bench_conv: null argument");
     HIPCHK(h, hipSetDevice(h->device));
-    ConvArgs a{};
+    ConvPlan cp{};
+    ConvArgs &a = cp.a;
     std::vector<void *> bufs;
     // MONOCON_BENCH_ZERO=1: all-zero operands (same instruction stream, minimal toggling): how much of a launch's time is
     // the power limit (DVFS) rather than stalls
@@ -1125,7 +1130,7 @@ int mc_bench_conv(mc_handle *h, int B, int Hin, int Win, int nsrc, const int src
     }
     const int Ho = conv_out_dim(Hin, ksize, stride), Wo = conv_out_dim(Win, ksize, stride);
     const size_t wn = fwd_panel_elems(ksize, L.cin, L.coutp), on = (size_t)B * Ho * Wo * Cout;
-    const size_t stats_n = (size_t)B * conv_chunks_per_image(CFG_AUTO, Ho, Wo) * L.coutp * 2;     // one partial per 4x8 patch
+    const size_t stats_n = (size_t)B * ((Wo + 7) / 8) * ((Ho + 3) / 4) * L.coutp * 2;     // one partial per 4x8 patch
     L.wpk = alloc_fill(wn, 0.05f);
     a.scale = alloc_fill(Cout, 1.0f);
     a.bias = alloc_fill(Cout, 1.0f);
@@ -1165,7 +1170,7 @@ int mc_bench_conv(mc_handle *h, int B, int Hin, int Win, int nsrc, const int src
         for (int i = 0; i < nsrc; ++i) x[i].amax = static_cast<unsigned *>(q) + (size_t)i * AMAX_WORDS;
         L.w_amax = static_cast<unsigned *>(q) + (size_t)4 * AMAX_WORDS;
     }
-    conv_fwd_args(a, L, xs, h->prec);
+    conv_fwd_args(cp, L, xs, h->prec);
 #ifdef MC_PHASE_TIMERS
     const size_t prof_n = (size_t)1 << 22;          // (workgroups x waves x 5) upper bound
     {
@@ -1179,11 +1184,11 @@ int mc_bench_conv(mc_handle *h, int B, int Hin, int Win, int nsrc, const int src
     hipEvent_t e0, e1;
     HIPCHK(h, hipEventCreate(&e0));
     HIPCHK(h, hipEventCreate(&e1));
-    hipError_t e = launch_conv(a, ksize, stride, nullptr);
-    if (e == hipSuccess) e = launch_conv(a, ksize, stride, nullptr);
+    hipError_t e = launch_conv(cp, nullptr);
+    if (e == hipSuccess) e = launch_conv(cp, nullptr);
     if (e == hipSuccess) {
         (void)hipEventRecord(e0, nullptr);
-        for (int i = 0; i < iters && e == hipSuccess; ++i) e = launch_conv(a, ksize, stride, nullptr);
+        for (int i = 0; i < iters && e == hipSuccess; ++i) e = launch_conv(cp, nullptr);
         (void)hipEventRecord(e1, nullptr);
         (void)hipEventSynchronize(e1);
         float ms = 0;
@@ -1369,8 +1374,8 @@ int mc_profile_forward(mc_handle *h, int iters, float out_ms[3], int out_n[3], v
             if (it == 0 && std::getenv("MONOCON_HIP_PROFILE_DUMP")) {       // measurement aid: one line per op of the eval plan
                 const Op &o = pl->ops[i];
                 if (o.kind == OP_CONV)
-                    std::fprintf(stderr, "fprof %zu conv k%d s%d %4d -> %-4d (%d src) %3dx%-4d res %d cfg %3d  ms %.4f  gflop %.2f  TF(fp32-eq) %.1f\n", i, o.ks,
-                                 o.stride, o.ca.Cin, o.ca.Cout, o.ca.nsrc, o.ca.Hout, o.ca.Wout, o.ca.res != nullptr, o.ca.cfg, ms, o.flops * 1e-9,
+                    std::fprintf(stderr, "fprof %zu conv k%d s%d %4d -> %-4d (%d src) %3dx%-4d res %d cfg %3d  ms %.4f  gflop %.2f  TF(fp32-eq) %.1f\n", i, o.cp.ks,
+                                 o.cp.stride, o.cp.a.Cin, o.cp.a.Cout, o.cp.a.nsrc, o.cp.a.Hout, o.cp.a.Wout, o.cp.a.res != nullptr, o.cp.a.cfg, ms, o.flops * 1e-9,
                                  o.flops / (ms * 1e-3) * 1e-12);
                 else
                     std::fprintf(stderr, "fprof %zu kind %d  ms %.4f  mb %.1f\n", i, (int)o.kind, ms, o.bytes * 1e-6);

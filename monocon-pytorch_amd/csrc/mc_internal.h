@@ -70,11 +70,13 @@ struct ConvLayer {
 };
 
 // The operands and geometry of the forward conv of layer L over the virtual concat of srcs (1..4 maps of one size) in precision
-// mode prec: every field of `a` that follows from them -- sources, sizes, panels, a.prec (the mode where L has piece planes, 0
-// otherwise) and in mode 3 the max-|x| slots of the operands.  Everything else is left as it is: the shape id and the epilogue
-// (scale, bias, res, relu, out, stats, amax_out, cfg) are the caller's, and a caller that has changed a source (TB::materialise)
-// calls again.  false: the sources do not add up to L.cin channels.  (The data gradient's counterpart: dgrad_conv_args, train.h.)
-inline bool conv_fwd_args(ConvArgs &a, const ConvLayer &L, const std::vector<const Tensor *> &srcs, int prec) {
+// mode prec: every field of `p.a` that follows from them -- sources, sizes, panels, a.prec (the mode where L has piece planes, 0
+// otherwise) and in mode 3 the max-|x| slots of the operands -- and L's window, then plans (conv_plan).  Everything else is left
+// as it is: the shape id and the epilogue (scale, bias, res, relu, out, stats, amax_out, cfg) are the caller's, who plans again
+// after setting a.cfg or a.stats; a caller that has changed a source (TB::materialise) calls again.  false: the sources do not
+// add up to L.cin channels.  (The data gradient's counterpart: dgrad_conv_args, train.h.)
+inline bool conv_fwd_args(ConvPlan &p, const ConvLayer &L, const std::vector<const Tensor *> &srcs, int prec) {
+    ConvArgs &a = p.a;
     const Tensor &s0 = *srcs[0];
     a.nsrc = (int)srcs.size();
     a.Cin = 0;
@@ -90,6 +92,8 @@ inline bool conv_fwd_args(ConvArgs &a, const ConvLayer &L, const std::vector<con
         for (int i = 0; i < a.nsrc; ++i) a.amax_in[i] = srcs[i]->amax;
         a.amax_w = L.w_amax;
     }
+    p.ks = L.ks; p.stride = L.stride;
+    conv_plan(p);
     return a.Cin == L.cin;
 }
 // The weight gradient of a ks x ks conv of the given stride in precision mode prec: X = the virtual concat of srcs, dY = the
@@ -190,17 +194,16 @@ void *mc_param(mc_handle *h, const std::string &name, int64_t numel, int dtype =
 // The layer-table entry `name`.  Missing: h->err names it, `ok` is cleared and an empty layer is returned.
 ConvLayer &mc_conv_layer(mc_handle *h, const std::string &name, bool &ok);
 // The fused head conv (64 -> 9 x 64, 3x3) of a plan on `feat` into `hidden`: head3's panels and shape id, head_bias, and the
-// per-patch statistics of (v - head_rm), whose buffer it takes from `mem`: [B][patches per image][head3.coutp][2] (a.stats).
+// per-patch statistics of (v - head_rm), whose buffer it takes from `mem`: [B][patches per image][head3.coutp][2] (p.a.stats).
 // Returns the patches per image.
-int mc_head_conv_args(mc_handle *h, PlanAlloc &mem, const Tensor &feat, float *hidden, ConvArgs &a);
+int mc_head_conv_args(mc_handle *h, PlanAlloc &mem, const Tensor &feat, float *hidden, ConvPlan &p);
 
 enum OpKind { OP_STEM, OP_CONV, OP_POOL, OP_DECONV, OP_HEAD_ATTN, OP_HEAD_APPLY };
 
 struct Op {
     OpKind kind;
     // conv
-    ConvArgs ca{};
-    int ks = 0, stride = 0;
+    ConvPlan cp{};
     // generic
     const float *in = nullptr;
     float *out = nullptr, *out2 = nullptr;   // out2: OP_HEAD_ATTN's second output (the AttnBN shift beside the scale)
@@ -346,5 +349,5 @@ static inline hipError_t op_amax_slots(ScratchBuf &buf, const float *const src[]
 // the static heuristic.  The accumulation order of an output element does not depend on the shape,
 // so the choice never changes results (per-image statistics partials are regrouped, not reordered
 // within a partial).  `a.stats` must be null while tuning (callers attach it afterwards).
-int mc_choose_conv_cfg(mc_handle *h, const mc::ConvArgs &a, int ks, int stride);
+int mc_choose_conv_cfg(mc_handle *h, const mc::ConvPlan &p);
 

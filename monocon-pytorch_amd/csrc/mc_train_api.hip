@@ -236,10 +236,11 @@ int mc_op_conv_dgrad(mc_handle *h, const float *dy, const float *weight_oihw, in
     }
     hipError_t e = pack.launch(st);
     for (int c = 0; c < nclass && e == hipSuccess; ++c) {
-        mc::ConvArgs d;
-        const int kk = mc::dgrad_conv_args(d, pack.jobs[c], h->prec, dy, dy_amax, B, Ho, Wo, Cout, dx, Hin, Win, accumulate != 0);
-        d.cfg = h->force_cfg;
-        e = mc::launch_conv(d, kk, 1, st);
+        mc::ConvPlan d;
+        mc::dgrad_conv_args(d, pack.jobs[c], h->prec, dy, dy_amax, B, Ho, Wo, Cout, dx, Hin, Win, accumulate != 0);
+        d.a.cfg = h->force_cfg;
+        mc::conv_plan(d);
+        e = mc::launch_conv(d, st);
     }
     hipError_t e2 = hipStreamSynchronize(st);   // test entry point: the panels are temporaries
     HIPCHK(h, e);

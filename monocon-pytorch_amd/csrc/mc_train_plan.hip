@@ -83,12 +83,12 @@ struct PoolBwdArgs {       // a max-pool backward launch (stable address: bn_bac
 struct LastWriter {
     enum Kind { NONE, DGRAD_CONV, POOL_BWD, DECONV_BWD } kind = NONE;
     union {
-        ConvArgs *conv;           // a generic stride-1 data-gradient conv: its epilogue masks the gradient and leaves the partials
+        ConvPlan *conv;           // a generic stride-1 data-gradient conv: its epilogue masks the gradient and leaves the partials
         PoolBwdArgs *pool;        // a max-pool backward that accumulated into the map (launch_maxpool2_bwd's stats_partial)
         float **deconv_stats;     // the fused depthwise-deconv backward of the map's only consumer: where to attach `stats`
     };
     LastWriter() : conv(nullptr) {}
-    LastWriter(ConvArgs *c) : kind(c ? DGRAD_CONV : NONE), conv(c) {}
+    LastWriter(ConvPlan *c) : kind(c ? DGRAD_CONV : NONE), conv(c) {}
     LastWriter(PoolBwdArgs *p) : kind(p ? POOL_BWD : NONE), pool(p) {}
     LastWriter(float **s) : kind(s ? DECONV_BWD : NONE), deconv_stats(s) {}
 };
@@ -146,7 +146,7 @@ struct TrainState {
     std::vector<Rec> recs;
     std::vector<Fn> fwd;
     std::vector<BwdStep> bwd;
-    std::deque<ConvArgs> dgrads;     // data-gradient launches (stable addresses: bn_backward may still patch them)
+    std::deque<ConvPlan> dgrads;     // data-gradient launches (stable addresses: bn_backward may still patch them)
     std::deque<PoolBwdArgs> pool_bwds;
     std::deque<float *> deconv_stats;      // per fused deconv backward: its statistics buffer (null until bn_backward attaches one)
     hipStream_t side = nullptr;      // the weight-gradient stream
@@ -458,23 +458,25 @@ struct TB {   // train plan builder
         const bool lazy = !dead && !never_lazy && res < 0 && h->prec == 3 && (sw.lazy_z & (relu ? 1 : 2)) != 0 &&
                           (!relu || s.elementwise_consumers || (long long)Ho * Wo * Lr.cout >= sw.lazy_min);
         r.z = dead ? -1 : node(B, Ho, Wo, Lr.cout, true, !lazy);
-        ConvArgs a{};
+        ConvPlan cp{};
+        ConvArgs &a = cp.a;
         const std::vector<const Tensor *> xs = conv_sources(srcs);
-        if (!conv_fwd_args(a, Lr, xs, h->prec)) { ts->ok = false; h->err = "train plan: channel mismatch at " + Lr.conv; }
-        if (conv_any_lazy(a) && !conv_lazy_capable(a, Lr.ks, Lr.stride)) {
+        if (!conv_fwd_args(cp, Lr, xs, h->prec)) { ts->ok = false; h->err = "train plan: channel mismatch at " + Lr.conv; }
+        if (conv_any_lazy(a) && !cp.lazy_ok) {
             for (int s_ : srcs) materialise(s_);
-            conv_fwd_args(a, Lr, xs, h->prec);
+            conv_fwd_args(cp, Lr, xs, h->prec);
         }
         a.out = r.y.p; a.out_ld = Lr.cout;
         unsigned *yslot = lazy ? slot() : nullptr;      // max |y|, left by the conv's epilogue: bn_finalize bounds max |z| with it
         a.amax_out = yslot;
-        a.cfg = ts->ok ? mc_choose_conv_cfg(h, a, Lr.ks, Lr.stride) : CFG_128x32;
-        const int chunks = conv_chunks_per_image(a.cfg, Ho, Wo);
+        a.cfg = ts->ok ? mc_choose_conv_cfg(h, cp) : CFG_128x32;
+        conv_plan(cp);
+        const int chunks = cp.stat_rows;
         float *stats = alloc((size_t)B * chunks * Lr.coutp * 2);
         a.stats = stats;
         a.stat_shift = P(Lr.bn + ".running_mean", Lr.cout);
-        const int ks = Lr.ks, stride = Lr.stride;
-        ts->fwd.push_back([=](mc_handle *hh, hipStream_t st) { HIPCHK(hh, launch_conv(a, ks, stride, st)); return 0; });
+        conv_plan(cp);
+        ts->fwd.push_back([=](mc_handle *hh, hipStream_t st) { HIPCHK(hh, launch_conv(cp, st)); return 0; });
         bn_act(r, stats, B * chunks, Lr.coutp, lazy, yslot);
         ts->recs.push_back(r);
         return r.z;
@@ -534,10 +536,11 @@ struct TB {   // train plan builder
         TNode &sn = ts->nodes[srcnode];
         if (!sn.needs_grad) return;
         g_acquire(srcnode);
-        // a stride-1 conv over dY with the panel of one output-parity class (-1: the whole flipped kernel); returns its window code
-        auto dgrad_conv = [&](int cls, ConvArgs &d) {
+        // a stride-1 conv over dY with the panel of one output-parity class (-1: the whole flipped kernel), its shape id chosen
+        auto dgrad_conv = [&](int cls, ConvPlan &d) {
             const PackJobDesc &p = pack_job(w_master, Cout_fwd, CinTotal, ks, c_off, sn.t.C, CoutPad, cls);
-            return dgrad_conv_args(d, p, h->prec, dy.p, dy.amax, dy.B, dy.H, dy.W, dy.C, sn.g, sn.t.H, sn.t.W, sn.ginit);
+            dgrad_conv_args(d, p, h->prec, dy.p, dy.amax, dy.B, dy.H, dy.W, dy.C, sn.g, sn.t.H, sn.t.W, sn.ginit);
+            d.a.cfg = ts->ok ? mc_choose_conv_cfg(h, d) : CFG_128x32;
         };
         if (stride == 2 && ks == 3) {
             // four output-parity classes, each a small stride-1 window conv over dY that scatters to every
@@ -558,18 +561,17 @@ struct TB {   // train plan builder
                 return;
             }
             for (int cls = 0; cls < 4; ++cls) {
-                ConvArgs d;
-                const int kk = dgrad_conv(cls, d);
-                d.cfg = ts->ok ? mc_choose_conv_cfg(h, d, kk, 1) : CFG_128x32;
-                push_bwd([=](mc_handle *hh, hipStream_t st) { HIPCHK(hh, launch_conv(d, kk, 1, st)); return 0; });
+                ConvPlan d;
+                dgrad_conv(cls, d);
+                conv_plan(d);
+                push_bwd([=](mc_handle *hh, hipStream_t st) { HIPCHK(hh, launch_conv(d, st)); return 0; });
             }
             wrote(srcnode);
             return;
         }
-        ConvArgs d;
-        dgrad_conv(-1, d);
         if (dy.H != sn.t.H || dy.W != sn.t.W) { ts->ok = false; h->err = "train plan: dgrad shape mismatch"; }
-        d.cfg = ts->ok ? mc_choose_conv_cfg(h, d, ks, 1) : CFG_128x32;
+        ConvPlan d;
+        dgrad_conv(-1, d);
         // The weight-resident kernel (conv_wres.hip) owns its CU -- four waves with the whole register file -- so beside the
         // weight-gradient stream it cannot share one the way the tiled kernels do and the two streams take
         // turns: measured in the step (rocprofv3) a plain 64 -> 64 data gradient takes ~595 us on it against 389 us
@@ -578,12 +580,13 @@ struct TB {   // train plan builder
         // with the twins on it.  Backward launches therefore keep the tiled kernels.
         // MONOCON_HIP_WRES_BWD: 0 (default) = never in the backward, 1 = the twins (bn_backward sets the flag), 2 = wherever
         // the autotuner chose it
-        if (sw.wres_bwd < 2) d.cfg &= ~CFG_WRES;
+        if (sw.wres_bwd < 2) d.a.cfg &= ~CFG_WRES;
+        conv_plan(d);
         ts->dgrads.push_back(d);
-        ConvArgs *dp = &ts->dgrads.back();
-        push_bwd([=](mc_handle *hh, hipStream_t st) { HIPCHK(hh, launch_conv(*dp, ks, 1, st)); return 0; });
+        ConvPlan *dp = &ts->dgrads.back();
+        push_bwd([=](mc_handle *hh, hipStream_t st) { HIPCHK(hh, launch_conv(*dp, st)); return 0; });
         // (the fp32 row kernel has no backward-statistics epilogue; its fp16-pipe replacement for 16 -> 16 layers has)
-        wrote(srcnode, (d.cfg == CFG_SMALL && !conv_thin_ok(d, ks, 1)) ? nullptr : dp);
+        wrote(srcnode, d.bm_ok ? dp : nullptr);
     }
 
     // the weight gradient of a conv, on the weight-gradient stream: dy is not written again in this step.  Returns its step.
@@ -645,7 +648,8 @@ struct TB {   // train plan builder
             return BnBwd{dy, coef, !affine};
         };
         const LastWriter last = zn.last;
-        ConvArgs *lc = last.kind == LastWriter::DGRAD_CONV ? last.conv : nullptr;
+        ConvPlan *lp = last.kind == LastWriter::DGRAD_CONV ? last.conv : nullptr;
+        ConvArgs *lc = lp ? &lp->a : nullptr;
         // MONOCON_HIP_BM_EPILOGUE: 0 = never take over the reductions in the data gradient's epilogue (always the reduction
         // pass), N > 1 = only for maps of at most N pixels per image
         if (sw.bm_epilogue == 0 || (sw.bm_epilogue > 1 && r.y.H * r.y.W > sw.bm_epilogue)) lc = nullptr;
@@ -655,18 +659,23 @@ struct TB {   // train plan builder
         if (lc && lc->out == zn.g && lc->Cout == C && lc->out_ld == C && lc->Hout == r.y.H && lc->Wout == r.y.W && !lc->stats) {
             // the gradient of this map was completed by a data-gradient conv: its epilogue masks it and emits the
             // (sum d, sum d*y) partials per 4x8 patch -- no reduction pass, and the affine pass needs no mask
-            const int ppi = conv_chunks_per_image(lc->cfg, r.y.H, r.y.W), nbp = B * ppi, cstride = lc->CoutP;   // per 4x8 patch / per row
+            const int ppi = lp->stat_rows, nbp = B * ppi, cstride = lc->CoutP;   // per 4x8 patch / per row
             float *partial = alloc((size_t)nbp * cstride * 2);
             lc->stats = partial;
             lc->bm_y = yp; lc->bm_z = zp; lc->bm_a = fa; lc->bm_b = fb; lc->bm_relu = relu;
             lc->bm_zbits = relu == 1 ? r.zbits : nullptr;
-            if (sw.wres_bwd >= 1 && !(lc->cfg & (CFG_SMALL | CFG_WS)) && conv_wres_ok(*lc, 3, 1)) lc->cfg |= CFG_WRES;      // (see emit_dgrad)
+            // (see emit_dgrad) the twin takes the weight-resident kernel where it is eligible
+            const bool try_wres = sw.wres_bwd >= 1 && !(lc->cfg & (CFG_SMALL | CFG_WS | CFG_WRES));
+            if (try_wres) lc->cfg |= CFG_WRES;
+            conv_plan(*lp);
+            if (try_wres && lp->kernel != CONV_WRES) { lc->cfg &= ~CFG_WRES; conv_plan(*lp); }
+            if (!lp->ok && ts->ok) { ts->ok = false; h->err = "train plan: no conv kernel carries the backward-statistics epilogue of " + bn; }
             if (sw.plan_debug)
                 fprintf(stderr, "[plan]   twin of %-36s cfg %3d  K %4d  Cout %3d  %dx%d  res %d  nsrc %d srcC %d wres %d\n", bn.c_str(), lc->cfg,
                         lc->Cin, lc->Cout, lc->Hout, lc->Wout, lc->res != nullptr, lc->nsrc, lc->src[0].C, (lc->cfg & CFG_WRES) != 0);
             const bool skip_affine = caller_forms_dy && !gres;
             // the epilogue then also leaves max |d| (for the consumer's operand scale); only the coefficients are computed here
-            if (skip_affine) lc->amax_out = dymax;
+            if (skip_affine) lc->amax_out = dymax;      // (no part of the kernel choice)
             return step(partial, nbp, cstride, false, !skip_affine);
         }
         // the gradient of this map was completed by a max-pool backward over a LAZY map (it holds y, forms z for its window
@@ -725,14 +734,14 @@ struct TB {   // train plan builder
             gp.d_att_g[hd] = G(an + ".attn_weights.attention.1.weight", A);
             gp.d_att_b[hd] = G(an + ".attn_weights.attention.1.bias", A);
         }
-        ConvArgs c3{};
+        ConvPlan c3{};
         at.chunks = mc_head_conv_args(h, mem, ts->nodes[feat].t, xh.p, c3);
-        if (conv_any_lazy(c3) && (!ts->nodes[feat].t.lrelu || !conv_lazy_capable(c3, 3, 1))) {
+        if (conv_any_lazy(c3.a) && (!ts->nodes[feat].t.lrelu || !c3.lazy_ok)) {
             materialise(feat);
             conv_fwd_args(c3, h->head3, {&ts->nodes[feat].t}, h->prec);
         }
         at.stat_ld = h->head3.coutp;
-        at.stats = c3.stats; at.B = B; at.HW = HW;
+        at.stats = c3.a.stats; at.B = B; at.HW = HW;
         at.stats64 = reinterpret_cast<double *>(alloc((size_t)B * at.stat_ld * 4));   // [B][stat_ld][2] doubles
         at.sv_inst = alloc((size_t)B * CP * 3); at.mu_r = alloc((size_t)CP * 2); at.bn10 = alloc(NUM_HEADS * NUM_AFFINE * 2);
         at.that = alloc((size_t)B * NUM_HEADS * NUM_AFFINE); at.yatt = alloc((size_t)B * NUM_HEADS * NUM_AFFINE);
@@ -745,7 +754,7 @@ struct TB {   // train plan builder
         ha.B = B; ha.HW = HW; ha.z_out = nullptr;
         for (int i = 0; i < 10; ++i) ha.pred_c[i] = PRED_CH[i];     // the prediction pointers are per call (ts->preds)
         // one closure per kernel family so that mc_profile_train attributes the durations correctly
-        ts->fwd.push_back([=](mc_handle *hh, hipStream_t st) { HIPCHK(hh, launch_conv(c3, 3, 1, st)); return 0; });
+        ts->fwd.push_back([=](mc_handle *hh, hipStream_t st) { HIPCHK(hh, launch_conv(c3, st)); return 0; });
         ts->fwd.push_back([=, ts = ts, at = at](mc_handle *hh, hipStream_t st) {
             HIPCHK(hh, launch_attn_train_fwd(at, st));
             HeadApplyArgs a2 = ha;

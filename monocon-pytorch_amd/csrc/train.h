@@ -91,12 +91,13 @@ inline PackJobDesc pack_job_dgrad(const float *w, int Cout, int CinTotal, int k,
 }
 // The launch of one data-gradient panel: a stride-1 conv over dY (B, Hd, Wd, Cd channels, max-|dY| slot dy_amax) with the
 // panel of job `p` in precision mode prec, into g, the NHWC gradient (Hs x Ws) of the panel's source -- dense for the
-// stride-1 panel, every second pixel from (py, px) for a parity class; accumulate: on top of what g holds.  Fills d (shape
-// id and epilogue extras stay the caller's) and returns the window code to hand launch_conv() as ks, with stride 1.
-inline int dgrad_conv_args(ConvArgs &d, const PackJobDesc &p, int prec, const float *dy, const unsigned *dy_amax, int B, int Hd,
-                           int Wd, int Cd, float *g, int Hs, int Ws, bool accumulate) {
+// stride-1 panel, every second pixel from (py, px) for a parity class; accumulate: on top of what g holds.  Fills d, window
+// code included, and plans it (conv_plan); the shape id and epilogue extras stay the caller's, who plans again after setting them.
+inline void dgrad_conv_args(ConvPlan &dp, const PackJobDesc &p, int prec, const float *dy, const unsigned *dy_amax, int B, int Hd,
+                            int Wd, int Cd, float *g, int Hs, int Ws, bool accumulate) {
     const int ld = p.Cin, py = p.cls >> 1, px = p.cls & 1;
-    d = ConvArgs{};
+    dp = ConvPlan{};
+    ConvArgs &d = dp.a;
     d.nsrc = 1; d.src[0].p = dy; d.src[0].C = Cd;
     d.B = B; d.Hin = Hd; d.Win = Wd; d.Hout = Hd; d.Wout = Wd;
     d.Cin = Cd; d.Cout = ld; d.CoutP = p.CsP; d.wpk = p.dst32;
@@ -108,9 +109,10 @@ inline int dgrad_conv_args(ConvArgs &d, const PackJobDesc &p, int prec, const fl
         d.o_px = 2 * ld; d.o_row = 2 * Ws * ld; d.o_img = Hs * Ws * ld;
     }
     if (accumulate) { d.res = d.out; d.res_ld = ld; d.r_px = d.o_px; d.r_row = d.o_row; d.r_img = d.o_img; }
-    if (p.cls < 0) return p.k;
     const int code = (1 + py) * 10 + (1 + px);      // window KH x KW as KH * 10 + KW; 1 x 1 is the plain 1x1 conv
-    return code == 11 ? 1 : code;
+    dp.ks = p.cls < 0 ? p.k : (code == 11 ? 1 : code);
+    dp.stride = 1;
+    conv_plan(dp);
 }
 struct PackBatch {
     std::vector<PackJobDesc> jobs;
