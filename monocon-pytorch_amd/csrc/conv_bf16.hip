@@ -44,17 +44,6 @@
 
 namespace mc {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-
-// element type / vectors / MFMA of a split mode: SPL 1, 3 = bf16 pieces, SPL 2 = fp16 pieces
-template <int SPL> struct Piece { typedef __bf16 T; typedef bf16x8 V8; typedef bf16x4 V4; };
-template <> struct Piece<2> { typedef _Float16 T; typedef f16x8 V8; typedef f16x4 V4; };
-__device__ __forceinline__ f32x16 mfma_k16(bf16x8 a, bf16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ f32x16 mfma_k16(f16x8 a, f16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-
 template <int KS, int S, int WM, int WN, int WTM, int WTN, int SPL>
 struct ConvCfgB16 {
     static constexpr int CK = 32;

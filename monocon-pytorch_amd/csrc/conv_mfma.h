@@ -33,8 +33,8 @@
 // variants are bit-identical across workgroup shapes.
 // This header is what the family shares: the contract (ConvArgs, ConvPlan, the shape ids and their table CONV_SHAPES, the
 // prototypes), the host-side visitors and the one dynamic-LDS launcher (with_conv_shape, with_conv_window,
-// launch_dyn_lds), and the device helpers every kernel file uses (buffer access, max-|x| slots, xcd_order, conv_wg,
-// conv_epilogue).  No kernel is defined here.
+// launch_dyn_lds), and the device helpers every kernel file uses (the 16-bit vector types, Piece / mfma_k16, split_pair, buffer
+// access, max-|x| slots, xcd_order, conv_wg, conv_epilogue).  No kernel is defined here.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -46,6 +46,33 @@ namespace mc {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+// element type / vectors / MFMA of a split mode (conv_bf16.hip, wgrad_bf16.hip): SPL 1, 3 = bf16 pieces, SPL 2 = fp16 pieces
+template <int SPL> struct Piece { typedef __bf16 T; typedef bf16x8 V8; typedef bf16x4 V4; typedef bf16x2 V2; };
+template <> struct Piece<2> { typedef _Float16 T; typedef f16x8 V8; typedef f16x4 V4; typedef f16x2 V2; };
+__device__ __forceinline__ f32x16 mfma_k16(bf16x8 a, bf16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ f32x16 mfma_k16(f16x8 a, f16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+
+// (x0, x1) * s -> packed fp16 pair of the hi pieces and of the lo pieces, four instructions: v_fma_mix{lo,hi}_f16 computes
+// fma(a, b, c) in fp32 (sources fp32 or one half of a register) and rounds once to fp16 -- hi = f16(x * s), lo = f16(x * s - hi),
+// each ONE rounding of an exact fp32 value: the same bits as the cvt / sub / cvt sequence of conv_bf16_kernel
+// (conv_wres.hip, wgrad_pipe.hip)
+__device__ __forceinline__ void split_pair(float x0, float x1, float s, unsigned &hi, unsigned &lo) {
+    unsigned h, l;
+    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h) : "v"(x0), "v"(s));
+    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h) : "v"(x1), "v"(s));
+    asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(l) : "v"(x0), "v"(s), "v"(h));
+    asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(l) : "v"(x1), "v"(s), "v"(h));
+    hi = h;
+    lo = l;
+}
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a property of (function, DEVICE): a process-wide "already set" flag would
 // launch a second handle's kernels on another GPU without it.  One bit per device in a per-instantiation mask;

@@ -45,7 +45,6 @@
 
 namespace mc {
 
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
 
 struct WresCfg {
@@ -63,18 +62,6 @@ struct WresCfg {
     static constexpr int KDUP = NT * NIT - TOTAL;        // ... threads beyond duplicate an earlier item of their quad (128)
     static_assert(KDUP % C4 == 0 && KDUP <= TOTAL, "duplicate items keep the thread's channel quad");
 };
-
-// (x0, x1) * s -> packed fp16 pair of the hi pieces and of the lo pieces: hi = f16(x * s), lo = f16(x * s - hi), each ONE
-// rounding of an exact fp32 value -- the same bits as the cvt / sub / cvt sequence of conv_bf16_kernel
-__device__ __forceinline__ void wres_split_pair(float x0, float x1, float s, unsigned &hi, unsigned &lo) {
-    unsigned h, l;
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h) : "v"(x0), "v"(s));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h) : "v"(x1), "v"(s));
-    asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(l) : "v"(x0), "v"(s), "v"(h));
-    asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(l) : "v"(x1), "v"(s), "v"(h));
-    hi = h;
-    lo = l;
-}
 
 // Template flags select ONE straight-line epilogue: RES residual (or the gradient accumulated so far), STATS per-patch
 // (sum, sum of squares) partials of a train-mode forward, BM backward-statistics mode (ConvArgs::bm_y; always with
@@ -112,14 +99,14 @@ __global__ __launch_bounds__(256, 1) void conv_wres_kernel(const ConvArgs a, con
     const int w_plane = 9 * a.Cin * a.CoutP * 2;          // bytes of one piece plane of the panel
     const __amdgpu_buffer_rsrc_t r_w = make_rsrc(a.wpk16, (unsigned)(2 * w_plane));
     const int w_lane = (g * a.CoutP + n0 + wn * 32 + li) * 16;
-    h16x8 breg[36][2];
+    f16x8 breg[36][2];
 #pragma unroll
     for (int s = 0; s < 36; ++s) {
         const int kc = (s / 18) * 32, tap = (s % 18) / 2, m = s % 2;
         const int soff = (tap * Cin8 + ((kc + m * 16) >> 3)) * a.CoutP * 16;
 #pragma unroll
         for (int q = 0; q < 2; ++q)
-            breg[s][q] = __builtin_bit_cast(h16x8, __builtin_amdgcn_raw_buffer_load_b128(r_w, w_lane, soff + q * w_plane, 0));
+            breg[s][q] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(r_w, w_lane, soff + q * w_plane, 0));
     }
 
     // ---- the epilogue's per-lane constants (conv_epilogue: column n = lane & 31 of the wave's tile, rows = pixels)
@@ -201,16 +188,16 @@ __global__ __launch_bounds__(256, 1) void conv_wres_kernel(const ConvArgs a, con
         if constexpr (EXP & 2) asm volatile("" ::"v"(pv[i]));
         else if constexpr (LZ) {
             lz_cap = f_voff[i] != BUF_OOB ? __builtin_inff() : 0.f;
-            wres_split_pair(lazy_act(pv[i][0], lzA[0], lzB[0], lz_cap), lazy_act(pv[i][1], lzA[1], lzB[1], lz_cap), 1.f, st_h01, st_l01);
-        } else wres_split_pair(pv[i][0], pv[i][1], a_scale, st_h01, st_l01);
+            split_pair(lazy_act(pv[i][0], lzA[0], lzB[0], lz_cap), lazy_act(pv[i][1], lzA[1], lzB[1], lz_cap), 1.f, st_h01, st_l01);
+        } else split_pair(pv[i][0], pv[i][1], a_scale, st_h01, st_l01);
     };
     auto stage_b = [&](int i, int buf) {
         if constexpr (EXP & 2) return;
         unsigned h23, l23;
         if constexpr (LZ)
-            wres_split_pair(lazy_act(pv[i][2], lzA[2], lzB[2], lz_cap), lazy_act(pv[i][3], lzA[3], lzB[3], lz_cap), 1.f, h23, l23);
+            split_pair(lazy_act(pv[i][2], lzA[2], lzB[2], lz_cap), lazy_act(pv[i][3], lzA[3], lzB[3], lz_cap), 1.f, h23, l23);
         else
-        wres_split_pair(pv[i][2], pv[i][3], a_scale, h23, l23);
+        split_pair(pv[i][2], pv[i][3], a_scale, h23, l23);
         unsigned char *dst = lds_raw + buf * TILE + sdst[i];
         u32x2_t hv, lv;
         hv[0] = st_h01; hv[1] = h23; lv[0] = st_l01; lv[1] = l23;
@@ -354,19 +341,19 @@ __global__ __launch_bounds__(256, 1) void conv_wres_kernel(const ConvArgs a, con
         constexpr bool EPI = decltype(epi_c)::value && !(EXP & 8);
         const int cur = t & 1, nxt = cur ^ 1;
         const unsigned char *abase = lds_raw + cur * TILE + a_off;
-        auto load_a = [&](h16x8(&dst)[2], int s) {
+        auto load_a = [&](f16x8(&dst)[2], int s) {
             const int c = s / 18, tap = (s % 18) / 2, m = s % 2;
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
                 if constexpr (EXP & 16) asm volatile("" : "+v"(dst[q]));
-                else dst[q] = *reinterpret_cast<const h16x8 *>(abase + q * PIECE + (4 * c + 2 * m) * CPL + ((tap / 3) * RS + tap % 3) * 16);
+                else dst[q] = *reinterpret_cast<const f16x8 *>(abase + q * PIECE + (4 * c + 2 * m) * CPL + ((tap / 3) * RS + tap % 3) * 16);
             }
         };
 #pragma unroll
         for (int r = 0; r < 16; ++r) { acc[r] = 0.f; accm[r] = 0.f; }
         // fragments are requested TWO K-steps ahead (ring of three): one step -- 96 cycles of matrix work -- does not cover
         // an LDS round trip when the wave is alone on its SIMD
-        h16x8 afr[3][2];
+        f16x8 afr[3][2];
         load_a(afr[0], 0);
         load_a(afr[1], 1);
         constexpr int S0 = 20;         // first staging step
@@ -374,7 +361,7 @@ __global__ __launch_bounds__(256, 1) void conv_wres_kernel(const ConvArgs a, con
 #pragma unroll
         for (int s = 0; s < 36; ++s) {
             if (s + 2 < 36) load_a(afr[(s + 2) % 3], s + 2);
-            const h16x8 ah = afr[s % 3][0], al = afr[s % 3][1];
+            const f16x8 ah = afr[s % 3][0], al = afr[s % 3][1];
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (EXP & 1) asm volatile("" : "+v"(accm) : "v"(al), "v"(breg[s][0]));
             else accm = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, breg[s][0], accm, 0, 0, 0);      // l * h

@@ -6,10 +6,8 @@
 // supplies 8 consecutive k from one 16-byte register group -- so both operands must sit in LDS
 // channel-major, 8 pixels of one row contiguous: the staging transposes.
 //   * A[n][k]: dYt[n][patch row][8 px] bf16.  One ds_read_b128 = row 2q+g of channel n = 8 of the 16 k.
-//   * B[k][c]: Xt[c][halo row][16 px] bf16 (10 used).  For tap column s the 8 pixels x+s..x+s+7 start at a
-//     2-byte offset, which LDS cannot serve in one aligned read; instead a lane reads pixels 0..7 (b128) and
-//     8..9 (b32) once per halo row and builds the three operands in registers: s = 0 as read, s = 2 is the
-//     same registers shifted by one dword (free), s = 1 is four v_alignbit.
+//   * B[k][c]: Xt[c][halo row][16 px] bf16 (10 used); a lane reads pixels 0..7 (b128) and 8..9 once per halo row and builds
+//     the operands of the three tap columns in registers (wg_taps).
 //   * staging: a thread loads the float4 (4 channels) of TWO horizontally adjacent pixels, rounds to bf16
 //     (RNE) and writes one packed dword per channel -- the transpose costs ds_write_b32, not ds_write_b16.
 //     Offsets, zero fill and the register prefetch across the MFMA phase are as in wgrad_mfma_kernel.
@@ -19,64 +17,21 @@
 //     their tensor's max |x| dictates (WgradArgs::amax_dy / amax_x), staged as two fp16 pieces each, three partial
 //     products per tap; the partial sums leave the kernel multiplied by the exact inverse of both scales.
 // Accumulation, split-K partials and the deterministic reduce stay fp32 (wgrad_reduce_kernel).
-// Stride-2 3x3 layers (round 3): template parameter S = 2, see WgB16Cfg.  The 16-channel layers keep their fp32 kernel.
-#include "conv_mfma.h"
-#include "train.h"
+// Stride-2 3x3 layers (round 3): template parameter S = 2, see WgLds.  The 16-channel layers keep their fp32 kernel.
+// The LDS image, the in-row test of the loads and the MFMAs of a halo row with their taps are shared with wgrad_pipe_kernel:
+// wgrad_tile.h.
+#include "wgrad_tile.h"
 
 namespace mc {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-template <int SPL> struct WPiece { typedef __bf16 T; typedef bf16x8 V8; typedef bf16x2 V2; };
-template <> struct WPiece<2> { typedef _Float16 T; typedef f16x8 V8; typedef f16x2 V2; };
-__device__ __forceinline__ f32x16 wmfma_k16(bf16x8 a, bf16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ f32x16 wmfma_k16(f16x8 a, f16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-
 template <int KS, int S, int WN, int WC, int SPL>
-struct WgB16Cfg {
-    static_assert(S == 1 || (S == 2 && KS == 3), "stride 2: 3x3 only");
+struct WgB16Cfg : WgLds<KS, S> {
     static constexpr int PB = SPL == 1 ? 2 : 1;                 // patches per staged group (WgradArgs::pb)
     static constexpr int NB = 32 * WN, CB = 32 * WC, NT = 64 * WN * WC;
-    static constexpr int PAD = KS / 2;
-    // stride 1: halo tile 6 x 10 (3x3) or 4 x 8 (1x1).  stride 2: the 4 x 8 output patch reads input rows 2y-1 .. 2y+7 and
-    // columns 2x-1 .. 2x+15; a staged row holds the ODD columns (2x-1+2j, j = 0..8, 16 slots) followed by the EVEN ones
-    // (2x+2j, j = 0..7), so that the 8 pixels a tap column needs are again 8 consecutive slots: tap 0 = odd slots 0..7,
-    // tap 1 = even slots 0..7, tap 2 = odd slots 1..8
-    static constexpr int IH = S == 2 ? 9 : 3 + KS, IW = 7 + KS;
-    static constexpr int XROW = S == 2 ? 48 : (KS == 3 ? 32 : 16);   // bytes per staged halo row
-    // Bytes per channel row.  The staging writes of a wave go to 16 channel groups x 4 pixel pairs: with 16-byte aligned
-    // rows the 4-channel stride is a multiple of 16 banks whatever the padding, i.e. 4 distinct banks for 16 lanes (a
-    // 4-way conflict on every ds_write_b32; PMC: SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE = 0.75).  Every group of 16
-    // channels is therefore skewed by another 16 bytes (lds_skew): the 16 channel groups land on 16 distinct multiples
-    // of 4 banks and the pixel pairs fill the gaps -- conflict-free writes; the fragment reads (8 lanes = 8 consecutive
-    // channels, same skew) keep their disjoint banks.  Rows grow by the largest skew (48 bytes).
-    // (stride 2: 9 * 48 + 64 = 496 = 31 * 16 -- an odd number of 16-byte windows per channel keeps the fragment reads of 16
-    //  consecutive channels on 16 distinct windows, as 15 does for stride 1)
-    static constexpr int XCH = IH * XROW + (S == 2 ? 64 : 48);   // 240 (3x3) / 112 (1x1) / 496 (3x3 stride 2)
-    static constexpr int DCH = 4 * 16 + 48;                     // bytes per dY channel: 112
-    static constexpr int X_PLANE = PB * CB * XCH, D_PLANE = PB * NB * DCH;   // one bf16 piece of each tile
+    static constexpr int X_PLANE = PB * CB * WgLds<KS, S>::XCH, D_PLANE = PB * NB * WgLds<KS, S>::DCH;   // one bf16 piece of each tile
     static constexpr int X_BYTES = SPL * X_PLANE, D_BYTES = SPL * D_PLANE;
     static constexpr size_t LDS_BYTES = X_BYTES + D_BYTES;
 };
-
-__device__ __forceinline__ int lds_skew(int channel) { return ((channel >> 4) & 3) * 16; }
-// Which channel of its wave's 32 a lane reads (MFMA row / column li <-> channel lane_chan(li), an involution).  The LDS
-// serves a ds_read_b128 in the lane groups {0-3, 12-15, 20-27} and {4-11, 16-19, 28-31} (+32): with the identity mapping
-// a group straddles two 16-channel blocks, whose rows lds_skew() shifts against each other by 16 bytes -- half the 16-byte
-// windows of a group then collide (PMC, rounds 2 / 3: SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE = 0.67).  Swapping lanes
-// 4-11 with 20-27 gives every group the 16 channels of ONE block: window = (7 or 15) * channel + const mod 16, a bijection.
-__device__ __forceinline__ int lane_chan(int li) { return ((li & 15) >= 4 && (li & 15) < 12) ? (li ^ 16) : li; }
-
-__device__ __forceinline__ unsigned pack_bf16x2(float a, float b) {
-    bf16x2 v;
-    v[0] = (__bf16)a;
-    v[1] = (__bf16)b;
-    return __builtin_bit_cast(unsigned, v);
-}
 
 // LZ (SPL == 2): some source of X is a lazy tensor (ConvSrc::la in conv_mfma.h) -- see wgrad_pipe_kernel
 template <int KS, int S, int WN, int WC, int SPL, bool LZ = false>
@@ -88,9 +43,9 @@ template <int KS, int S, int WN, int WC, int SPL, bool LZ = false>
 #endif
 __global__ __launch_bounds__(64 * WN * WC, S == 2 ? MC_WG16_S2_OCC : 2) void wgrad_bf16_kernel(const WgradArgs a) {
     using Cfg = WgB16Cfg<KS, S, WN, WC, SPL>;
-    typedef typename WPiece<SPL>::T pc_t;
-    typedef typename WPiece<SPL>::V8 pc8;
-    typedef typename WPiece<SPL>::V2 pc2;
+    typedef typename Piece<SPL>::T pc_t;
+    typedef typename Piece<SPL>::V8 pc8;
+    typedef typename Piece<SPL>::V2 pc2;
     constexpr int XPL = Cfg::X_PLANE, DPL = Cfg::D_PLANE;
     constexpr int PB = Cfg::PB, NB = Cfg::NB, CB = Cfg::CB, NT = Cfg::NT, PAD = Cfg::PAD;
     constexpr int IH = Cfg::IH, IW = Cfg::IW, XROW = Cfg::XROW, XCH = Cfg::XCH, DCH = Cfg::DCH;
@@ -141,7 +96,6 @@ __global__ __launch_bounds__(64 * WN * WC, S == 2 ? MC_WG16_S2_OCC : 2) void wgr
     constexpr int NC4 = NB / 4, DP = 4 * 4 * NC4, NID = (DP + NT - 1) / NT;
     static_assert(NT % XC4 == 0 && NT % NC4 == 0 && IW % 2 == 0, "static channel group per thread");
     constexpr int DEAD = -(1 << 24);
-    constexpr int XSTEP = S;                 // the two pixels of a staged pair are S columns apart in the image
     const int xc4 = tid % XC4, dn4 = tid % NC4;
     const bool xc_ok = cs0 + xc4 * 4 < Cs && c0 + xc4 * 4 < a.Cin;
     const bool dn_ok = n0 + dn4 * 4 + 3 < a.dy_ld;
@@ -207,15 +161,12 @@ __global__ __launch_bounds__(64 * WN * WC, S == 2 ? MC_WG16_S2_OCC : 2) void wgr
         const int oy = prow * 4, ox = valid ? (pp - prow * a.ppr) * 8 : DEAD;
         const int xb = (oy * S * a.Win + ox * S) * Cs * 4;
         const int db = (oy * a.Wout + ox) * a.dy_ld * 4;
-        // (one UNSIGNED compare per pixel: with `xx >= 0 && xx < W` hipcc branches on the shared half of the two conditions
-        //  and, since both arms load into the same registers, puts s_waitcnt vmcnt(0) between them -- a full memory latency
-        //  in front of the MFMAs of every group.  Dead items carry a column far outside either way.)
         if constexpr (LZ) okm[slot][p] = 0u;
 #pragma unroll
         for (int i = 0; i < NIX; ++i) {
             const int xx = ox * S + x_ix[i];
-            const bool in0 = (unsigned)xx < (unsigned)a.Win, in1 = (unsigned)(xx + XSTEP) < (unsigned)a.Win;
-            const int vo0 = in0 ? xb + x_stat[i] : BUF_OOB, vo1 = in1 ? xb + x_stat[i] + XSTEP * Cs * 4 : BUF_OOB;
+            const bool in0 = wg_in_row(xx, a.Win), in1 = wg_in_row(xx + S, a.Win);
+            const int vo0 = in0 ? xb + x_stat[i] : BUF_OOB, vo1 = in1 ? xb + x_stat[i] + S * Cs * 4 : BUF_OOB;
             xv[slot][p][i][0] = buf_load4(r_x, vo0, 0);
             xv[slot][p][i][1] = buf_load4(r_x, vo1, 0);
             // (the column is inside: the offset is inside the image's bytes <=> the row is)
@@ -224,7 +175,7 @@ __global__ __launch_bounds__(64 * WN * WC, S == 2 ? MC_WG16_S2_OCC : 2) void wgr
 #pragma unroll
         for (int i = 0; i < NID; ++i) {
             const int xx = ox + d_mx[i];
-            const bool in0 = (unsigned)xx < (unsigned)a.Wout, in1 = (unsigned)(xx + 1) < (unsigned)a.Wout;
+            const bool in0 = wg_in_row(xx, a.Wout), in1 = wg_in_row(xx + 1, a.Wout);
             dv[slot][p][i][0] = buf_load4(r_d, in0 ? db + d_stat[i] : BUF_OOB, 0);
             dv[slot][p][i][1] = buf_load4(r_d, in1 ? db + d_stat[i] + a.dy_ld * 4 : BUF_OOB, 0);
         }
@@ -295,10 +246,6 @@ __global__ __launch_bounds__(64 * WN * WC, S == 2 ? MC_WG16_S2_OCC : 2) void wgr
 #pragma unroll
             for (int p = 0; p < PB; ++p) fetch(gi + PD, p, d);
         }
-        // partial products (piece of dY, piece of X), smallest first; mode 1: the single (0, 0)
-        constexpr int NP = SPL == 1 ? 1 : (SPL == 2 ? 3 : 6);
-        constexpr int PA[6] = {SPL == 2 ? 1 : 0, SPL == 2 ? 0 : 2, SPL == 2 ? 0 : 1, 0, 1, 0};
-        constexpr int PX[6] = {SPL == 2 ? 0 : 2, SPL == 2 ? 1 : 0, SPL == 2 ? 0 : 1, 1, 0, 0};
 #pragma unroll
         for (int p = 0; p < PB; ++p)
 #pragma unroll
@@ -312,39 +259,16 @@ __global__ __launch_bounds__(64 * WN * WC, S == 2 ? MC_WG16_S2_OCC : 2) void wgr
                     const unsigned char *row = b_base + p * CB * XCH + (2 * q * S + r) * XROW;
                     u32x4 b0[SPL], b1[SPL], b2[SPL];     // the three tap columns of every piece of X
 #pragma unroll
-                    for (int z = 0; z < SPL; ++z) {
-                        const u32x4 lo = *reinterpret_cast<const u32x4 *>(row + z * XPL);
-                        b0[z] = lo;
-                        if (KS == 3) {
-                            // pixels 8, 9 of the row: a second 16-byte read (conflict-free, 4 LDS cycles) rather than a
-                            // ds_read_b32, whose 32-lane groups meet 4-way on channel rows that are multiples of 16 bytes
-                            // (the empty asm keeps the compiler from narrowing it back to the one dword that is used)
-                            u32x4 hi4 = *reinterpret_cast<const u32x4 *>(row + z * XPL + 16);
-                            asm volatile("" : "+v"(hi4));
-                            const unsigned hi = hi4[0];
-                            u32x4 sh;                        // slots 1..8 of the plane `lo` starts
-                            sh[0] = __builtin_amdgcn_alignbit(lo[1], lo[0], 16);
-                            sh[1] = __builtin_amdgcn_alignbit(lo[2], lo[1], 16);
-                            sh[2] = __builtin_amdgcn_alignbit(lo[3], lo[2], 16);
-                            sh[3] = __builtin_amdgcn_alignbit(hi, lo[3], 16);
-                            if (S == 2) {                    // odd columns: taps 0 and 2; even columns: tap 1
-                                b1[z] = *reinterpret_cast<const u32x4 *>(row + z * XPL + 32);
-                                b2[z] = sh;
-                            } else {
-                                b1[z] = sh;
-                                b2[z][0] = lo[1]; b2[z][1] = lo[2]; b2[z][2] = lo[3]; b2[z][3] = hi;
-                            }
-                        }
-                    }
+                    for (int z = 0; z < SPL; ++z) wg_taps<KS, S>(row + z * XPL, b0[z], b1[z], b2[z]);
 #pragma unroll
-                    for (int pp = 0; pp < NP; ++pp) {
-                        const int za = SPL == 1 ? 0 : PA[pp], zx = SPL == 1 ? 0 : PX[pp];
+                    for (int pp = 0; pp < WgProducts<SPL>::NP; ++pp) {
+                        const int za = SPL == 1 ? 0 : WgProducts<SPL>::PA[pp], zx = SPL == 1 ? 0 : WgProducts<SPL>::PX[pp];
                         if (KS == 1) {
-                            acc[0] = wmfma_k16(av[za], __builtin_bit_cast(pc8, b0[zx]), acc[0]);
+                            acc[0] = mfma_k16(av[za], __builtin_bit_cast(pc8, b0[zx]), acc[0]);
                         } else {
-                            acc[r * 3 + 0] = wmfma_k16(av[za], __builtin_bit_cast(pc8, b0[zx]), acc[r * 3 + 0]);
-                            acc[r * 3 + 1] = wmfma_k16(av[za], __builtin_bit_cast(pc8, b1[zx]), acc[r * 3 + 1]);
-                            acc[r * 3 + 2] = wmfma_k16(av[za], __builtin_bit_cast(pc8, b2[zx]), acc[r * 3 + 2]);
+                            acc[r * 3 + 0] = mfma_k16(av[za], __builtin_bit_cast(pc8, b0[zx]), acc[r * 3 + 0]);
+                            acc[r * 3 + 1] = mfma_k16(av[za], __builtin_bit_cast(pc8, b1[zx]), acc[r * 3 + 1]);
+                            acc[r * 3 + 2] = mfma_k16(av[za], __builtin_bit_cast(pc8, b2[zx]), acc[r * 3 + 2]);
                         }
                     }
                 }

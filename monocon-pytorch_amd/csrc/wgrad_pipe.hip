@@ -10,49 +10,28 @@
 //   iteration g:  issue loads(g + 2) -> register set g & 1
 //                 MFMAs(g), fragment reads from buffer g & 1; convert + ds_write of register set (g + 1) & 1 -> buffer (g + 1) & 1
 //                 s_waitcnt lgkmcnt(0); s_barrier          (raw: hipcc's __syncthreads would also drain the loads in flight)
-// Same operand preparation, LDS image (channel-major, 8 pixels contiguous, skewed rows: conflict-free writes and reads),
-// tap construction (one aligned read per halo row, the three column taps built in registers) and accumulation order per
-// split-K slice as wgrad_bf16_kernel -- the same partial sums; what differs is the split-K slicing (WgradArgs::ksplit) and,
-// for the 64 x 64 tile, that the two 16-pixel halves of a group go to different waves and slices (WK = 2).
+// Operand preparation, LDS image (channel-major, 8 pixels contiguous, skewed rows: conflict-free writes and reads), tap
+// construction (one aligned read per halo row, the three column taps built in registers) and accumulation order per
+// split-K slice are wgrad_bf16_kernel's (the image, the tap construction and the product order: wgrad_tile.h) -- the partial sums
+// are the same; what differs is the split-K slicing (WgradArgs::ksplit) and, for the 64 x 64 tile, that the two 16-pixel halves of
+// a group go to different waves and slices (WK = 2).
 // Tiles (cout x cin): 128 x 64 (WN 4, WC 2), 64 x 128 (WN 2, WC 4), 64 x 64 (WN 2, WC 2, WK 2); 8 waves each.
 // Reference: what autograd computes for nn.Conv2d.weight.grad (model/backbone/dla.py:21-29, dla_neck.py:56-57).
 #include <cstdlib>
-#include "conv_mfma.h"
-#include "train.h"
+#include "wgrad_tile.h"
 
 namespace mc {
 
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned w32x4 __attribute__((ext_vector_type(4)));
 template <int V> struct WpInt { static constexpr int value = V; };
 
 template <int KS, int WN, int WC, int WK>
-struct WgPipeCfg {
+struct WgPipeCfg : WgLds<KS, 1> {
     static constexpr int NB = 32 * WN, CB = 32 * WC, NW = WN * WC * WK, NT = 64 * NW;
-    static constexpr int PAD = KS / 2, IH = 3 + KS, IW = 7 + KS, T = KS * KS;
-    static constexpr int XROW = KS == 3 ? 32 : 16;               // bytes per staged halo row (10 / 8 pixels)
-    static constexpr int XCH = IH * XROW + 48, DCH = 4 * 16 + 48;   // bytes per channel row (see WgB16Cfg: the skew needs 48)
-    static constexpr int X_PLANE = CB * XCH, D_PLANE = NB * DCH;  // one fp16 piece of each tile
+    static constexpr int X_PLANE = CB * WgLds<KS, 1>::XCH, D_PLANE = NB * WgLds<KS, 1>::DCH;  // one fp16 piece of each tile
     static constexpr int BUF = 2 * (X_PLANE + D_PLANE);
     static constexpr size_t LDS_BYTES = 2 * BUF;
     static_assert(LDS_BYTES <= 160 * 1024, "two tile buffers per CU");
 };
-
-__device__ __forceinline__ int wp_skew(int channel) { return ((channel >> 4) & 3) * 16; }
-// lane <-> channel permutation inside a wave's 32 channels (an involution; see lane_chan() of wgrad_bf16.hip)
-__device__ __forceinline__ int wp_lane_chan(int li) { return ((li & 15) >= 4 && (li & 15) < 12) ? (li ^ 16) : li; }
-
-// (x0, x1) * s -> packed fp16 pair of the hi pieces and of the lo pieces, four instructions: v_fma_mix{lo,hi}_f16 computes
-// fma(a, b, c) in fp32 (sources fp32 or one half of a register) and rounds once to fp16 -- hi = f16(x * s), lo = f16(x * s - hi)
-__device__ __forceinline__ void split_pair(float x0, float x1, float s, unsigned &hi, unsigned &lo) {
-    unsigned h, l;
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h) : "v"(x0), "v"(s));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h) : "v"(x1), "v"(s));
-    asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(l) : "v"(x0), "v"(s), "v"(h));
-    asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(l) : "v"(x1), "v"(s), "v"(h));
-    hi = h;
-    lo = l;
-}
 
 __device__ __forceinline__ void wp_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
@@ -94,6 +73,8 @@ __global__ __launch_bounds__(64 * WN * WC * WK, WN * WC * WK == 4 ? 2 : 1) void 
     const int ex = f16_scale_exp(amax_read(a.amax_x[si])), ed = f16_scale_exp(amax_read(a.amax_dy));
     const float x_scale = exp2i(ex), d_scale = exp2i(ed), omul = exp2i(-ex) * exp2i(-ed);
 
+    // (prologue, plan, loads, lazy values, store: as in wgrad_bf16_kernel -- as shared functions they compile differently,
+    //  profiles/wgrad_tile_symbols.txt)
     // ---- staging plan (as wgrad_bf16_kernel): X item = (halo row, pixel pair, channel quad), dY item = (patch row, pixel
     //      pair, channel quad), channel quad fastest
     constexpr int XC4 = CB / 4, XPAIRS = IW / 2, XP = IH * XPAIRS * XC4, NIX = (XP + NT - 1) / NT;
@@ -117,7 +98,7 @@ __global__ __launch_bounds__(64 * WN * WC * WK, WN * WC * WK == 4 ? 2 : 1) void 
         const int ix = pr * 2 - PAD;
         x_ix[i] = xc_ok ? ix : DEAD;
         x_stat[i] = (((iy - PAD) * a.Win + ix) * Cs + cs0 + xc4 * 4) * 4;
-        x_dst[i] = (xc4 * 4) * XCH + wp_skew(xc4 * 4) + iy * XROW + pr * 4;
+        x_dst[i] = (xc4 * 4) * XCH + lds_skew(xc4 * 4) + iy * XROW + pr * 4;
     }
     int d_stat[NID], d_mx[NID], d_dst[NID];
 #pragma unroll
@@ -126,7 +107,7 @@ __global__ __launch_bounds__(64 * WN * WC * WK, WN * WC * WK == 4 ? 2 : 1) void 
         const int my = item / 4, mx = (item % 4) * 2;
         d_mx[i] = dn_ok ? mx : DEAD;
         d_stat[i] = ((my * a.Wout + mx) * a.dy_ld + n0 + dn4 * 4) * 4;
-        d_dst[i] = 2 * XPL + (dn4 * 4) * DCH + wp_skew(dn4 * 4) + my * 16 + mx * 2;
+        d_dst[i] = 2 * XPL + (dn4 * 4) * DCH + lds_skew(dn4 * 4) + my * 16 + mx * 2;
     }
 
     f32x4 xv[2][NIX][2], dv[2][NID][2];       // two register sets of raw fp32 data: groups g + 1 and g + 2 while g runs
@@ -165,14 +146,11 @@ __global__ __launch_bounds__(64 * WN * WC * WK, WN * WC * WK == 4 ? 2 : 1) void 
         const int oy = prow * 4, ox = (pp - prow * a.ppr) * 8;
         const int xb = (oy * a.Win + ox) * Cs * 4;
         const int db = (oy * a.Wout + ox) * a.dy_ld * 4;
-        // (one UNSIGNED compare per pixel: with `xx >= 0 && xx < W` hipcc branches on the shared half of the two conditions
-        //  and, since both arms load into the same registers, puts s_waitcnt vmcnt(0) between them -- a full memory latency
-        //  in the middle of the MFMA stream, every group)
         if constexpr (LZ) okm[slot] = 0u;
 #pragma unroll
         for (int i = 0; i < NIX; ++i) {
             const int xx = ox + x_ix[i];
-            const bool in0 = (unsigned)xx < (unsigned)a.Win, in1 = (unsigned)(xx + 1) < (unsigned)a.Win;
+            const bool in0 = wg_in_row(xx, a.Win), in1 = wg_in_row(xx + 1, a.Win);
             const int vo0 = in0 ? xb + x_stat[i] : BUF_OOB, vo1 = in1 ? xb + x_stat[i] + Cs * 4 : BUF_OOB;
             xv[slot][i][0] = buf_load4(r_x, vo0, 0);
             xv[slot][i][1] = buf_load4(r_x, vo1, 0);
@@ -182,7 +160,7 @@ __global__ __launch_bounds__(64 * WN * WC * WK, WN * WC * WK == 4 ? 2 : 1) void 
 #pragma unroll
         for (int i = 0; i < NID; ++i) {
             const int xx = ox + d_mx[i];
-            const bool in0 = (unsigned)xx < (unsigned)a.Wout, in1 = (unsigned)(xx + 1) < (unsigned)a.Wout;
+            const bool in0 = wg_in_row(xx, a.Wout), in1 = wg_in_row(xx + 1, a.Wout);
             dv[slot][i][0] = buf_load4(r_d, in0 ? db + d_stat[i] : BUF_OOB, 0);
             dv[slot][i][1] = buf_load4(r_d, in1 ? db + d_stat[i] + a.dy_ld * 4 : BUF_OOB, 0);
         }
@@ -222,46 +200,31 @@ __global__ __launch_bounds__(64 * WN * WC * WK, WN * WC * WK == 4 ? 2 : 1) void 
         put(buf + d_dst[i], DPL, dv[slot][i][0], dv[slot][i][1], DCH, d_scale);
     };
 
-    const int lc = wp_lane_chan(li);
-    const int a_off = 2 * XPL + (wn * 32 + lc) * DCH + wp_skew(wn * 32 + lc) + g * 16;
-    const int b_off = (wc * 32 + lc) * XCH + wp_skew(wc * 32 + lc) + g * XROW;
+    const int lc = lane_chan(li);
+    const int a_off = 2 * XPL + (wn * 32 + lc) * DCH + lds_skew(wn * 32 + lc) + g * 16;
+    const int b_off = (wc * 32 + lc) * XCH + lds_skew(wc * 32 + lc) + g * XROW;
 
     // the MFMAs of one 16-pixel half (patch rows 2q, 2q + 1) of the group in buffer `buf`; `mid` runs after the first tap row
     // has been issued (the staging work of the next group is slotted in there, behind MFMAs that are already queued)
     auto half = [&](const unsigned char *buf, int q, auto &&mid) {
-        h16x8 av[2];
+        f16x8 av[2];
 #pragma unroll
-        for (int z = 0; z < 2; ++z) av[z] = *reinterpret_cast<const h16x8 *>(buf + a_off + z * DPL + (2 * q) * 16);
+        for (int z = 0; z < 2; ++z) av[z] = *reinterpret_cast<const f16x8 *>(buf + a_off + z * DPL + (2 * q) * 16);
 #pragma unroll
         for (int r = 0; r < KS; ++r) {
             const unsigned char *row = buf + b_off + (2 * q + r) * XROW;
-            w32x4 b0[2], b1[2], b2[2];
+            u32x4 b0[2], b1[2], b2[2];
 #pragma unroll
-            for (int z = 0; z < 2; ++z) {
-                const w32x4 lo = *reinterpret_cast<const w32x4 *>(row + z * XPL);
-                b0[z] = lo;
-                if (KS == 3) {
-                    w32x4 hi4 = *reinterpret_cast<const w32x4 *>(row + z * XPL + 16);
-                    asm volatile("" : "+v"(hi4));
-                    const unsigned hi = hi4[0];
-                    b1[z][0] = __builtin_amdgcn_alignbit(lo[1], lo[0], 16);
-                    b1[z][1] = __builtin_amdgcn_alignbit(lo[2], lo[1], 16);
-                    b1[z][2] = __builtin_amdgcn_alignbit(lo[3], lo[2], 16);
-                    b1[z][3] = __builtin_amdgcn_alignbit(hi, lo[3], 16);
-                    b2[z][0] = lo[1]; b2[z][1] = lo[2]; b2[z][2] = lo[3]; b2[z][3] = hi;
-                }
-            }
-            // partial products (piece of dY, piece of X), smallest first: (lo, hi), (hi, lo), (hi, hi)
-            constexpr int PA[3] = {1, 0, 0}, PX[3] = {0, 1, 0};
+            for (int z = 0; z < 2; ++z) wg_taps<KS, 1>(row + z * XPL, b0[z], b1[z], b2[z]);
 #pragma unroll
-            for (int pp = 0; pp < 3; ++pp) {
-                const int za = PA[pp], zx = PX[pp];
+            for (int pp = 0; pp < WgProducts<2>::NP; ++pp) {
+                const int za = WgProducts<2>::PA[pp], zx = WgProducts<2>::PX[pp];
                 if (KS == 1) {
-                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(av[za], __builtin_bit_cast(h16x8, b0[zx]), acc[0], 0, 0, 0);
+                    acc[0] = mfma_k16(av[za], __builtin_bit_cast(f16x8, b0[zx]), acc[0]);
                 } else {
-                    acc[r * 3 + 0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(av[za], __builtin_bit_cast(h16x8, b0[zx]), acc[r * 3 + 0], 0, 0, 0);
-                    acc[r * 3 + 1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(av[za], __builtin_bit_cast(h16x8, b1[zx]), acc[r * 3 + 1], 0, 0, 0);
-                    acc[r * 3 + 2] = __builtin_amdgcn_mfma_f32_32x32x16_f16(av[za], __builtin_bit_cast(h16x8, b2[zx]), acc[r * 3 + 2], 0, 0, 0);
+                    acc[r * 3 + 0] = mfma_k16(av[za], __builtin_bit_cast(f16x8, b0[zx]), acc[r * 3 + 0]);
+                    acc[r * 3 + 1] = mfma_k16(av[za], __builtin_bit_cast(f16x8, b1[zx]), acc[r * 3 + 1]);
+                    acc[r * 3 + 2] = mfma_k16(av[za], __builtin_bit_cast(f16x8, b2[zx]), acc[r * 3 + 2]);
                 }
             }
             if (r == 0) mid();
@@ -316,7 +279,7 @@ __global__ __launch_bounds__(64 * WN * WC * WK, WN * WC * WK == 4 ? 2 : 1) void 
         for (int t = 0; t < T; ++t)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int n = n0 + wn * 32 + wp_lane_chan((r & 3) + 8 * (r >> 2) + 4 * g);
+                const int n = n0 + wn * 32 + lane_chan((r & 3) + 8 * (r >> 2) + 4 * g);
                 if (n < a.Cout) a.partial[(((size_t)slice * T + t) * a.Cout + n) * a.Cin + c] = acc[t][r] * omul;
             }
     }
