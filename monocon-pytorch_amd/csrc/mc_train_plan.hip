@@ -316,25 +316,30 @@ struct TB {   // train plan builder
     float *G(const std::string &name, int64_t numel) { return P(name + "#grad", numel); }
     long long *NBT(const std::string &name) { return static_cast<long long *>(bound(name, 1, MC_I64)); }
 
-    double *fold_scratch(int nb, int C) {
+    // reserved: whether the partial list gets a fold buffer, i.e. partial_fold + the double finalise run (launch_bn_finalize)
+    double *fold_scratch(int nb, int C, bool *reserved = nullptr) {
         const size_t nd = partial_fold_doubles(nb, C);
+        if (reserved) *reserved = nd != 0;
         return nd ? reinterpret_cast<double *>(alloc(nd * 2)) : nullptr;
     }
 
     // ---------------------------------------------------------------- forward pieces
-    void bn_train_ops(const Tensor &y, const float *stats, int nb, int cstride, const std::string &bn, float eps,
+    // returns whether the partials are folded first (fold_scratch)
+    bool bn_train_ops(const Tensor &y, const float *stats, int nb, int cstride, const std::string &bn, float eps,
                       float mom, float *a, float *b, float *mean, float *rstd, const unsigned *ymax = nullptr,
                       unsigned *zmax = nullptr, int zrelu = 1) {
         const int C = y.C;
         float *g = P(bn + ".weight", C), *be = P(bn + ".bias", C), *rm = P(bn + ".running_mean", C), *rv = P(bn + ".running_var", C);
         long long *nbt = NBT(bn + ".num_batches_tracked");
         const double n = (double)y.B * y.H * y.W;
-        double *fold = fold_scratch(nb, C);
+        bool folds = false;
+        double *fold = fold_scratch(nb, C, &folds);
         ts->fwd.push_back([=](mc_handle *hh, hipStream_t st) {
             HIPCHK(hh, launch_bn_finalize(stats, nb, cstride, n, C, rm, g, be, eps, mom, rm, rv, nbt, a, b, mean, rstd, st, fold,
                                           ymax, zmax, zrelu));
             return 0;
         });
+        return folds;
     }
 
     // the max-|x| slots start every forward at zero: their producers only raise them (mode 3; the first step of the forward)
@@ -364,12 +369,13 @@ struct TB {   // train plan builder
 
     // BatchNorm of the raw conv output r.y from its statistics partials, then the activation: lazy (never stored: the node
     // points at y and carries the coefficients; ymax = the slot where the conv left max |y|), or one element-wise pass
-    void bn_act(Rec &r, const float *stats, int nb, int cstride, bool lazy, const unsigned *ymax) {
+    // (returns bn_train_ops' answer)
+    bool bn_act(Rec &r, const float *stats, int nb, int cstride, bool lazy, const unsigned *ymax) {
         const int B = r.y.B, C = r.y.C, res = r.res, rl = r.relu;
         float *ca = alloc(C), *cb = alloc(C);
         r.ca = ca; r.cb = cb;
         r.mean = alloc(C); r.rstd = alloc(C);
-        bn_train_ops(r.y, stats, nb, cstride, r.bn, 1e-5f, 0.1f, ca, cb, r.mean, r.rstd, ymax, lazy ? ts->nodes[r.z].t.amax : nullptr, rl);
+        const bool folds = bn_train_ops(r.y, stats, nb, cstride, r.bn, 1e-5f, 0.1f, ca, cb, r.mean, r.rstd, ymax, lazy ? ts->nodes[r.z].t.amax : nullptr, rl);
         if (lazy) {
             TNode &zn = ts->nodes[r.z];
             zn.t.p = r.y.p; zn.t.la = ca; zn.t.lb = cb; zn.t.lrelu = r.relu;
@@ -392,6 +398,15 @@ struct TB {   // train plan builder
                 return 0;
             });
         }
+        return folds;
+    }
+
+    // MONOCON_HIP_PLAN_DEBUG: which launch leaves a layer's forward statistics partials (the conv kernel's name, or the
+    // stem's), how many rows of them, which bn_finalize build finishes them (folds: bn_act's answer), and what becomes of z
+    void say_forward(const Rec &r, const char *producer, int nb, bool folds, bool lazy) {
+        if (!sw.plan_debug) return;
+        fprintf(stderr, "[plan] forward %-40s node %3d  statistics by %-10s %6d partial rows  finalize %s  z %s\n", r.bn.c_str(), r.z,
+                producer, nb, folds ? "double" : "float", r.dead ? "dead" : (lazy ? "lazy" : "stored"));
     }
 
     // ---- stem (raw conv -> batch stats -> normalise + ReLU)
@@ -425,7 +440,8 @@ struct TB {   // train plan builder
             }
             return 0;
         });
-        bn_act(stem, partial, nb, 16, stem_lazy, stem_lazy ? ymax : nullptr);
+        const bool folds = bn_act(stem, partial, nb, 16, stem_lazy, stem_lazy ? ymax : nullptr);
+        say_forward(stem, fused_stats ? "stem_f16" : "chan_reduce", nb, folds, stem_lazy);
         ts->recs.push_back(stem);
     }
 
@@ -477,7 +493,11 @@ struct TB {   // train plan builder
         a.stat_shift = P(Lr.bn + ".running_mean", Lr.cout);
         conv_plan(cp);
         ts->fwd.push_back([=](mc_handle *hh, hipStream_t st) { HIPCHK(hh, launch_conv(cp, st)); return 0; });
-        bn_act(r, stats, B * chunks, Lr.coutp, lazy, yslot);
+        const bool folds = bn_act(r, stats, B * chunks, Lr.coutp, lazy, yslot);
+        static const char *const KERNEL[] = {"fp32", "fp32_ws", "split", "wres", "row", "row_lazy", "thin16"};      // by ConvKernel
+        static_assert(sizeof(KERNEL) / sizeof(KERNEL[0]) == CONV_THIN16 + 1 && CONV_FP32 == 0 && CONV_WRES == 3 && CONV_ROW == 4,
+                      "one name per ConvKernel, in its order");
+        say_forward(r, KERNEL[cp.kernel], B * chunks, folds, lazy);
         ts->recs.push_back(r);
         return r.z;
     }

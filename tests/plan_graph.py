@@ -1,8 +1,10 @@
-"""The network graph as the tests see it, the stressed state, and the layer-local backward and eval references.
+"""The network graph as the tests see it, the stressed state, and the layer-local backward, forward and eval references.
 
 A plain module (no fixtures): `test_hip_operand_scale.py` (forward, layer by layer), `test_hip_backward_layers.py` (backward,
-layer by layer), `test_backward_reference_cpu.py` (the checker checked against autograd), `test_hip_eval_layers.py` (the eval
-plan, layer by layer) and `test_eval_reference_cpu.py` (that checker checked against the oracle) share it.
+layer by layer), `test_backward_reference_cpu.py` (the checker checked against autograd), `test_hip_forward_layers.py` (the
+train forward with its statistics, layer by layer), `test_forward_reference_cpu.py` (that checker checked against the oracle),
+`test_hip_eval_layers.py` (the eval plan, layer by layer) and `test_eval_reference_cpu.py` (that checker checked against the
+oracle) share it.
 
 The graph mirrors mc_api.hip `build_net` / mc_train_plan.hip: node 0 is the stem's output, every live conv + BatchNorm, every
 2x2 max-pool and every depthwise deconv makes one node, in forward order.
@@ -19,9 +21,11 @@ and nothing is amplified.  The buffers, as `mc_train_debug_node` hands them out 
              skipped and the buffer keeps d = dZ * [z > 0], the masked gradient.  With STEM_FUSE=0, in fp32 / bf16x3, or with
              MONOCON_HIP_BM_EPILOGUE=0 it holds dY.
 """
+import contextlib
 import math
 import os
 import sys
+import tempfile
 
 import torch
 import torch.nn.functional as F
@@ -85,6 +89,7 @@ class PlanGraph:
     pools: (input node, output node); deconvs: (parameter name `neck.ida_i.up_t`, input node, output node);
     steps: all of them in forward order, ("conv", rec) / ("pool", in, out) / ("deconv", name, in, out);
     node_c / node_down: channels and down-scale of every node (node 0: 16 channels at full resolution);
+    dead: (conv name, source node) of the outer `project` convs of the two-level trees: no node, their statistics still tick;
     consumers[n]: who reads node n, in the order the BACKWARD writes their shares into n's gradient (records in reverse
     forward order; within a conv record the residual's share -- written by the BatchNorm backward -- before the data gradients
     of its sources in source order): ("conv", rec, source index, channel offset) / ("res", rec) / ("pool", out) /
@@ -95,6 +100,7 @@ class PlanGraph:
         self.node_c, self.node_down = [16], [1]
         self.feat = -1
         self.levels = []          # the nodes of the backbone's level outputs l0 .. l5
+        self.dead = []            # (conv name, source node) of the outer `project` convs: never consumed, statistics still tick
 
     @property
     def n_nodes(self):
@@ -136,6 +142,7 @@ def plan_graph():
 
     def conv_bn(name, ks, stride, srcs, res, relu, dead=False):
         if dead:
+            G.dead.append((name, srcs[0]))
             return -1
         cout = shapes[name + ".weight"][0][0]
         assert shapes[name + ".weight"][0][1] == sum(G.node_c[s] for s in srcs), name
@@ -221,6 +228,25 @@ def _model(sd, precision):
     m = MonoConDetector(34, pretrained_backbone=False)
     m.load_state_dict(sd, strict=True)
     return m.cuda().train().set_precision(precision)
+
+
+@contextlib.contextmanager
+def stderr_lines():
+    """what the library writes to file descriptor 2 inside the block (the plan's `[plan]` debug lines), as a list of lines
+    filled on exit (capfd is function-scoped; the step fixtures are module-scoped)"""
+    lines = []
+    sys.stderr.flush()
+    keep = os.dup(2)
+    with tempfile.TemporaryFile(mode="w+b") as f:
+        os.dup2(f.fileno(), 2)
+        try:
+            yield lines
+        finally:
+            sys.stderr.flush()
+            os.dup2(keep, 2)
+            os.close(keep)
+            f.seek(0)
+            lines += f.read().decode(errors="replace").splitlines()
 
 
 def _node_dims(m, i):
@@ -434,6 +460,108 @@ def compare_normwise(R, g, grads, stem_holds="dY"):
         out[("dZ", name)] = norm_err(g[o], R.dZ[o].ref)
     out[("stem g", STEM)] = norm_err(g[0], R.dY[0] if stem_holds == "dY" else R.d[0])
     return out
+
+
+# ------------------------------------------------------------------------------------------------ the forward reference
+BN_MOMENTUM = 0.1
+
+
+class ForwardReference:
+    """what `forward_reference` found.
+    layers: [(kind, conv name, node, Triple)] for the stem and every live conv (`feat` included): z in fp64, its magnitude
+      M = |a| conv2d(|x|, |w|) + |b| + |res| (unfloored; Triple.floored() floors it), the float32 yard-stick;
+    pools: [(in, out, max_pool2d(act[in], 2, 2))]; deconvs: [(name, in, out, Triple)];
+    stats[conv name] (dead `project` convs too), per channel unless said: n (a number), K (terms per output), mean, var (biased),
+      shift (the running mean before the step), m0 = mean - shift, e1 = E|y - shift|, e2 = E[(y - shift)^2], a, b, tmax (the
+      operand-split scale T_c), ymag = conv2d(|x|, |w|) (the whole map) and ymag_max, its maximum over the map, node; live
+      layers also dev = |y - mean| and zmag = |a| |y| + |b| (whole maps: the size of a y + b before residual and ReLU);
+    running[bn name]: rm, rv (Triple: the fp64 update, its magnitude sum (1 - m) |old| + m |statistic|, the float32
+      yard-stick's buffer), nbt (num_batches_tracked after the step)"""
+
+    def __init__(self, graph):
+        self.graph = graph
+        self.layers, self.pools, self.deconvs, self.stats, self.running = [], [], [], {}, {}
+
+
+def forward_reference(graph, act, img, sd_before, yardstick=True):
+    """The layer-local train-mode forward of backbone + neck in float64 from the plan's own buffers: `act[n]` is node n as
+    `mc_train_debug_node(which = 0)` hands it out AFTER the forward, `sd_before` the state the forward started from (its
+    running means are also the shift of the kernels' variance sums).  No quantity goes through more than ONE layer:
+
+        conv node    y = conv2d(cat(act[srcs]), W) (the stem: of img), biased batch mean / var over (B, H, W),
+                     a = gamma / sqrt(var + eps), b = beta - mean a, z = a y + b (+ act[res]), clamped at 0 under a ReLU
+        pool node    max_pool2d(act[in], 2, 2), in the precision of act[in]: a maximum rounds nothing
+        deconv node  the depthwise conv_transpose2d of act[in], magnitude from |x|, |w|
+        running      rm' = (1 - m) rm + m mean, rv' = (1 - m) rv + m var n / (n - 1), m = 0.1, for every BatchNorm of
+                     `_plan_convs()`: the dead outer `project` convs read their `bottom` pool node (graph.dead)
+
+    yardstick: the same conv node by torch in float32 from the same float32 buffers -- F.conv2d, then
+    F.batch_norm(training=True) on copies of the running buffers, which are the yard-stick's running buffers."""
+    R = ForwardReference(graph)
+    D, S = torch.float64, torch.float32
+    m = BN_MOMENTUM
+    v = lambda t: t[None, :, None, None]          # noqa: E731
+
+    def conv_bn(rec, xs, live=True):
+        name, srcs, res, relu, o, ks, stride = rec
+        bn = _bn_of(name)
+        w = sd_before[name + ".weight"].to(D)
+        gamma, beta = sd_before[bn + ".weight"].to(D), sd_before[bn + ".bias"].to(D)
+        rm, rv = sd_before[bn + ".running_mean"].to(D), sd_before[bn + ".running_var"].to(D)
+        x = torch.cat([t.to(D) for t in xs], 1)
+        y = F.conv2d(x, w, stride=stride, padding=ks // 2)
+        ymag = F.conv2d(x.abs(), w.abs(), stride=stride, padding=ks // 2)
+        tm, c0 = torch.zeros_like(gamma), 0
+        for t in xs:          # the f16x2 operand-split scale, as bn_backward's tmax
+            tm += float(t.abs().max()) * w[:, c0:c0 + t.shape[1]].abs().sum((1, 2, 3))
+            c0 += t.shape[1]
+        n = y.numel() // y.shape[1]
+        mean = y.mean((0, 2, 3))
+        var = y.var((0, 2, 3), unbiased=False)
+        a = gamma / torch.sqrt(var + EPS)
+        b = beta - mean * a
+        ys = y - v(rm)
+        R.stats[name] = dict(n=n, K=w[0].numel(), mean=mean, var=var, shift=rm, m0=mean - rm, e1=ys.abs().mean((0, 2, 3)),
+                             e2=(ys * ys).mean((0, 2, 3)), a=a, b=b, tmax=tm, ymag=ymag, ymag_max=ymag.amax((0, 2, 3)),
+                             dev=(y - v(mean)).abs() if live else None, zmag=v(a.abs()) * y.abs() + v(b.abs()) if live else None,
+                             node=o if live else None)
+        unb = var * n / (n - 1)
+        run = dict(rm=Triple((1 - m) * rm + m * mean, (1 - m) * rm.abs() + m * mean.abs()),
+                   rv=Triple((1 - m) * rv + m * unb, (1 - m) * rv.abs() + m * unb),
+                   nbt=int(sd_before[bn + ".num_batches_tracked"]) + 1)
+        R.running[bn] = run
+        z32 = None
+        if yardstick:
+            rm32, rv32 = sd_before[bn + ".running_mean"].to(S).clone(), sd_before[bn + ".running_var"].to(S).clone()
+            y32 = F.conv2d(torch.cat([t.to(S) for t in xs], 1), sd_before[name + ".weight"].to(S), stride=stride, padding=ks // 2)
+            z32 = F.batch_norm(y32, rm32, rv32, sd_before[bn + ".weight"].to(S), sd_before[bn + ".bias"].to(S), True, m, EPS)
+            run["rm"].f32, run["rv"].f32 = rm32, rv32
+        if not live:
+            return
+        z = v(a) * y + v(b)
+        M = v(a.abs()) * ymag + v(b.abs())
+        if res >= 0:
+            z, M = z + act[res].to(D), M + act[res].to(D).abs()
+            if yardstick:
+                z32 = z32 + act[res].to(S)
+        if relu:
+            z = z.clamp_min(0)
+            z32 = z32.clamp_min(0) if yardstick else None
+        R.layers.append((layer_kind(ks, stride), name, o, Triple(z, M, z32)))
+
+    conv_bn(STEM_REC, [img])
+    for st in graph.steps:
+        if st[0] == "conv":
+            conv_bn(st[1], [act[s] for s in st[1][1]])
+        elif st[0] == "pool":
+            R.pools.append((st[1], st[2], F.max_pool2d(act[st[1]], 2, 2)))
+        else:
+            _, name, i, o = st
+            R.deconvs.append((name, i, o, Triple(eval_deconv(sd_before, name, act[i], D), eval_deconv(sd_before, name, act[i], D, True),
+                                                 eval_deconv(sd_before, name, act[i], S) if yardstick else None)))
+    for name, src in graph.dead:
+        conv_bn((name, [src], -1, False, -1, 1, 1), [act[src]], live=False)
+    return R
 
 
 # ------------------------------------------------------------------------------------------------ the eval plan

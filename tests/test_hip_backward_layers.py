@@ -34,21 +34,17 @@ Tolerances -- no number is fitted to the code under test (U = 2^-24):
     gamma rstd / n + dy_c through yhat and rstd.
 
 Measured (MI355X, worst over the configs' shapes; conv quantities as HIP / float32 yard-stick, the others as
-measured / bound): see MEASURED below and DESIGN.md 8d.
+measured / bound): see MEASURED below and DESIGN.md 3c ("The backward, layer by layer").
 """
-import contextlib
 import math
-import os
 import re
-import sys
-import tempfile
 import time
 
 import pytest
 import torch
 
 from plan_graph import (STEM, _bn_of, _model, _node_dims, _read_node, backward_reference, layer_kind, norm_err, plan_graph,
-                        stressed_batch, stressed_state_dict)
+                        stderr_lines, stressed_batch, stressed_state_dict)
 
 pytestmark = pytest.mark.gpu
 
@@ -94,25 +90,6 @@ the plain gate): reported in DESIGN.md, not tightened.  The stem dW gate adds co
 
 def _say(line):
     print("\n[backward layers] " + line)
-
-
-@contextlib.contextmanager
-def stderr_lines():
-    """what the library writes to file descriptor 2 inside the block, as a list of lines filled on exit (capfd is
-    function-scoped; the step fixture is module-scoped)"""
-    lines = []
-    sys.stderr.flush()
-    keep = os.dup(2)
-    with tempfile.TemporaryFile(mode="w+b") as f:
-        os.dup2(f.fileno(), 2)
-        try:
-            yield lines
-        finally:
-            sys.stderr.flush()
-            os.dup2(keep, 2)
-            os.close(keep)
-            f.seek(0)
-            lines += f.read().decode(errors="replace").splitlines()
 
 
 class Step:
