@@ -302,6 +302,28 @@ int mc_clip_adamw_step_classes(mc_handle *h, const mc_optim_class *classes, int 
 int mc_clip_bind(mc_handle *h, int n, float *const grads[], const int64_t numel[]);
 int mc_clip_grad_norm(mc_handle *h, double max_norm, double norm_type, float *out_norm, void *stream);
 
+/* Exponential moving average of the weights (timm ModelEmaV2, mmdet's EMA hook, YOLO's ModelEMA; the
+ * reference's loop has none): e += ema_weight * (x - e), ema_weight = 1 - decay of this update, folded
+ * by the caller in double.  Python: solver.ModelEMA, solver.AdamW.set_ema.
+ * mc_optim_bind_ema attaches one average per tensor of the bound optimizer table (n == its size;
+ * entries may be NULL: that tensor has none); mc_optim_bind and mc_optim_bind_classes drop them again.
+ * It fails when no table is bound, when n differs from the table's size and when some ema[i] overlaps
+ * its parameter.  mc_clip_adamw_ema_step_classes is mc_clip_adamw_step_classes whose AdamW pass also
+ * updates the attached averages from the new parameter values while they are in registers: 8 B/param
+ * more, no launch and no second read of the parameters.  ema_weight == 0 or no average attached:
+ * exactly mc_clip_adamw_step_classes, launch for launch.
+ * mc_ema_bind registers n (average, source) pairs in a table of their own, beside the optimizer's
+ * and the clip's -- BatchNorm running statistics, parameters without a gradient, the parameters of a
+ * loop with another optimizer; it fails when some ema[i] overlaps its src[i].  mc_ema_update applies
+ * one update to all of them in one launch, with the arithmetic of the fused pass bit for bit.
+ * ema_weight == 1 copies the source exactly, 0 leaves the average untouched.
+ * ema_weight must lie in [0, 1]: NaN or a value outside fails the call before anything is launched. */
+int mc_optim_bind_ema(mc_handle *h, int n, float *const ema[]);
+int mc_clip_adamw_ema_step_classes(mc_handle *h, const mc_optim_class *classes, int ncls, double max_norm,
+                                   double norm_type, double ema_weight, float *out_norm, void *stream);
+int mc_ema_bind(mc_handle *h, int n, float *const ema[], const float *const src[], const int64_t numel[]);
+int mc_ema_update(mc_handle *h, double ema_weight, void *stream);
+
 /* ---- op-level entry points (unit parity tests; same kernels the forward uses) -------
  * Fused convolution, NHWC fp32: out = act(conv(cat(src...)) * scale + bias + residual).
  * Replaces nn.Conv2d + nn.BatchNorm2d(eval) + ReLU (+ torch.cat, + residual add) of

@@ -32,6 +32,9 @@ _DEFAULTS = {
         "OPTIM": {"LR": 2.25e-4, "WEIGHT_DECAY": 1e-5, "NUM_EPOCHS": 200, "BACKBONE_LR_MULT": 1.0, "NO_DECAY_NORM_BIAS": False},
         "SCHEDULER": {"ENABLE": True},
         "CLIP_GRAD": {"ENABLE": True, "NORM_TYPE": 2.0, "MAX_NORM": 35},
+        # EMA (not in the reference's tree; off = its loop): an exponential moving average of the weights and BatchNorm
+        # statistics, updated inside the fused AdamW step, used by evaluate() and kept in the checkpoints -- solver/model_ema.py
+        "EMA": {"ENABLE": False, "DECAY": 0.9998, "WARMUP": True},
     },
     "PERIOD": {"EVAL_PERIOD": 10, "LOG_PERIOD": 50},
 }

@@ -6,7 +6,8 @@
 // Every kernel is a template whose all-default instantiation (L2 norm; one hyper-parameter set, no amsgrad) is the
 // reference recipe's path: launch_clip_adamw reaches only those, and their arithmetic, chunk walk and partial order are
 // the ones the committed goldens were recorded against.  The other instantiations add the norm kinds of
-// clip_grad_norm_ and torch.optim.AdamW's per-group options.
+// clip_grad_norm_ and torch.optim.AdamW's per-group options, and (EMA) the exponential moving average of the weights that
+// long runs keep for evaluation: formed in the step's own pass, 8 B/param more, no launch and no second read of p.
 #include <stdint.h>
 #include "conv_mfma.h"
 #include "train.h"
@@ -89,29 +90,50 @@ __device__ __forceinline__ void adamw_one(float &p, float g, float &m, float &v,
     p -= hp.step_size * (m / denom);
 }
 
-template <bool AMS>
-__device__ __forceinline__ void adamw_chunk(const OptTensor &t, const OptChunk &ck, float coef, const AdamHyper &hp) {
+// ---- weight average (solver/model_ema.py): the only place it is formed.  w = 1 - decay_t, folded on the host in double.
+// w == 1 (decay 0) is the copy it means: (p - e) + e rounds twice and misses p by an ulp where |e| << |p|.  w is a kernel
+// argument, so the select is on a scalar condition.  (w == 0 never gets here: the entry points launch nothing for it.)
+__device__ __forceinline__ void ema_one(float &e, float p, float w) { e = w == 1.f ? p : fmaf(w, p - e, e); }
+
+// EMA: a chunk whose tensor has an average (t.e, uniform per chunk: a scalar branch) updates it with the new p still in
+// registers -- in the float4 body and in the scalar tail alike.  Whether an element is walked by the body or by the tail
+// never depends on e: the two round p differently (contraction), and attaching an average must not move a bit of the
+// update.  So an e that is not 16-byte aligned like the other pointers (no torch allocation is) is read and written
+// with four dword accesses inside the body.
+template <bool AMS, bool EMA = false>
+__device__ __forceinline__ void adamw_chunk(const OptTensor &t, const OptChunk &ck, float coef, const AdamHyper &hp, float w = 0.f) {
     float *p = t.p + ck.begin, *m = t.m + ck.begin, *v = t.v + ck.begin;
     const float *g = t.g + ck.begin;
     float *x = AMS ? t.vmax + ck.begin : nullptr;
+    float *e = (EMA && t.e) ? t.e + ck.begin : nullptr;
     int i0 = 0;
     if (aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && (!AMS || aligned16(x))) {
         const int n4 = ck.count >> 2;
+        const bool e16 = aligned16(e);
         for (int i = threadIdx.x; i < n4; i += 256) {
             f32x4 p4 = reinterpret_cast<f32x4 *>(p)[i], m4 = reinterpret_cast<f32x4 *>(m)[i], v4 = reinterpret_cast<f32x4 *>(v)[i];
             const f32x4 g4 = reinterpret_cast<const f32x4 *>(g)[i];
-            f32x4 x4 = {0.f, 0.f, 0.f, 0.f};
+            f32x4 x4 = {0.f, 0.f, 0.f, 0.f}, e4 = {0.f, 0.f, 0.f, 0.f};
             if constexpr (AMS) x4 = reinterpret_cast<f32x4 *>(x)[i];
+            if constexpr (EMA) {
+                if (e && e16) e4 = reinterpret_cast<f32x4 *>(e)[i];
+                else if (e) { e4[0] = e[4 * i]; e4[1] = e[4 * i + 1]; e4[2] = e[4 * i + 2]; e4[3] = e[4 * i + 3]; }
+            }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 float pj = p4[j], mj = m4[j], vj = v4[j], xj = x4[j];
                 adamw_one<AMS>(pj, g4[j], mj, vj, xj, coef, hp);
                 p4[j] = pj; m4[j] = mj; v4[j] = vj; x4[j] = xj;
+                if constexpr (EMA) { float ej = e4[j]; ema_one(ej, pj, w); e4[j] = ej; }
             }
             reinterpret_cast<f32x4 *>(p)[i] = p4;
             reinterpret_cast<f32x4 *>(m)[i] = m4;
             reinterpret_cast<f32x4 *>(v)[i] = v4;
             if constexpr (AMS) reinterpret_cast<f32x4 *>(x)[i] = x4;
+            if constexpr (EMA) {
+                if (e && e16) reinterpret_cast<f32x4 *>(e)[i] = e4;
+                else if (e) { e[4 * i] = e4[0]; e[4 * i + 1] = e4[1]; e[4 * i + 2] = e4[2]; e[4 * i + 3] = e4[3]; }
+            }
         }
         i0 = n4 << 2;
     }
@@ -120,6 +142,7 @@ __device__ __forceinline__ void adamw_chunk(const OptTensor &t, const OptChunk &
         if constexpr (AMS) xi = x[i];
         adamw_one<AMS>(p[i], g[i], m[i], v[i], xi, coef, hp);
         if constexpr (AMS) x[i] = xi;
+        if constexpr (EMA) if (e) ema_one(e[i], p[i], w);
     }
 }
 
@@ -130,6 +153,17 @@ __global__ __launch_bounds__(256) void adamw_kernel(const OptTensor *tab, const 
         const OptChunk ck = chunks[c];
         const OptTensor t = tab[ck.tensor];
         adamw_chunk<false>(t, ck, coef, hp);
+    }
+}
+
+// the same walk with the weight average folded in (w > 0 and some bound tensor has one: the launchers choose)
+__global__ __launch_bounds__(256) void adamw_ema_kernel(const OptTensor *tab, const OptChunk *chunks, int nchunks,
+                                                        const float *normcoef, AdamHyper hp, float w) {
+    const float coef = normcoef[1];
+    for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+        const OptChunk ck = chunks[c];
+        const OptTensor t = tab[ck.tensor];
+        adamw_chunk<false, true>(t, ck, coef, hp, w);
     }
 }
 
@@ -149,6 +183,46 @@ __global__ __launch_bounds__(256) void adamw_classes_kernel(const OptTensor *tab
         const float coef = ((tb.maximize >> k) & 1u) ? -coef0 : coef0;
         if (AMSGRAD && ((tb.amsgrad >> k) & 1u)) adamw_chunk<true>(t, ck, coef, hp);
         else adamw_chunk<false>(t, ck, coef, hp);
+    }
+}
+
+template <bool AMSGRAD>
+__global__ __launch_bounds__(256) void adamw_classes_ema_kernel(const OptTensor *tab, const OptChunk *chunks, int nchunks,
+                                                                const float *normcoef, AdamTable tb, float w) {
+    const float coef0 = normcoef[1];
+    for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+        const OptChunk ck = chunks[c];
+        const OptTensor t = tab[ck.tensor];
+        const int k = __builtin_amdgcn_readfirstlane(t.cls) & (OPT_MAX_CLASSES - 1);
+        const AdamHyper hp = tb.hp[k];
+        const float coef = ((tb.maximize >> k) & 1u) ? -coef0 : coef0;
+        if (AMSGRAD && ((tb.amsgrad >> k) & 1u)) adamw_chunk<true, true>(t, ck, coef, hp, w);
+        else adamw_chunk<false, true>(t, ck, coef, hp, w);
+    }
+}
+
+// stand-alone weight average over a table of its own (mc_ema_bind: e in .p, its source in .g): e = ema_one(e, src, w) for
+// everything the optimizer did not step -- BatchNorm running statistics, parameters without a gradient, loops with another
+// optimizer -- and the yardstick of the fused path.  12 B/element.
+__global__ __launch_bounds__(256) void ema_kernel(const OptTensor *tab, const OptChunk *chunks, int nchunks, float w) {
+    for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+        const OptChunk ck = chunks[c];
+        const OptTensor t = tab[ck.tensor];
+        float *e = t.p + ck.begin;
+        const float *src = t.g + ck.begin;
+        int i0 = 0;
+        if (aligned16(e) && aligned16(src)) {
+            const int n4 = ck.count >> 2;
+            for (int i = threadIdx.x; i < n4; i += 256) {
+                f32x4 e4 = reinterpret_cast<f32x4 *>(e)[i];
+                const f32x4 s4 = reinterpret_cast<const f32x4 *>(src)[i];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { float ej = e4[j]; ema_one(ej, s4[j], w); e4[j] = ej; }
+                reinterpret_cast<f32x4 *>(e)[i] = e4;
+            }
+            i0 = n4 << 2;
+        }
+        for (int i = i0 + threadIdx.x; i < ck.count; i += 256) ema_one(e[i], src[i], w);
     }
 }
 
@@ -196,18 +270,29 @@ hipError_t launch_grad_norm(const OptTensor *tab, const OptChunk *chunks, int nc
     return hipGetLastError();
 }
 
+// ema_w: the step's weight of the average, 0 unless it is > 0 AND some bound tensor has one (the entry points see to that);
+// 0 launches the instantiations without EMA, as before
 hipError_t launch_clip_adamw(const OptTensor *tab, const OptChunk *chunks, int nchunks, float *partial, float *normcoef,
-                             float max_norm, const AdamHyper &hp, hipStream_t st) {
+                             float max_norm, const AdamHyper &hp, hipStream_t st, float ema_w) {
     launch_norm_kind<NORM_L2>(tab, chunks, nchunks, partial, normcoef, max_norm, 2.0, st);
-    hipLaunchKernelGGL(adamw_kernel, dim3(opt_blocks(nchunks)), dim3(256), 0, st, tab, chunks, nchunks, normcoef, hp);
+    if (ema_w > 0.f) hipLaunchKernelGGL(adamw_ema_kernel, dim3(opt_blocks(nchunks)), dim3(256), 0, st, tab, chunks, nchunks, normcoef, hp, ema_w);
+    else hipLaunchKernelGGL(adamw_kernel, dim3(opt_blocks(nchunks)), dim3(256), 0, st, tab, chunks, nchunks, normcoef, hp);
     return hipGetLastError();
 }
 
 hipError_t launch_adamw_classes(const OptTensor *tab, const OptChunk *chunks, int nchunks, const float *normcoef,
-                                const AdamTable &tb, hipStream_t st) {
+                                const AdamTable &tb, hipStream_t st, float ema_w) {
     const int blocks = opt_blocks(nchunks);
-    if (tb.amsgrad) hipLaunchKernelGGL(adamw_classes_kernel<true>, dim3(blocks), dim3(256), 0, st, tab, chunks, nchunks, normcoef, tb);
+    if (ema_w > 0.f) {
+        if (tb.amsgrad) hipLaunchKernelGGL(adamw_classes_ema_kernel<true>, dim3(blocks), dim3(256), 0, st, tab, chunks, nchunks, normcoef, tb, ema_w);
+        else hipLaunchKernelGGL(adamw_classes_ema_kernel<false>, dim3(blocks), dim3(256), 0, st, tab, chunks, nchunks, normcoef, tb, ema_w);
+    } else if (tb.amsgrad) hipLaunchKernelGGL(adamw_classes_kernel<true>, dim3(blocks), dim3(256), 0, st, tab, chunks, nchunks, normcoef, tb);
     else hipLaunchKernelGGL(adamw_classes_kernel<false>, dim3(blocks), dim3(256), 0, st, tab, chunks, nchunks, normcoef, tb);
+    return hipGetLastError();
+}
+
+hipError_t launch_ema(const OptTensor *tab, const OptChunk *chunks, int nchunks, float w, hipStream_t st) {
+    hipLaunchKernelGGL(ema_kernel, dim3(opt_blocks(nchunks)), dim3(256), 0, st, tab, chunks, nchunks, w);
     return hipGetLastError();
 }
 

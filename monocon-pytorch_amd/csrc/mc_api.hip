@@ -599,6 +599,8 @@ int mc_destroy(mc_handle *h) {
     if (h->opt_chunks) (void)hipFree(h->opt_chunks);
     if (h->clip_tab) (void)hipFree(h->clip_tab);
     if (h->clip_chunks) (void)hipFree(h->clip_chunks);
+    if (h->ema_tab) (void)hipFree(h->ema_tab);
+    if (h->ema_chunks) (void)hipFree(h->ema_chunks);
     if (h->opt_ws) (void)hipFree(h->opt_ws);
     delete h;
     return 0;

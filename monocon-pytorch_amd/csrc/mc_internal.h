@@ -275,6 +275,14 @@ struct mc_handle {
     mc::OptTensor *clip_tab = nullptr;
     mc::OptChunk *clip_chunks = nullptr;
     int clip_nchunks = 0;
+    // weight averages: the optimizer table's host copy (mc_optim_bind_ema fills its .e and uploads it again) and the
+    // (average, source) table of the stand-alone update (mc_ema_bind)
+    std::vector<mc::OptTensor> opt_host;
+    std::vector<int64_t> opt_numel;
+    bool opt_has_ema = false;   // some tensor of the bound optimizer table has an average
+    mc::OptTensor *ema_tab = nullptr;
+    mc::OptChunk *ema_chunks = nullptr;
+    int ema_nchunks = 0;
     // train-step plan (mc_train_plan.hip)
     TrainState *train = nullptr;
     size_t train_bytes = 0;   // device memory owned by the train plan

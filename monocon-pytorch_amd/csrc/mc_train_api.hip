@@ -295,10 +295,43 @@ static int optim_bind(mc_handle *h, const char *who, int n, float *const params[
         if (!vmax) novmax |= 1u << c;
     }
     h->opt_ntensors = 0;
+    h->opt_has_ema = false;     // a new table has no averages: mc_optim_bind_ema attaches them again
+    h->opt_host.clear();
+    h->opt_numel.clear();
     if (upload_opt_table(h, tab, numel, &h->opt_tab, &h->opt_chunks, &h->opt_nchunks)) return -1;
     h->opt_ntensors = n;
     h->opt_max_cls = max_cls;
     h->opt_novmax = novmax;
+    h->opt_host = tab;
+    h->opt_numel.assign(numel, numel + n);
+    return 0;
+}
+
+static bool ranges_overlap(const float *a, const float *b, int64_t n) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b), len = (uintptr_t)n * sizeof(float);
+    return x < y + len && y < x + len;
+}
+
+int mc_optim_bind_ema(mc_handle *h, int n, float *const ema[]) {
+    if (!h) return -1;
+    if (!h->opt_tab || h->opt_ntensors < 1) return fail(h, "mc_optim_bind_ema: call mc_optim_bind or mc_optim_bind_classes first");
+    if (!ema) return fail(h, "mc_optim_bind_ema: bad argument");
+    if (n != h->opt_ntensors)
+        return fail(h, "mc_optim_bind_ema: %d averages for a bound table of %d tensors", n, h->opt_ntensors);
+    bool any = false;
+    for (int i = 0; i < n; ++i) {
+        if (!ema[i]) continue;
+        if (ranges_overlap(ema[i], h->opt_host[i].p, h->opt_numel[i]))
+            return fail(h, "mc_optim_bind_ema: the average of tensor %d aliases its parameter", i);
+        any = true;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipDeviceSynchronize());      // a step in flight still reads the table
+    std::vector<mc::OptTensor> tab = h->opt_host;
+    for (int i = 0; i < n; ++i) tab[i].e = ema[i];
+    HIPCHK(h, hipMemcpy(h->opt_tab, tab.data(), tab.size() * sizeof(mc::OptTensor), hipMemcpyHostToDevice));
+    h->opt_host.swap(tab);
+    h->opt_has_ema = any;
     return 0;
 }
 
@@ -341,10 +374,11 @@ int mc_clip_adamw_step(mc_handle *h, double lr, double beta1, double beta2, doub
 
 static bool bad_norm_type(double p) { return !(p > 0.0); }   // p <= 0 and NaN
 
-int mc_clip_adamw_step_classes(mc_handle *h, const mc_optim_class *classes, int ncls, double max_norm, double norm_type,
-                               float *out_norm, void *stream) {
-    const char *who = "mc_clip_adamw_step_classes";
+// ema_weight: w = 1 - decay of this step's weight average; 0 (or a table without averages) is the step without it
+static int step_classes(mc_handle *h, const char *who, const mc_optim_class *classes, int ncls, double max_norm, double norm_type,
+                        double ema_weight, float *out_norm, void *stream) {
     if (!h) return -1;
+    if (!(ema_weight >= 0.0 && ema_weight <= 1.0)) return fail(h, "%s: ema_weight must lie in [0, 1], got %g", who, ema_weight);
     if (!h->opt_tab) return fail(h, "%s: call mc_optim_bind_classes first", who);
     if (!classes || ncls < 1) return fail(h, "%s: bad argument", who);
     if (ncls > MC_OPT_MAX_CLASSES)
@@ -367,16 +401,28 @@ int mc_clip_adamw_step_classes(mc_handle *h, const mc_optim_class *classes, int 
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     float *normcoef = h->opt_ws + mc::opt_partial_floats();
+    // the EMA instantiations only when there is something to average: in every other case the launches are the old ones
+    const float ema_w = h->opt_has_ema ? (float)ema_weight : 0.f;
     if (ncls == 1 && !tb.amsgrad && !tb.maximize && norm_type == 2.0) {
         // the reference recipe: the very launch mc_clip_adamw_step makes
-        HIPCHK(h, mc::launch_clip_adamw(h->opt_tab, h->opt_chunks, h->opt_nchunks, h->opt_ws, normcoef, (float)max_norm, tb.hp[0], st));
+        HIPCHK(h, mc::launch_clip_adamw(h->opt_tab, h->opt_chunks, h->opt_nchunks, h->opt_ws, normcoef, (float)max_norm, tb.hp[0], st, ema_w));
     } else {
         HIPCHK(h, mc::launch_grad_norm(h->opt_tab, h->opt_chunks, h->opt_nchunks, h->opt_ws, normcoef, (float)max_norm, norm_type, st));
-        HIPCHK(h, mc::launch_adamw_classes(h->opt_tab, h->opt_chunks, h->opt_nchunks, normcoef, tb, st));
+        HIPCHK(h, mc::launch_adamw_classes(h->opt_tab, h->opt_chunks, h->opt_nchunks, normcoef, tb, st, ema_w));
     }
     if (out_norm) HIPCHK(h, hipMemcpyAsync(out_norm, normcoef, sizeof(float), hipMemcpyDeviceToDevice, st));
     h->pack_clean = false;   // parameters changed: the packed panels are stale
     return 0;
+}
+
+int mc_clip_adamw_step_classes(mc_handle *h, const mc_optim_class *classes, int ncls, double max_norm, double norm_type,
+                               float *out_norm, void *stream) {
+    return step_classes(h, "mc_clip_adamw_step_classes", classes, ncls, max_norm, norm_type, 0.0, out_norm, stream);
+}
+
+int mc_clip_adamw_ema_step_classes(mc_handle *h, const mc_optim_class *classes, int ncls, double max_norm, double norm_type,
+                                   double ema_weight, float *out_norm, void *stream) {
+    return step_classes(h, "mc_clip_adamw_ema_step_classes", classes, ncls, max_norm, norm_type, ema_weight, out_norm, stream);
 }
 
 int mc_clip_bind(mc_handle *h, int n, float *const grads[], const int64_t numel[]) {
@@ -403,6 +449,31 @@ int mc_clip_grad_norm(mc_handle *h, double max_norm, double norm_type, float *ou
     HIPCHK(h, mc::launch_grad_norm(h->clip_tab, h->clip_chunks, h->clip_nchunks, h->opt_ws, normcoef, (float)max_norm, norm_type, st));
     if (max_norm > 0.0) HIPCHK(h, mc::launch_grad_scale(h->clip_tab, h->clip_chunks, h->clip_nchunks, normcoef, st));
     if (out_norm) HIPCHK(h, hipMemcpyAsync(out_norm, normcoef, sizeof(float), hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
+int mc_ema_bind(mc_handle *h, int n, float *const ema[], const float *const src[], const int64_t numel[]) {
+    if (!h) return -1;
+    if (n < 1 || !ema || !src || !numel) return fail(h, "mc_ema_bind: bad argument");
+    HIPCHK(h, hipSetDevice(h->device));
+    std::vector<mc::OptTensor> tab(n);
+    for (int i = 0; i < n; ++i) {
+        if (!ema[i] || !src[i] || numel[i] < 1) return fail(h, "mc_ema_bind: tensor %d has a null pointer / empty size", i);
+        if (numel[i] > INT32_MAX) return fail(h, "mc_ema_bind: tensor %d has more than 2^31-1 elements", i);
+        if (ranges_overlap(ema[i], src[i], numel[i])) return fail(h, "mc_ema_bind: the average of tensor %d aliases its source", i);
+        // the table's .p is the average, its .g the source it follows
+        tab[i] = mc::OptTensor{ema[i], const_cast<float *>(src[i]), nullptr, nullptr, nullptr, 0};
+    }
+    return upload_opt_table(h, tab, numel, &h->ema_tab, &h->ema_chunks, &h->ema_nchunks);
+}
+
+int mc_ema_update(mc_handle *h, double ema_weight, void *stream) {
+    if (!h) return -1;
+    if (!h->ema_tab) return fail(h, "mc_ema_update: call mc_ema_bind first");
+    if (!(ema_weight >= 0.0 && ema_weight <= 1.0)) return fail(h, "mc_ema_update: ema_weight must lie in [0, 1], got %g", ema_weight);
+    if ((float)ema_weight == 0.f) return 0;     // the average stays as it is, bit for bit (fmaf(0, x, -0) would be +0)
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, mc::launch_ema(h->ema_tab, h->ema_chunks, h->ema_nchunks, (float)ema_weight, static_cast<hipStream_t>(stream)));
     return 0;
 }
 

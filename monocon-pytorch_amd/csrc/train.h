@@ -149,8 +149,9 @@ struct FoldBatch {
 };
 
 // ---- fused clip + AdamW (reference engine/monocon_engine.py:94-102)
-// vmax: max_exp_avg_sq of an amsgrad class (null otherwise); cls: the tensor's hyper-parameter class (row of AdamTable)
-struct OptTensor { float *p, *g, *m, *v, *vmax; int cls; };
+// vmax: max_exp_avg_sq of an amsgrad class (null otherwise); cls: the tensor's hyper-parameter class (row of AdamTable);
+// e: the tensor's weight average (mc_optim_bind_ema; null: it has none)
+struct OptTensor { float *p, *g, *m, *v, *vmax; int cls; float *e; };
 struct OptChunk { int tensor, begin, count; };
 struct AdamHyper { float decay, beta1, one_minus_beta1, beta2, one_minus_beta2, sqrt_bc2, eps, step_size; };
 constexpr int OPT_MAX_CLASSES = 16;     // == MC_OPT_MAX_CLASSES
@@ -158,13 +159,15 @@ constexpr int OPT_MAX_CLASSES = 16;     // == MC_OPT_MAX_CLASSES
 // step kernel BY VALUE (kernel-argument segment): lr moves every step, and an argument has no buffer to race on.
 struct AdamTable { AdamHyper hp[OPT_MAX_CLASSES]; unsigned amsgrad, maximize; /* bit c: class c */ };
 hipError_t launch_clip_adamw(const OptTensor *tab, const OptChunk *chunks, int nchunks, float *partial, float *normcoef,
-                             float max_norm, const AdamHyper &hp, hipStream_t st);
+                             float max_norm, const AdamHyper &hp, hipStream_t st, float ema_w = 0.f);
 // the pieces of the general path: global p-norm (p = 1, 2, +inf or any finite p > 0) + clip coefficient into
 // normcoef[0..1]; the per-class step; the in-place gradient scale of a stand-alone clip_grad_norm_
 hipError_t launch_grad_norm(const OptTensor *tab, const OptChunk *chunks, int nchunks, float *partial, float *normcoef,
                             float max_norm, double norm_type, hipStream_t st);
 hipError_t launch_adamw_classes(const OptTensor *tab, const OptChunk *chunks, int nchunks, const float *normcoef,
-                                const AdamTable &tb, hipStream_t st);
+                                const AdamTable &tb, hipStream_t st, float ema_w = 0.f);
+// stand-alone weight average e = ema_one(e, src, w) over a table whose .p is e and whose .g is src (mc_ema_bind)
+hipError_t launch_ema(const OptTensor *tab, const OptChunk *chunks, int nchunks, float w, hipStream_t st);
 hipError_t launch_grad_scale(const OptTensor *tab, const OptChunk *chunks, int nchunks, const float *normcoef, hipStream_t st);
 int opt_partial_floats();
 

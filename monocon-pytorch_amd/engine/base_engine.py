@@ -5,6 +5,8 @@ one-process-per-GPU data parallelism (rank 0 prints / writes), TensorBoard optio
 Checkpoints keep the reference's layout: ``{'engine_attrs': {...}, 'state_dict': {'model',
 'optimizer', 'scheduler'}}`` in ``checkpoints/epoch_NNN[_postfix].pth``; loading uses
 ``weights_only=False`` because the reference pickles engine attributes (base_engine.py:171-174).
+With ``SOLVER.EMA.ENABLE`` (off by default; solver/model_ema.py) ``state_dict`` also has ``'ema'``: the
+averaged weights with their update count.  Without it the file is exactly the reference's layout.
 """
 import glob
 import os
@@ -50,6 +52,7 @@ class BaseEngine:
         self.model = self.build_model()
         # data parallelism averages gradients only: every replica starts from rank 0's weights and buffers
         hdist.sync_module_state(self.model)
+        self.ema = None         # solver.ModelEMA when SOLVER.EMA.ENABLE (build_solver creates and attaches it)
         self.optimizer, self.scheduler = self.build_solver() if not is_test else (None, None)
 
         self.root = cfg.OUTPUT_DIR
@@ -142,7 +145,7 @@ class BaseEngine:
 
     # ------------------------------------------------------------------ checkpoints
     _ATTR_EXCEPT = ('cfg', 'writer', 'train_loader', 'test_loader', 'train_dataset', 'test_dataset', 'model', 'optimizer',
-                    'scheduler')
+                    'scheduler', 'ema')
 
     def save_checkpoint(self, post_fix: str = None, save_after_update: bool = True, verbose: bool = True) -> None:
         if not self.is_main:
@@ -152,10 +155,12 @@ class BaseEngine:
         path = os.path.join(self.weight_dir, name)
         os.makedirs(self.weight_dir, exist_ok=True)
         attrs = {k: v for k, v in self.__dict__.items() if k not in self._ATTR_EXCEPT and not callable(v)}
-        torch.save({'engine_attrs': attrs,
-                    'state_dict': {'model': self.model.state_dict() if self.model is not None else None,
-                                   'optimizer': self.optimizer.state_dict() if self.optimizer is not None else None,
-                                   'scheduler': self.scheduler.state_dict() if self.scheduler is not None else None}}, path)
+        state = {'model': self.model.state_dict() if self.model is not None else None,
+                 'optimizer': self.optimizer.state_dict() if self.optimizer is not None else None,
+                 'scheduler': self.scheduler.state_dict() if self.scheduler is not None else None}
+        if getattr(self, 'ema', None) is not None:      # (without the average: the reference's three keys, nothing else)
+            state['ema'] = self.ema.state_dict()
+        torch.save({'engine_attrs': attrs, 'state_dict': state}, path)
         if verbose:
             tprint("Checkpoint is saved to '%s'." % path)
 
@@ -176,6 +181,13 @@ class BaseEngine:
             self.optimizer.load_state_dict(sd['optimizer'])
         if sd['scheduler'] is not None and self.scheduler is not None:
             self.scheduler.load_state_dict(sd['scheduler'])
+        ema = getattr(self, 'ema', None)
+        if ema is not None:
+            if sd.get('ema') is not None:
+                ema.load_state_dict(sd['ema'])
+            else:                           # e.g. a reference-layout .pth, or a run that had SOLVER.EMA off
+                ema.reset_from(self.model)
+                self._say("Checkpoint '%s' holds no averaged weights: the EMA starts from the loaded model." % ckpt_file)
         if verbose:
             self._say("Checkpoint is loaded from '%s'." % ckpt_file)
 

@@ -19,7 +19,7 @@ from torch.utils.data.distributed import DistributedSampler
 
 from engine.base_engine import BaseEngine
 from model import MonoConDetector
-from solver import AdamW, CyclicScheduler, build_param_groups
+from solver import AdamW, CyclicScheduler, ModelEMA, build_param_groups
 from utils.decorators import decorator_timer
 from hipmonocon.feed import WORKER_CONTEXT, DeferredScalars, DevicePrefetcher, RingLoader, prepare_worker_context
 from utils.engine_utils import move_data_device, progress_to_string_bar, reduce_loss_dict, tprint
@@ -59,6 +59,14 @@ class MonoconEngine(BaseEngine):
         optimizer = AdamW(groups, lr=optim.LR, weight_decay=optim.WEIGHT_DECAY, betas=(0.95, 0.99),
                           max_grad_norm=float(clip.MAX_NORM) if clip.ENABLE else None,
                           norm_type=float(clip.NORM_TYPE) if clip.ENABLE else 2.0)
+        # SOLVER.EMA: the optimizer's step keeps an average of the weights and BatchNorm statistics (solver/model_ema.py);
+        # evaluate() runs on it and the checkpoints carry it.  Under data parallelism every rank keeps its own: the ranks
+        # start from the same weights and apply the same all-reduced gradients, so the averages are identical and nothing
+        # is exchanged; rank 0 saves.
+        ema_cfg = self.cfg.SOLVER.get('EMA', None)
+        if ema_cfg is not None and ema_cfg.ENABLE:
+            self.ema = ModelEMA(self.model, decay=float(ema_cfg.DECAY), warmup=bool(ema_cfg.WARMUP))
+            optimizer.set_ema(self.ema)
         scheduler = None
         if self.cfg.SOLVER.SCHEDULER.ENABLE:
             total_steps = len(self.train_loader) * self.cfg.SOLVER.OPTIM.NUM_EPOCHS
@@ -158,6 +166,13 @@ class MonoconEngine(BaseEngine):
 
     @torch.no_grad()
     def evaluate(self) -> Dict[str, float]:
+        if self.ema is None:
+            return self._evaluate_model()
+        # SOLVER.EMA: on the averaged weights; the live ones are back, bit for bit, when this returns or raises
+        with self.ema.applied(self.model):
+            return self._evaluate_model()
+
+    def _evaluate_model(self) -> Dict[str, float]:
         was_training = self.model.training
         if was_training:
             self.model.eval()

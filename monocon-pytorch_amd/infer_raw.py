@@ -11,6 +11,10 @@ boxes of the label files back to each source frame.  Without the argument it is 
 default, the reference has none): taken off the command line and added to the test_config that test_raw.py builds, by the
 detector class its ``main`` finds in ``model.detector``.  Nothing outside this script's process and nothing in the package
 changes for it.
+
+``--use_ema`` runs the drive on the checkpoint's averaged weights (``state_dict['ema']``, written by a run with
+SOLVER.EMA.ENABLE; solver/model_ema.py) instead of the live ones, the same way: the detector class test_raw.py finds loads
+them in its ``load_checkpoint``, and a file without an average is an error, not a silent use of the live weights.
 """
 import argparse
 import os
@@ -22,7 +26,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 def main():
     # (behind the __main__ guard: the loader's workers come from a fork server and import this module again)
     ap = argparse.ArgumentParser('MonoCon Tester for KITTI Raw Dataset, at a chosen resolution', add_help=False,
-                                 usage="infer_raw.py [--target_hw H W] [--nms_thres T [--nms_mode M] [--nms_class_agnostic]] <arguments of test_raw.py, listed below>")
+                                 usage="infer_raw.py [--target_hw H W] [--nms_thres T [--nms_mode M] [--nms_class_agnostic]] [--use_ema] <arguments of test_raw.py, listed below>")
     ap.add_argument('--target_hw', type=int, nargs=2, default=None, metavar=('H', 'W'),
                     help="Run the network at this resolution: the frames are resampled on the device (default: their own size)")
     ap.add_argument('--nms_thres', type=float, default=None,
@@ -30,6 +34,8 @@ def main():
     ap.add_argument('--nms_mode', type=str, default='bev', choices=('bev', '3d'),
                     help="Overlap of the NMS: rotated bird's-eye-view IoU or 3D IoU")
     ap.add_argument('--nms_class_agnostic', action='store_true', help="Let boxes of different classes suppress each other")
+    ap.add_argument('--use_ema', action='store_true',
+                    help="Use the checkpoint's averaged weights (a run with SOLVER.EMA.ENABLE) instead of the live ones")
     args, rest = ap.parse_known_args()
     if '-h' in rest or '--help' in rest:
         ap.print_help()
@@ -47,6 +53,15 @@ def main():
                                  **kw)
 
         detector_pkg.MonoConDetector = MonoConDetectorWithNms
+    if args.use_ema:
+        # (after the NMS class, so that both can be asked for: this one derives from whatever model.detector holds now)
+        import model.detector as detector_pkg
+
+        class MonoConDetectorWithEma(detector_pkg.MonoConDetector):
+            def load_checkpoint(self, ckpt_file, use_ema=True):
+                super().load_checkpoint(ckpt_file, use_ema=True)        # (raises if the file holds no average)
+
+        detector_pkg.MonoConDetector = MonoConDetectorWithEma
     if args.target_hw is not None:
         if min(args.target_hw) < 1:
             ap.error("--target_hw needs two positive integers")

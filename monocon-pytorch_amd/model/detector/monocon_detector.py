@@ -167,10 +167,19 @@ class MonoConDetector(nn.Module):
                             'img_bbox2d': per_class})
         return kitti, vis
 
-    def load_checkpoint(self, ckpt_file: str):
+    def load_checkpoint(self, ckpt_file: str, use_ema: bool = False):
+        """``use_ema``: the checkpoint's averaged weights (written by a run with SOLVER.EMA.ENABLE, solver/model_ema.py)
+        instead of the live ones; a file without them is an error, never a silent use of the live weights"""
         # the reference pickles whole engine objects; torch >= 2.6 needs weights_only=False for those
         from utils.engine_utils import load_checkpoint_file
-        model_dict = load_checkpoint_file(ckpt_file)['state_dict']['model']
+        state = load_checkpoint_file(ckpt_file)['state_dict']
+        if use_ema:
+            if state.get('ema') is None:
+                raise KeyError("checkpoint '%s' holds no averaged weights (state_dict['ema']): it was written without "
+                               "SOLVER.EMA.ENABLE; run without --use_ema to use its live weights" % ckpt_file)
+            model_dict = state['ema']['tensors']
+        else:
+            model_dict = state['model']
         self.load_state_dict(model_dict)
 
     def _extract_feat_from_data_dict(self, data_dict: Dict[str, Any]) -> torch.Tensor:

@@ -1,6 +1,7 @@
-"""One-cycle LR / momentum schedule, the fused clip + AdamW step and the fused clip_grad_norm_."""
+"""One-cycle LR / momentum schedule, the fused clip + AdamW step, the fused clip_grad_norm_ and the weight average (ModelEMA)."""
 from .fused_adamw import AdamW, clip_grad_norm_
 from .cyclic_scheduler import CyclicScheduler
 from .param_groups import build_param_groups
+from .model_ema import ModelEMA
 
-__all__ = ("AdamW", "CyclicScheduler", "clip_grad_norm_", "build_param_groups")
+__all__ = ("AdamW", "CyclicScheduler", "clip_grad_norm_", "build_param_groups", "ModelEMA")

@@ -14,6 +14,12 @@ distinct (hyper-parameters, step) sets of one ``step()`` -- its *classes* -- go 
 table of at most ``MC_OPT_MAX_CLASSES`` rows, every bound tensor carries the index of its row.
 ``clip_grad_norm_`` is ``torch.nn.utils.clip_grad_norm_`` as three launches for the loop that clips
 by itself.
+
+``set_ema(ema)`` attaches a ``solver.ModelEMA``: the AdamW pass then also updates the average of every
+parameter it steps, from the new value while it is in registers (``mc_optim_bind_ema`` +
+``mc_clip_adamw_ema_step_classes``: 8 B/param more, no further launch), and ``step()`` ends with one
+``mc_ema_update`` over the rest of the model's state (BatchNorm running statistics, parameters
+without a gradient).  A loop with an attached average does not call ``ema.update`` itself.
 """
 import ctypes as C
 
@@ -91,12 +97,20 @@ class AdamW(Optimizer):
         self.max_grad_norm = max_grad_norm
         self.norm_type = check_norm_type(norm_type)
         self._engine = engine
+        self._ema = None                # solver.ModelEMA whose update step() performs (set_ema)
         self._bound_sig = None
         self._step_cache = None         # (key, host-side copies of the bound tensors' step counts); None: re-read the state
         self.last_grad_norm = None      # device scalar of the most recent pre-clip norm
 
     def set_engine(self, engine):
         self._engine = engine
+        self._bound_sig = None
+
+    def set_ema(self, ema):
+        """Attach (None: detach) a ``solver.ModelEMA``.  From now on ``step()`` performs the average's whole update: the
+        stepped parameters inside the AdamW pass, the rest of the model's state with one ``mc_ema_update``, then
+        ``ema.updates += 1``.  The caller must NOT call ``ema.update()`` as well -- that would average twice per step."""
+        self._ema = ema
         self._bound_sig = None
 
     def load_state_dict(self, state_dict):
@@ -155,14 +169,16 @@ class AdamW(Optimizer):
             self._step_cache = (key, [int(st['step']) for st in states])
         return self._step_cache[1]
 
-    def _bind(self, plist, states, ams, cls):
+    def _bind(self, plist, states, ams, cls, emas=None):
         eng = self._engine
         if eng is None:
             from hipmonocon.engine import Engine
             eng = self._engine = Engine(plist[0].device.index)
         # re-bound only when a pointer or a class index changes: lr moves every step, the class assignment does not
+        # (the averages of an attached ModelEMA are part of the same signature: one cache for both bindings)
         sig = (tuple([(p.data_ptr(), p.grad.data_ptr(), st['exp_avg'].data_ptr(), st['exp_avg_sq'].data_ptr(),
-                       st['max_exp_avg_sq'].data_ptr() if a else 0) for p, st, a in zip(plist, states, ams)]), cls)
+                       st['max_exp_avg_sq'].data_ptr() if a else 0) for p, st, a in zip(plist, states, ams)]), cls,
+               None if emas is None else tuple([0 if e is None else e.data_ptr() for e in emas]))
         if sig == self._bound_sig and getattr(eng, '_optim_sig', None) is self._bound_sig:
             return eng
         n = len(plist)
@@ -177,7 +193,14 @@ class AdamW(Optimizer):
                 _check_tensor(st[key], p, "state['%s']" % key)
             P[i], G[i], M[i], V[i], X[i] = sig[0][i]
             N[i] = p.numel()
+            if emas is not None and emas[i] is not None:
+                _check_tensor(emas[i], p, "the ModelEMA tensor of a stepped parameter")
+                if emas[i].numel() != p.numel():
+                    raise _lib.MonoconHipError("fused AdamW: a ModelEMA tensor and its parameter differ in size")
         _lib.check(eng.h, eng.lib.mc_optim_bind_classes(eng.h, n, P, G, M, V, X, N, K), "mc_optim_bind_classes")
+        if emas is not None:
+            E = (C.c_void_p * n)(*[e or None for e in sig[2]])
+            _lib.check(eng.h, eng.lib.mc_optim_bind_ema(eng.h, n, E), "mc_optim_bind_ema")
         self._bound_sig = eng._optim_sig = sig
         return eng
 
@@ -197,14 +220,18 @@ class AdamW(Optimizer):
                     gis.append(gi)
                     ams.append(a)
         if not plist:
+            if self._ema is not None:           # nothing to step: the average still follows the buffers
+                self._ema.update()
             return loss
         states = [self._init_state(p, a) for p, a in zip(plist, ams)]
         steps = self._steps(plist, states)
         for i in range(len(steps)):
             steps[i] += 1
+        ema = self._ema
         try:
             classes, cls = fold_classes(self.param_groups, list(zip(gis, steps)))
-            eng = self._bind(plist, states, ams, cls)
+            emas = ema.entries_of(plist) if ema is not None else None
+            eng = self._bind(plist, states, ams, cls, emas)
         except Exception:
             self._step_cache = None             # nothing was stepped: the state's own counts are the truth again
             raise
@@ -212,15 +239,27 @@ class AdamW(Optimizer):
         if self.last_grad_norm is None:
             self.last_grad_norm = torch.zeros(1, dtype=torch.float32, device=plist[0].device)
         table = (_lib.OptimClass * len(classes))(*classes)
+        max_norm = float(self.max_grad_norm) if self.max_grad_norm else 0.0
+        norm_out = C.c_void_p(self.last_grad_norm.data_ptr())
         with torch.cuda.device(plist[0].device):
-            rc = eng.lib.mc_clip_adamw_step_classes(eng.h, table, len(classes),
-                                                    float(self.max_grad_norm) if self.max_grad_norm else 0.0,
-                                                    self.norm_type, C.c_void_p(self.last_grad_norm.data_ptr()),
-                                                    C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _lib.check(eng.h, rc, "mc_clip_adamw_step_classes")
+            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)     # (the parameters' device's current stream)
+            if ema is None:
+                who = "mc_clip_adamw_step_classes"
+                rc = eng.lib.mc_clip_adamw_step_classes(eng.h, table, len(classes), max_norm, self.norm_type, norm_out, stream)
+            else:
+                who, w = "mc_clip_adamw_ema_step_classes", ema.weight()
+                rc = eng.lib.mc_clip_adamw_ema_step_classes(eng.h, table, len(classes), max_norm, self.norm_type, w, norm_out,
+                                                            stream)
+        _lib.check(eng.h, rc, who)
         # the kernels updated the parameters behind torch's back: advance their version counters
         # (host-only bookkeeping) so autograd and the engine's packed-weight cache see the change
         torch.autograd.graph.increment_version(plist)
+        if ema is not None:
+            done = [e for e in emas if e is not None]
+            if done:
+                torch.autograd.graph.increment_version(done)
+            # everything the pass above did not step: buffers, parameters without a gradient; counts the update
+            ema.update_rest(ema.model, w, skip=frozenset(map(id, done)), engine=eng)
         return loss
 
 

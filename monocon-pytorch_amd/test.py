@@ -20,12 +20,17 @@ def main():
     ap.add_argument('--nms_mode', type=str, default='bev', choices=('bev', '3d'),
                     help="Overlap of the NMS: rotated bird's-eye-view IoU or 3D IoU")
     ap.add_argument('--nms_class_agnostic', action='store_true', help="Let boxes of different classes suppress each other")
+    ap.add_argument('--use_ema', action='store_true',
+                    help="Evaluate the checkpoint's averaged weights (a run with SOLVER.EMA.ENABLE) instead of the live ones")
     args = ap.parse_args()
 
     cfg = load_cfg(args.config_file)
     cfg.GPU_ID = args.gpu_id
     engine = MonoconEngine(cfg, auto_resume=False, is_test=True)
     engine.load_checkpoint(args.checkpoint_file, verbose=True)
+    if args.use_ema:
+        engine.model.load_checkpoint(args.checkpoint_file, use_ema=True)    # (raises if the file has none)
+        tprint("Averaged (EMA) weights of '%s' are loaded to model." % args.checkpoint_file)
     if args.nms_thres is not None:
         # the head reads these keys when it decodes; a copy, so that the detector's default dict stays as it is
         engine.model.head.test_config = dict(engine.model.head.test_config, nms_thres=args.nms_thres, nms_mode=args.nms_mode,
