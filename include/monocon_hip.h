@@ -324,6 +324,37 @@ int mc_clip_adamw_ema_step_classes(mc_handle *h, const mc_optim_class *classes, 
 int mc_ema_bind(mc_handle *h, int n, float *const ema[], const float *const src[], const int64_t numel[]);
 int mc_ema_update(mc_handle *h, double ema_weight, void *stream);
 
+/* Non-finite guard of the fused step (torch's fused AdamW has found_inf, GradScaler skips the step,
+ * clip_grad_norm_ has error_if_nonfinite; the reference's loop has none): a step whose global gradient
+ * norm, as computed, is NaN or infinite is skipped on the device -- no host round trip, no further
+ * launch.  Python: solver.AdamW(skip_nonfinite=True), SOLVER.NONFINITE_GUARD.
+ * mc_optim_set_guard switches it (off by default).  Off, mc_clip_adamw_step, mc_clip_adamw_step_classes
+ * and mc_clip_adamw_ema_step_classes launch exactly what they always launched.  On, they launch guarded
+ * instantiations, as many as before: a step with a finite norm writes the same bits; a skipped step writes
+ * nothing to the parameters, the moments, max_exp_avg_sq and the attached averages (the gradients are
+ * only read, out_norm still receives the non-finite norm) and records the culprit instead.
+ * A skipped step still COUNTS: the caller folded `step` into the hyper-parameters before the launch and
+ * does not wait for the device to learn the outcome, so state['step'], the schedule and the average's
+ * update count advance as for a taken step.  The report carries the skip; a caller who wants taken
+ * steps subtracts.  A norm that is infinite only because finite squares overflowed fp32 skips as well,
+ * with first_tensor -1 and n_elements 0: the guard follows the norm as computed, as error_if_nonfinite does.
+ * Not protected: whatever the forward pass wrote before the step (BatchNorm running statistics).
+ * mc_optim_guard_report enqueues a copy of the last guarded step's record into dst -- device memory or
+ * page-locked host memory; anything else fails before the copy is enqueued, as does a handle whose guard
+ * is off.  Before the first guarded step the record reads {0, -1, 0, 0}.
+ * mc_ema_update_guarded is mc_ema_update that does nothing when the last guarded step was skipped, so that
+ * the rest of an average (BatchNorm statistics, parameters without a gradient) stays where the stepped
+ * part stayed; with the guard off, or before any guarded step, it is exactly mc_ema_update. */
+typedef struct mc_guard_report {
+    int skipped;                    /* 1: the step was skipped */
+    int first_tensor;               /* smallest index in the bound table of a tensor with a NaN/inf gradient element; -1: none */
+    unsigned long long n_elements;  /* NaN/inf gradient elements over the whole table (counted on a skipped step only) */
+    float norm;                     /* the norm as computed */
+} mc_guard_report;
+int mc_optim_set_guard(mc_handle *h, int on);
+int mc_optim_guard_report(mc_handle *h, mc_guard_report *dst, void *stream);
+int mc_ema_update_guarded(mc_handle *h, double ema_weight, void *stream);
+
 /* ---- op-level entry points (unit parity tests; same kernels the forward uses) -------
  * Fused convolution, NHWC fp32: out = act(conv(cat(src...)) * scale + bias + residual).
  * Replaces nn.Conv2d + nn.BatchNorm2d(eval) + ReLU (+ torch.cat, + residual add) of

@@ -35,6 +35,10 @@ _DEFAULTS = {
         # EMA (not in the reference's tree; off = its loop): an exponential moving average of the weights and BatchNorm
         # statistics, updated inside the fused AdamW step, used by evaluate() and kept in the checkpoints -- solver/model_ema.py
         "EMA": {"ENABLE": False, "DECAY": 0.9998, "WARMUP": True},
+        # NONFINITE_GUARD (not in the reference's tree; off = its loop): the fused AdamW step skips itself, on the device, when
+        # the gradient norm is NaN or infinite; the loop reports the step one iteration late and gives up after
+        # MAX_CONSECUTIVE skipped steps in a row -- solver/fused_adamw.py (skip_nonfinite)
+        "NONFINITE_GUARD": {"ENABLE": False, "MAX_CONSECUTIVE": 10},
     },
     "PERIOD": {"EVAL_PERIOD": 10, "LOG_PERIOD": 50},
 }

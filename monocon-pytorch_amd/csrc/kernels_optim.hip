@@ -8,6 +8,9 @@
 // the ones the committed goldens were recorded against.  The other instantiations add the norm kinds of
 // clip_grad_norm_ and torch.optim.AdamW's per-group options, and (EMA) the exponential moving average of the weights that
 // long runs keep for evaluation: formed in the step's own pass, 8 B/param more, no launch and no second read of p.
+// The *_guarded kernels (mc_optim_set_guard, off by default) are further instantiations beside those: the step skips
+// itself when the norm is not finite, decided on the device from the norm that is already there.  The unguarded
+// kernels are launched exactly as before while the guard is off.
 #include <stdint.h>
 #include "conv_mfma.h"
 #include "train.h"
@@ -74,6 +77,33 @@ __global__ void gradnorm_final_kernel(const float *partial, int n, float max_nor
         out[0] = norm;
         const float coef = max_norm / (norm + 1e-6f);
         out[1] = (max_norm > 0.f && coef < 1.f) ? coef : 1.f;
+    }
+}
+
+// ---- non-finite guard (mc_optim_set_guard).  An element with an all-ones exponent is a NaN or an infinity.
+__device__ __forceinline__ unsigned nonfinite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u ? 1u : 0u; }
+
+// gradnorm_final_kernel (its reduction, its root, its coefficient: the same bits in out[0..1]) that also opens the step's
+// guard record: skipped when the norm AS COMPUTED is not finite -- a NaN or infinite element, or finite squares whose fp32
+// sum overflowed -- as clip_grad_norm_(error_if_nonfinite=True) judges it.  The AdamW pass that follows reads the flag.
+template <int KIND>
+__global__ void gradnorm_final_guarded_kernel(const float *partial, int n, float max_norm, float *out /*[2]: norm, coef*/, double inv_p,
+                                              GuardRecord *rec) {
+    double s = 0;
+    for (int i = threadIdx.x; i < n; i += 64) s = norm_join<KIND>(s, (double)partial[i]);
+    for (int o = 32; o > 0; o >>= 1) s = norm_join<KIND>(s, __shfl_xor(s, o));
+    if (threadIdx.x == 0) {
+        float norm;
+        if constexpr (KIND == NORM_L2) norm = (float)sqrt(s);
+        else if constexpr (KIND == NORM_P) norm = (float)pow(s, inv_p);
+        else norm = (float)s;
+        out[0] = norm;
+        const float coef = max_norm / (norm + 1e-6f);
+        out[1] = (max_norm > 0.f && coef < 1.f) ? coef : 1.f;
+        rec->skipped = (int)nonfinite(norm);
+        rec->first_tensor = -1;
+        rec->n_elements = 0ull;
+        rec->norm = norm;
     }
 }
 
@@ -201,10 +231,92 @@ __global__ __launch_bounds__(256) void adamw_classes_ema_kernel(const OptTensor 
     }
 }
 
+// ---- the guarded step.  The flag is read once per workgroup, as a uniform value.  Clear: the very walk of the kernels
+// above over the same adamw_chunk bodies, so every bit of p, m, v, vmax and e is theirs.  Set: nothing is written to any of
+// them; the workgroups walk g alone (4 B/param, the norm pass's float4-body / scalar-tail split) and name the culprit with
+// one vector-memory atomic pair per workgroup that found something: the smallest table index of a tensor holding a NaN/inf
+// element (first_tensor is -1 = 0xffffffff before: an unsigned minimum) and the number of such elements.  A norm that
+// overflowed from finite elements finds nothing and leaves -1 / 0.
+__device__ __forceinline__ void guard_scan(const OptTensor *tab, const OptChunk *chunks, int nchunks, GuardRecord *rec) {
+    unsigned long long cnt = 0ull;
+    unsigned first = ~0u;
+    for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+        const OptChunk ck = chunks[c];
+        const float *g = tab[ck.tensor].g + ck.begin;
+        unsigned here = 0u;
+        int i0 = 0;
+        if (aligned16(g)) {
+            const int n4 = ck.count >> 2;
+            const f32x4 *g4 = reinterpret_cast<const f32x4 *>(g);
+            for (int i = threadIdx.x; i < n4; i += 256) {
+                const f32x4 v = g4[i];
+                here += nonfinite(v[0]) + nonfinite(v[1]) + nonfinite(v[2]) + nonfinite(v[3]);
+            }
+            i0 = n4 << 2;
+        }
+        for (int i = i0 + threadIdx.x; i < ck.count; i += 256) here += nonfinite(g[i]);
+        if (here) {
+            cnt += here;
+            if ((unsigned)ck.tensor < first) first = (unsigned)ck.tensor;
+        }
+    }
+    __shared__ unsigned long long red_cnt[4];
+    __shared__ unsigned red_first[4];
+    for (int o = 32; o > 0; o >>= 1) {
+        cnt += __shfl_xor(cnt, o);
+        const unsigned f = __shfl_xor(first, o);
+        first = f < first ? f : first;
+    }
+    if ((threadIdx.x & 63) == 0) { red_cnt[threadIdx.x >> 6] = cnt; red_first[threadIdx.x >> 6] = first; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        cnt = red_cnt[0] + red_cnt[1] + red_cnt[2] + red_cnt[3];
+        for (int k = 1; k < 4; ++k) first = red_first[k] < first ? red_first[k] : first;
+        if (cnt) {
+            atomicAdd(&rec->n_elements, cnt);
+            atomicMin(reinterpret_cast<unsigned *>(&rec->first_tensor), first);
+        }
+    }
+}
+
+template <bool EMA>
+__global__ __launch_bounds__(256) void adamw_guarded_kernel(const OptTensor *tab, const OptChunk *chunks, int nchunks,
+                                                            const float *normcoef, AdamHyper hp, float w, GuardRecord *rec) {
+    if (__builtin_amdgcn_readfirstlane(rec->skipped)) { guard_scan(tab, chunks, nchunks, rec); return; }
+    const float coef = normcoef[1];
+    for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+        const OptChunk ck = chunks[c];
+        const OptTensor t = tab[ck.tensor];
+        if constexpr (EMA) adamw_chunk<false, true>(t, ck, coef, hp, w);
+        else adamw_chunk<false>(t, ck, coef, hp);
+    }
+}
+
+template <bool AMSGRAD, bool EMA>
+__global__ __launch_bounds__(256) void adamw_classes_guarded_kernel(const OptTensor *tab, const OptChunk *chunks, int nchunks,
+                                                                    const float *normcoef, AdamTable tb, float w, GuardRecord *rec) {
+    if (__builtin_amdgcn_readfirstlane(rec->skipped)) { guard_scan(tab, chunks, nchunks, rec); return; }
+    const float coef0 = normcoef[1];
+    for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+        const OptChunk ck = chunks[c];
+        const OptTensor t = tab[ck.tensor];
+        const int k = __builtin_amdgcn_readfirstlane(t.cls) & (OPT_MAX_CLASSES - 1);
+        const AdamHyper hp = tb.hp[k];
+        const float coef = ((tb.maximize >> k) & 1u) ? -coef0 : coef0;
+        if constexpr (EMA) {
+            if (AMSGRAD && ((tb.amsgrad >> k) & 1u)) adamw_chunk<true, true>(t, ck, coef, hp, w);
+            else adamw_chunk<false, true>(t, ck, coef, hp, w);
+        } else {
+            if (AMSGRAD && ((tb.amsgrad >> k) & 1u)) adamw_chunk<true>(t, ck, coef, hp);
+            else adamw_chunk<false>(t, ck, coef, hp);
+        }
+    }
+}
+
 // stand-alone weight average over a table of its own (mc_ema_bind: e in .p, its source in .g): e = ema_one(e, src, w) for
 // everything the optimizer did not step -- BatchNorm running statistics, parameters without a gradient, loops with another
 // optimizer -- and the yardstick of the fused path.  12 B/element.
-__global__ __launch_bounds__(256) void ema_kernel(const OptTensor *tab, const OptChunk *chunks, int nchunks, float w) {
+__device__ __forceinline__ void ema_walk(const OptTensor *tab, const OptChunk *chunks, int nchunks, float w) {
     for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
         const OptChunk ck = chunks[c];
         const OptTensor t = tab[ck.tensor];
@@ -224,6 +336,18 @@ __global__ __launch_bounds__(256) void ema_kernel(const OptTensor *tab, const Op
         }
         for (int i = i0 + threadIdx.x; i < ck.count; i += 256) ema_one(e[i], src[i], w);
     }
+}
+
+__global__ __launch_bounds__(256) void ema_kernel(const OptTensor *tab, const OptChunk *chunks, int nchunks, float w) {
+    ema_walk(tab, chunks, nchunks, w);
+}
+
+// mc_ema_update_guarded: nothing at all when the handle's last guarded step was skipped -- the rest of the average
+// (BatchNorm running statistics, parameters without a gradient) then stays where the stepped part stayed
+__global__ __launch_bounds__(256) void ema_guarded_kernel(const OptTensor *tab, const OptChunk *chunks, int nchunks, float w,
+                                                          const GuardRecord *rec) {
+    if (__builtin_amdgcn_readfirstlane(rec->skipped)) return;
+    ema_walk(tab, chunks, nchunks, w);
 }
 
 // stand-alone clip_grad_norm_: every bound gradient times the clip coefficient, in place
@@ -254,18 +378,19 @@ static int opt_blocks(int nchunks) { return nchunks < OPT_BLOCKS ? nchunks : OPT
 
 template <int KIND>
 static void launch_norm_kind(const OptTensor *tab, const OptChunk *chunks, int nchunks, float *partial, float *normcoef,
-                             float max_norm, double norm_type, hipStream_t st) {
+                             float max_norm, double norm_type, hipStream_t st, GuardRecord *guard = nullptr) {
     const int blocks = opt_blocks(nchunks);
     hipLaunchKernelGGL(gradnorm_partial_kernel<KIND>, dim3(blocks), dim3(256), 0, st, tab, chunks, nchunks, partial, (float)norm_type);
-    hipLaunchKernelGGL(gradnorm_final_kernel<KIND>, dim3(1), dim3(64), 0, st, partial, blocks, max_norm, normcoef, 1.0 / norm_type);
+    if (guard) hipLaunchKernelGGL(gradnorm_final_guarded_kernel<KIND>, dim3(1), dim3(64), 0, st, partial, blocks, max_norm, normcoef, 1.0 / norm_type, guard);
+    else hipLaunchKernelGGL(gradnorm_final_kernel<KIND>, dim3(1), dim3(64), 0, st, partial, blocks, max_norm, normcoef, 1.0 / norm_type);
 }
 
 hipError_t launch_grad_norm(const OptTensor *tab, const OptChunk *chunks, int nchunks, float *partial, float *normcoef,
-                            float max_norm, double norm_type, hipStream_t st) {
-    if (norm_type == 2.0) launch_norm_kind<NORM_L2>(tab, chunks, nchunks, partial, normcoef, max_norm, norm_type, st);
-    else if (norm_type == 1.0) launch_norm_kind<NORM_L1>(tab, chunks, nchunks, partial, normcoef, max_norm, norm_type, st);
-    else if (norm_type == INFINITY) launch_norm_kind<NORM_INF>(tab, chunks, nchunks, partial, normcoef, max_norm, norm_type, st);
-    else if (norm_type > 0.0) launch_norm_kind<NORM_P>(tab, chunks, nchunks, partial, normcoef, max_norm, norm_type, st);
+                            float max_norm, double norm_type, hipStream_t st, GuardRecord *guard) {
+    if (norm_type == 2.0) launch_norm_kind<NORM_L2>(tab, chunks, nchunks, partial, normcoef, max_norm, norm_type, st, guard);
+    else if (norm_type == 1.0) launch_norm_kind<NORM_L1>(tab, chunks, nchunks, partial, normcoef, max_norm, norm_type, st, guard);
+    else if (norm_type == INFINITY) launch_norm_kind<NORM_INF>(tab, chunks, nchunks, partial, normcoef, max_norm, norm_type, st, guard);
+    else if (norm_type > 0.0) launch_norm_kind<NORM_P>(tab, chunks, nchunks, partial, normcoef, max_norm, norm_type, st, guard);
     else return hipErrorInvalidValue;            // p <= 0 or NaN (the entry points reject it before this)
     return hipGetLastError();
 }
@@ -273,17 +398,26 @@ hipError_t launch_grad_norm(const OptTensor *tab, const OptChunk *chunks, int nc
 // ema_w: the step's weight of the average, 0 unless it is > 0 AND some bound tensor has one (the entry points see to that);
 // 0 launches the instantiations without EMA, as before
 hipError_t launch_clip_adamw(const OptTensor *tab, const OptChunk *chunks, int nchunks, float *partial, float *normcoef,
-                             float max_norm, const AdamHyper &hp, hipStream_t st, float ema_w) {
-    launch_norm_kind<NORM_L2>(tab, chunks, nchunks, partial, normcoef, max_norm, 2.0, st);
-    if (ema_w > 0.f) hipLaunchKernelGGL(adamw_ema_kernel, dim3(opt_blocks(nchunks)), dim3(256), 0, st, tab, chunks, nchunks, normcoef, hp, ema_w);
+                             float max_norm, const AdamHyper &hp, hipStream_t st, float ema_w, GuardRecord *guard) {
+    launch_norm_kind<NORM_L2>(tab, chunks, nchunks, partial, normcoef, max_norm, 2.0, st, guard);
+    if (guard) {
+        if (ema_w > 0.f) hipLaunchKernelGGL(adamw_guarded_kernel<true>, dim3(opt_blocks(nchunks)), dim3(256), 0, st, tab, chunks, nchunks, normcoef, hp, ema_w, guard);
+        else hipLaunchKernelGGL(adamw_guarded_kernel<false>, dim3(opt_blocks(nchunks)), dim3(256), 0, st, tab, chunks, nchunks, normcoef, hp, 0.f, guard);
+    } else if (ema_w > 0.f) hipLaunchKernelGGL(adamw_ema_kernel, dim3(opt_blocks(nchunks)), dim3(256), 0, st, tab, chunks, nchunks, normcoef, hp, ema_w);
     else hipLaunchKernelGGL(adamw_kernel, dim3(opt_blocks(nchunks)), dim3(256), 0, st, tab, chunks, nchunks, normcoef, hp);
     return hipGetLastError();
 }
 
 hipError_t launch_adamw_classes(const OptTensor *tab, const OptChunk *chunks, int nchunks, const float *normcoef,
-                                const AdamTable &tb, hipStream_t st, float ema_w) {
+                                const AdamTable &tb, hipStream_t st, float ema_w, GuardRecord *guard) {
     const int blocks = opt_blocks(nchunks);
-    if (ema_w > 0.f) {
+    if (guard) {
+        if (ema_w > 0.f) {
+            if (tb.amsgrad) hipLaunchKernelGGL((adamw_classes_guarded_kernel<true, true>), dim3(blocks), dim3(256), 0, st, tab, chunks, nchunks, normcoef, tb, ema_w, guard);
+            else hipLaunchKernelGGL((adamw_classes_guarded_kernel<false, true>), dim3(blocks), dim3(256), 0, st, tab, chunks, nchunks, normcoef, tb, ema_w, guard);
+        } else if (tb.amsgrad) hipLaunchKernelGGL((adamw_classes_guarded_kernel<true, false>), dim3(blocks), dim3(256), 0, st, tab, chunks, nchunks, normcoef, tb, 0.f, guard);
+        else hipLaunchKernelGGL((adamw_classes_guarded_kernel<false, false>), dim3(blocks), dim3(256), 0, st, tab, chunks, nchunks, normcoef, tb, 0.f, guard);
+    } else if (ema_w > 0.f) {
         if (tb.amsgrad) hipLaunchKernelGGL(adamw_classes_ema_kernel<true>, dim3(blocks), dim3(256), 0, st, tab, chunks, nchunks, normcoef, tb, ema_w);
         else hipLaunchKernelGGL(adamw_classes_ema_kernel<false>, dim3(blocks), dim3(256), 0, st, tab, chunks, nchunks, normcoef, tb, ema_w);
     } else if (tb.amsgrad) hipLaunchKernelGGL(adamw_classes_kernel<true>, dim3(blocks), dim3(256), 0, st, tab, chunks, nchunks, normcoef, tb);
@@ -291,8 +425,9 @@ hipError_t launch_adamw_classes(const OptTensor *tab, const OptChunk *chunks, in
     return hipGetLastError();
 }
 
-hipError_t launch_ema(const OptTensor *tab, const OptChunk *chunks, int nchunks, float w, hipStream_t st) {
-    hipLaunchKernelGGL(ema_kernel, dim3(opt_blocks(nchunks)), dim3(256), 0, st, tab, chunks, nchunks, w);
+hipError_t launch_ema(const OptTensor *tab, const OptChunk *chunks, int nchunks, float w, hipStream_t st, const GuardRecord *guard) {
+    if (guard) hipLaunchKernelGGL(ema_guarded_kernel, dim3(opt_blocks(nchunks)), dim3(256), 0, st, tab, chunks, nchunks, w, guard);
+    else hipLaunchKernelGGL(ema_kernel, dim3(opt_blocks(nchunks)), dim3(256), 0, st, tab, chunks, nchunks, w);
     return hipGetLastError();
 }
 

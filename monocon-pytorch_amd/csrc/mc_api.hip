@@ -602,6 +602,7 @@ int mc_destroy(mc_handle *h) {
     if (h->ema_tab) (void)hipFree(h->ema_tab);
     if (h->ema_chunks) (void)hipFree(h->ema_chunks);
     if (h->opt_ws) (void)hipFree(h->opt_ws);
+    if (h->opt_guard) (void)hipFree(h->opt_guard);
     delete h;
     return 0;
 }

@@ -283,6 +283,10 @@ struct mc_handle {
     mc::OptTensor *ema_tab = nullptr;
     mc::OptChunk *ema_chunks = nullptr;
     int ema_nchunks = 0;
+    // non-finite guard (mc_optim_set_guard): the step entries launch the guarded instantiations while it is on
+    mc::GuardRecord *opt_guard = nullptr;   // the last guarded step's record (device)
+    bool opt_guard_on = false;
+    bool opt_guard_ran = false; // a guarded step has run since the guard was switched on: the record is a step's
     // train-step plan (mc_train_plan.hip)
     TrainState *train = nullptr;
     size_t train_bytes = 0;   // device memory owned by the train plan

@@ -366,7 +366,9 @@ int mc_clip_adamw_step(mc_handle *h, double lr, double beta1, double beta2, doub
     mc::AdamHyper hp;
     fold_hyper(hp, lr, beta1, beta2, eps, weight_decay, step);
     float *normcoef = h->opt_ws + mc::opt_partial_floats();
-    HIPCHK(h, mc::launch_clip_adamw(h->opt_tab, h->opt_chunks, h->opt_nchunks, h->opt_ws, normcoef, (float)max_norm, hp, st));
+    mc::GuardRecord *guard = h->opt_guard_on ? h->opt_guard : nullptr;    // null: the launches of always
+    HIPCHK(h, mc::launch_clip_adamw(h->opt_tab, h->opt_chunks, h->opt_nchunks, h->opt_ws, normcoef, (float)max_norm, hp, st, 0.f, guard));
+    if (guard) h->opt_guard_ran = true;
     if (out_norm) HIPCHK(h, hipMemcpyAsync(out_norm, normcoef, sizeof(float), hipMemcpyDeviceToDevice, st));
     h->pack_clean = false;   // parameters changed: the packed panels are stale
     return 0;
@@ -403,13 +405,15 @@ static int step_classes(mc_handle *h, const char *who, const mc_optim_class *cla
     float *normcoef = h->opt_ws + mc::opt_partial_floats();
     // the EMA instantiations only when there is something to average: in every other case the launches are the old ones
     const float ema_w = h->opt_has_ema ? (float)ema_weight : 0.f;
+    mc::GuardRecord *guard = h->opt_guard_on ? h->opt_guard : nullptr;    // null: the launches of always
     if (ncls == 1 && !tb.amsgrad && !tb.maximize && norm_type == 2.0) {
         // the reference recipe: the very launch mc_clip_adamw_step makes
-        HIPCHK(h, mc::launch_clip_adamw(h->opt_tab, h->opt_chunks, h->opt_nchunks, h->opt_ws, normcoef, (float)max_norm, tb.hp[0], st, ema_w));
+        HIPCHK(h, mc::launch_clip_adamw(h->opt_tab, h->opt_chunks, h->opt_nchunks, h->opt_ws, normcoef, (float)max_norm, tb.hp[0], st, ema_w, guard));
     } else {
-        HIPCHK(h, mc::launch_grad_norm(h->opt_tab, h->opt_chunks, h->opt_nchunks, h->opt_ws, normcoef, (float)max_norm, norm_type, st));
-        HIPCHK(h, mc::launch_adamw_classes(h->opt_tab, h->opt_chunks, h->opt_nchunks, normcoef, tb, st, ema_w));
+        HIPCHK(h, mc::launch_grad_norm(h->opt_tab, h->opt_chunks, h->opt_nchunks, h->opt_ws, normcoef, (float)max_norm, norm_type, st, guard));
+        HIPCHK(h, mc::launch_adamw_classes(h->opt_tab, h->opt_chunks, h->opt_nchunks, normcoef, tb, st, ema_w, guard));
     }
+    if (guard) h->opt_guard_ran = true;
     if (out_norm) HIPCHK(h, hipMemcpyAsync(out_norm, normcoef, sizeof(float), hipMemcpyDeviceToDevice, st));
     h->pack_clean = false;   // parameters changed: the packed panels are stale
     return 0;
@@ -474,6 +478,57 @@ int mc_ema_update(mc_handle *h, double ema_weight, void *stream) {
     if ((float)ema_weight == 0.f) return 0;     // the average stays as it is, bit for bit (fmaf(0, x, -0) would be +0)
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, mc::launch_ema(h->ema_tab, h->ema_chunks, h->ema_nchunks, (float)ema_weight, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+// ---- non-finite guard
+int mc_optim_set_guard(mc_handle *h, int on) {
+    if (!h) return -1;
+    if (!on) {
+        h->opt_guard_on = h->opt_guard_ran = false;
+        return 0;
+    }
+    if (h->opt_guard_on) return 0;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!h->opt_guard) {
+        void *q = nullptr;
+        HIPCHK(h, hipMalloc(&q, sizeof(mc::GuardRecord)));
+        h->opt_guard = static_cast<mc::GuardRecord *>(q);
+    } else {
+        HIPCHK(h, hipDeviceSynchronize());      // a report of the guard's earlier life may still read the record
+    }
+    const mc::GuardRecord none{0, -1, 0ull, 0.f, 0};
+    HIPCHK(h, hipMemcpy(h->opt_guard, &none, sizeof(none), hipMemcpyHostToDevice));
+    h->opt_guard_on = true;
+    h->opt_guard_ran = false;
+    return 0;
+}
+
+static_assert(sizeof(mc_guard_report) == sizeof(mc::GuardRecord), "mc_guard_report is the device record");
+
+int mc_optim_guard_report(mc_handle *h, mc_guard_report *dst, void *stream) {
+    if (!h) return -1;
+    if (!h->opt_guard_on || !h->opt_guard) return fail(h, "mc_optim_guard_report: the guard is off (mc_optim_set_guard)");
+    if (!dst) return fail(h, "mc_optim_guard_report: bad argument");
+    HIPCHK(h, hipSetDevice(h->device));
+    // an asynchronous copy needs device or page-locked host memory: into pageable memory it would block, or land late
+    hipPointerAttribute_t attr{};
+    const hipError_t e = hipPointerGetAttributes(&attr, dst);
+    if (e != hipSuccess) (void)hipGetLastError();       // an address the runtime does not know
+    if (e != hipSuccess || (attr.type != hipMemoryTypeDevice && attr.type != hipMemoryTypeHost))
+        return fail(h, "mc_optim_guard_report: dst must be device memory or page-locked host memory");
+    HIPCHK(h, hipMemcpyAsync(dst, h->opt_guard, sizeof(mc_guard_report), hipMemcpyDefault, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int mc_ema_update_guarded(mc_handle *h, double ema_weight, void *stream) {
+    if (!h) return -1;
+    if (!h->opt_guard_on || !h->opt_guard_ran) return mc_ema_update(h, ema_weight, stream);
+    if (!h->ema_tab) return fail(h, "mc_ema_update_guarded: call mc_ema_bind first");
+    if (!(ema_weight >= 0.0 && ema_weight <= 1.0)) return fail(h, "mc_ema_update_guarded: ema_weight must lie in [0, 1], got %g", ema_weight);
+    if ((float)ema_weight == 0.f) return 0;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, mc::launch_ema(h->ema_tab, h->ema_chunks, h->ema_nchunks, (float)ema_weight, static_cast<hipStream_t>(stream), h->opt_guard));
     return 0;
 }
 

@@ -158,16 +158,23 @@ constexpr int OPT_MAX_CLASSES = 16;     // == MC_OPT_MAX_CLASSES
 // One row per distinct (lr, betas, eps, weight_decay, step, amsgrad, maximize), folded on the host in double; passed to the
 // step kernel BY VALUE (kernel-argument segment): lr moves every step, and an argument has no buffer to race on.
 struct AdamTable { AdamHyper hp[OPT_MAX_CLASSES]; unsigned amsgrad, maximize; /* bit c: class c */ };
+// The non-finite guard's device-resident record of one step (== mc_guard_report).  The guarded final norm kernel writes it
+// whole (skipped = !isfinite(norm), first_tensor -1, n_elements 0); the guarded AdamW kernels of a skipped step add what
+// they find in the gradients: the smallest table index of a tensor with a NaN/inf element, and how many such elements.
+struct GuardRecord { int skipped, first_tensor; unsigned long long n_elements; float norm; int pad_; };
+// `guard` (null: off) on every launcher below selects the guarded instantiations: the same number of launches, the same
+// bits while guard->skipped is clear; once it is set the AdamW pass only reads g and the stand-alone average does nothing.
 hipError_t launch_clip_adamw(const OptTensor *tab, const OptChunk *chunks, int nchunks, float *partial, float *normcoef,
-                             float max_norm, const AdamHyper &hp, hipStream_t st, float ema_w = 0.f);
+                             float max_norm, const AdamHyper &hp, hipStream_t st, float ema_w = 0.f, GuardRecord *guard = nullptr);
 // the pieces of the general path: global p-norm (p = 1, 2, +inf or any finite p > 0) + clip coefficient into
 // normcoef[0..1]; the per-class step; the in-place gradient scale of a stand-alone clip_grad_norm_
 hipError_t launch_grad_norm(const OptTensor *tab, const OptChunk *chunks, int nchunks, float *partial, float *normcoef,
-                            float max_norm, double norm_type, hipStream_t st);
+                            float max_norm, double norm_type, hipStream_t st, GuardRecord *guard = nullptr);
 hipError_t launch_adamw_classes(const OptTensor *tab, const OptChunk *chunks, int nchunks, const float *normcoef,
-                                const AdamTable &tb, hipStream_t st, float ema_w = 0.f);
+                                const AdamTable &tb, hipStream_t st, float ema_w = 0.f, GuardRecord *guard = nullptr);
 // stand-alone weight average e = ema_one(e, src, w) over a table whose .p is e and whose .g is src (mc_ema_bind)
-hipError_t launch_ema(const OptTensor *tab, const OptChunk *chunks, int nchunks, float w, hipStream_t st);
+hipError_t launch_ema(const OptTensor *tab, const OptChunk *chunks, int nchunks, float w, hipStream_t st,
+                      const GuardRecord *guard = nullptr);
 hipError_t launch_grad_scale(const OptTensor *tab, const OptChunk *chunks, int nchunks, const float *normcoef, hipStream_t st);
 int opt_partial_floats();
 

@@ -7,6 +7,7 @@ Checkpoints keep the reference's layout: ``{'engine_attrs': {...}, 'state_dict':
 ``weights_only=False`` because the reference pickles engine attributes (base_engine.py:171-174).
 With ``SOLVER.EMA.ENABLE`` (off by default; solver/model_ema.py) ``state_dict`` also has ``'ema'``: the
 averaged weights with their update count.  Without it the file is exactly the reference's layout.
+``skipped_steps`` (``SOLVER.NONFINITE_GUARD``; 0 without it) is one more engine attribute: saved and restored with the rest.
 """
 import glob
 import os
@@ -53,6 +54,11 @@ class BaseEngine:
         # data parallelism averages gradients only: every replica starts from rank 0's weights and buffers
         hdist.sync_module_state(self.model)
         self.ema = None         # solver.ModelEMA when SOLVER.EMA.ENABLE (build_solver creates and attaches it)
+        # SOLVER.NONFINITE_GUARD: optimizer steps skipped so far because the gradient norm was not finite (kept in the
+        # checkpoints), how many of them in a row up to now, and how many in a row end the run
+        guard_cfg = cfg.SOLVER.get('NONFINITE_GUARD', None)
+        self.skipped_steps, self.consecutive_skips = 0, 0
+        self.max_consecutive_skips = int(guard_cfg.MAX_CONSECUTIVE) if guard_cfg is not None else 10
         self.optimizer, self.scheduler = self.build_solver() if not is_test else (None, None)
 
         self.root = cfg.OUTPUT_DIR
@@ -143,9 +149,46 @@ class BaseEngine:
     def evaluate(self):
         raise NotImplementedError
 
+    # ------------------------------------------------------------------ non-finite guard
+    def account_steps(self, iters, losses, reports):
+        """The loop's bookkeeping of the steps it has just learned about, one step late: ``iters`` (global iteration numbers),
+        ``losses`` (floats) and ``reports`` (``solver.fused_adamw.GuardRecord``; None: the step was not guarded), in step
+        order.  Returns the losses of the steps that were taken -- a skipped step's loss stays out of the running means.  A
+        skipped step is logged with the name of the first parameter whose gradient held a NaN or an infinity, and the
+        model's floating-point buffers are checked once (a synchronisation, on this rare path only): the forward pass
+        that produced such a gradient has already written the BatchNorm running statistics, and nothing in the optimizer
+        can restore them.  ``max_consecutive_skips`` skipped steps in a row end the run."""
+        taken = []
+        for it, loss, rec in zip(iters, losses, reports):
+            if rec is None or not rec.skipped:
+                taken.append(loss)
+                self.consecutive_skips = 0
+                continue
+            self.skipped_steps += 1
+            self.consecutive_skips += 1
+            name = None
+            if rec.param is not None:
+                name = next((k for k, v in self.model.named_parameters() if v is rec.param), "<not a parameter of the model>")
+            self._say("Iteration %d: optimizer step SKIPPED, gradient norm %s (loss %s); %s. %d step(s) skipped so far."
+                      % (it, rec.norm, loss,
+                         "first non-finite gradient in '%s', %d non-finite element(s) in all" % (name, rec.n_elements)
+                         if name is not None else "every gradient element is finite: the norm overflowed", self.skipped_steps))
+            bad = [k for k, b in self.model.named_buffers() if b.is_floating_point() and not bool(torch.isfinite(b).all())]
+            if bad:
+                raise RuntimeError(
+                    "Iteration %d: the forward pass wrote non-finite values into %d buffer(s) of the model (first: '%s'; BatchNorm "
+                    "running statistics): the skipped optimizer step cannot restore them.  Resume from the last checkpoint in "
+                    "'%s'." % (it, len(bad), bad[0], self.weight_dir))
+            if self.consecutive_skips >= self.max_consecutive_skips:
+                raise RuntimeError(
+                    "Iteration %d: %d optimizer steps in a row were skipped for a non-finite gradient norm "
+                    "(SOLVER.NONFINITE_GUARD.MAX_CONSECUTIVE).  The last checkpoint is in '%s'."
+                    % (it, self.consecutive_skips, self.weight_dir))
+        return taken
+
     # ------------------------------------------------------------------ checkpoints
     _ATTR_EXCEPT = ('cfg', 'writer', 'train_loader', 'test_loader', 'train_dataset', 'test_dataset', 'model', 'optimizer',
-                    'scheduler', 'ema')
+                    'scheduler', 'ema', 'consecutive_skips', 'max_consecutive_skips')
 
     def save_checkpoint(self, post_fix: str = None, save_after_update: bool = True, verbose: bool = True) -> None:
         if not self.is_main:

@@ -9,6 +9,8 @@ the sampler shards the training set so an epoch has 1/N as many steps and the on
 ``total_steps`` shrinks with it; ``SOLVER.OPTIM.LR`` is used exactly as configured -- nothing is scaled
 automatically, scale it in the config if the larger global batch calls for it.  All ranks start from rank 0's
 weights (``hipmonocon.dist.sync_module_state``); rank 0 alone evaluates and writes checkpoints.
+``SOLVER.NONFINITE_GUARD`` needs no collective: every rank steps on the same all-reduced gradients, computes the same norm
+and takes the same decision to skip, so the replicas stay identical and every rank counts the same ``skipped_steps``.
 """
 import os
 from typing import Dict, List
@@ -56,9 +58,13 @@ class MonoconEngine(BaseEngine):
         groups = build_param_groups(self.model.named_parameters(), lr=optim.LR, weight_decay=optim.WEIGHT_DECAY,
                                     backbone_lr_mult=float(optim.get('BACKBONE_LR_MULT', 1.0)),
                                     no_decay_norm_bias=bool(optim.get('NO_DECAY_NORM_BIAS', False)))
+        # SOLVER.NONFINITE_GUARD: the step skips itself on the device when the gradient norm is NaN or infinite
+        # (solver/fused_adamw.py); train_one_epoch learns of it one step late, like the loss
+        guard_cfg = self.cfg.SOLVER.get('NONFINITE_GUARD', None)
         optimizer = AdamW(groups, lr=optim.LR, weight_decay=optim.WEIGHT_DECAY, betas=(0.95, 0.99),
                           max_grad_norm=float(clip.MAX_NORM) if clip.ENABLE else None,
-                          norm_type=float(clip.NORM_TYPE) if clip.ENABLE else 2.0)
+                          norm_type=float(clip.NORM_TYPE) if clip.ENABLE else 2.0,
+                          skip_nonfinite=bool(guard_cfg.ENABLE) if guard_cfg is not None else False)
         # SOLVER.EMA: the optimizer's step keeps an average of the weights and BatchNorm statistics (solver/model_ema.py);
         # evaluate() runs on it and the checkpoints carry it.  Under data parallelism every rank keeps its own: the ranks
         # start from the same weights and apply the same all-reduced gradients, so the averages are identical and nothing
@@ -133,9 +139,17 @@ class MonoconEngine(BaseEngine):
         # the batches arrive on the device one step ahead (copy stream, labels checked on the host) and the loss of a step is
         # read back while the NEXT one runs: nothing between two log lines drains the stream (hipmonocon/feed.py)
         losses = DeferredScalars()
+        guarded = bool(getattr(self.optimizer, 'skip_nonfinite', False))
+        iters = []                  # global iteration numbers of the steps whose loss has not been read yet
 
         def collect(keep):
             got = losses.ready(keep)
+            if guarded:
+                # the guard's reports ride behind the losses, one per step: a skipped step is logged, its loss left out
+                reports = self.optimizer.drain_guard_reports(keep)
+                assert len(reports) == len(got), (len(reports), len(got))
+                got = self.account_steps(iters[:len(got)], got, reports)
+                del iters[:len(reports)]
             epoch_losses.extend(got)
             self.entire_losses.extend(got)
 
@@ -149,6 +163,8 @@ class MonoconEngine(BaseEngine):
             total_loss = reduce_loss_dict(loss_dict)
             total_loss.backward()                       # HIP backward + (N > 1) gradient all-reduce
             losses.push(total_loss)
+            if guarded:
+                iters.append(self.global_iters)
             self.optimizer.step()                       # fused clip (SOLVER.CLIP_GRAD) + AdamW
             if self.scheduler is not None:
                 self.scheduler.step()
@@ -156,8 +172,9 @@ class MonoconEngine(BaseEngine):
             collect(0 if (logging or sync_loop) else 1)
             if logging:
                 bar = progress_to_string_bar(batch_idx + 1, len(self.train_loader), bins=20)
-                recent = sum(self.entire_losses[-100:]) / len(self.entire_losses[-100:])
-                print("| Progress %s | LR %.6f | Loss %8.4f (%8.4f) |" % (bar, self.current_lr, self.entire_losses[-1], recent))
+                last = self.entire_losses[-100:] or [float('nan')]      # (empty: every step so far was skipped)
+                recent = sum(last) / len(last)
+                print("| Progress %s | LR %.6f | Loss %8.4f (%8.4f) |" % (bar, self.current_lr, last[-1], recent))
                 self._update_dict_to_writer(loss_dict, tag='loss')
             self._iter_update()
         collect(0)

@@ -20,7 +20,19 @@ parameter it steps, from the new value while it is in registers (``mc_optim_bind
 ``mc_clip_adamw_ema_step_classes``: 8 B/param more, no further launch), and ``step()`` ends with one
 ``mc_ema_update`` over the rest of the model's state (BatchNorm running statistics, parameters
 without a gradient).  A loop with an attached average does not call ``ema.update`` itself.
+
+``skip_nonfinite=True`` guards the step against a non-finite gradient (torch's fused AdamW has ``found_inf``, ``GradScaler``
+skips the step): when the global norm, as computed, is NaN or infinite, the AdamW pass writes nothing -- parameters, moments,
+``max_exp_avg_sq``, the attached averages and (``mc_ema_update_guarded``) the rest of the average keep every bit -- and
+records which tensor held how many NaN/inf elements.  The decision is taken on the device from the norm that is already
+there: no host round trip, no further launch.  A skipped step still COUNTS: ``state[p]['step']``, ``ModelEMA.updates`` and
+a scheduler advance as for a taken one, because the step counts are folded into the kernel's arguments before the launch
+and the host does not wait to learn the outcome; the report carries the skip, a caller who wants taken steps subtracts.
+Every ``step()`` enqueues a copy of the device record into a page-locked slot behind an event; ``skipped_steps`` and
+``drain_guard_reports(keep=1)`` read them without a synchronisation.  Under data parallelism every rank sees the same
+all-reduced gradients, computes the same norm and takes the same decision: no collective is added.
 """
+import collections
 import ctypes as C
 
 import torch
@@ -80,9 +92,72 @@ def _check_tensor(t, like, what):
         raise _lib.MonoconHipError("fused AdamW: %s must be a contiguous float32 tensor on the parameter's device" % what)
 
 
+GuardRecord = collections.namedtuple("GuardRecord", "step skipped param n_elements norm")
+GuardRecord.__doc__ = """one guarded ``step()``: its 1-based index among this optimizer's ``step()`` calls, whether it was skipped,
+the first bound parameter (table order: groups in order, parameters in order) with a NaN/inf gradient element (None: none --
+a taken step, or a norm that overflowed from finite elements), the number of such elements, the norm as computed"""
+
+
+def _pinned_slot():
+    t = torch.empty(C.sizeof(_lib.GuardReport), dtype=torch.uint8, pin_memory=True)
+    return t, t.data_ptr()
+
+
+def _recorded_event():
+    ev = torch.cuda.Event()
+    ev.record(torch.cuda.current_stream())
+    return ev
+
+
+class GuardReportQueue:
+    """The ``DeferredScalars`` pattern (hipmonocon/feed.py) for ``mc_guard_report`` records: ``push`` enqueues the copy of the
+    handle's device record into a page-locked slot and an event behind it, ``ready(keep)`` returns, in order, the records of
+    all but the ``keep`` newest steps (``keep=0``: all, a synchronisation on the newest), ``skipped`` counts what is known
+    without waiting.  A loop that never reads does not grow the queue: beyond ``max_pending`` entries, the oldest whose event
+    has fired are counted and dropped.  ``alloc`` (-> (owner, address)) and ``event`` (-> an object with ``query`` and
+    ``synchronize``) default to page-locked memory and a recorded ``torch.cuda.Event``."""
+
+    def __init__(self, alloc=None, event=None, max_pending=64):
+        self._alloc, self._event, self.max_pending = alloc or _pinned_slot, event or _recorded_event, int(max_pending)
+        self.pending = collections.deque()      # (step index, bound parameters, slot, event)
+        self._free = []                         # slots of entries that were read
+        self._skipped = 0                       # skipped steps among the entries that have left the queue
+
+    def push(self, lib, handle, stream, step, params):
+        slot = self._free.pop() if self._free else self._alloc()
+        _lib.check(handle, lib.mc_optim_guard_report(handle, C.c_void_p(slot[1]), stream), "mc_optim_guard_report")
+        self.pending.append((step, params, slot, self._event()))
+        while len(self.pending) > self.max_pending and self.pending[0][3].query():
+            self._pop()
+
+    def _read(self, entry):
+        step, params, slot, _ = entry
+        r = _lib.GuardReport.from_address(slot[1])
+        k = int(r.first_tensor)
+        return GuardRecord(step, bool(r.skipped), params[k] if 0 <= k < len(params) else None, int(r.n_elements), float(r.norm))
+
+    def _pop(self):
+        entry = self.pending.popleft()
+        rec = self._read(entry)
+        self._free.append(entry[2])
+        self._skipped += rec.skipped
+        return rec
+
+    def ready(self, keep=1):
+        out = []
+        while len(self.pending) > max(int(keep), 0):
+            self.pending[0][3].synchronize()
+            out.append(self._pop())
+        return out
+
+    @property
+    def skipped(self):
+        return self._skipped + sum(self._read(e).skipped for e in self.pending if e[3].query())
+
+
 class AdamW(Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, maximize=False,
-                 max_grad_norm=None, norm_type=2.0, engine=None):
+                 max_grad_norm=None, norm_type=2.0, engine=None, skip_nonfinite=False):
         if not 0.0 <= lr:
             raise ValueError("Invalid learning rate: %r" % (lr,))
         if not 0.0 <= eps:
@@ -91,6 +166,8 @@ class AdamW(Optimizer):
             raise ValueError("Invalid beta parameters: %r" % (betas,))
         if not 0.0 <= weight_decay:
             raise ValueError("Invalid weight_decay value: %r" % (weight_decay,))
+        if not isinstance(skip_nonfinite, bool):
+            raise TypeError("skip_nonfinite must be a bool, got %r" % (skip_nonfinite,))
         defaults = dict(_torch_defaults())
         defaults.update(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize)
         super().__init__(params, defaults)
@@ -101,10 +178,23 @@ class AdamW(Optimizer):
         self._bound_sig = None
         self._step_cache = None         # (key, host-side copies of the bound tensors' step counts); None: re-read the state
         self.last_grad_norm = None      # device scalar of the most recent pre-clip norm
+        self.skip_nonfinite = skip_nonfinite
+        self._step_calls = 0            # guarded step() calls so far: the step index of the guard's records
+        self._guard_reports = GuardReportQueue() if skip_nonfinite else None
 
     def set_engine(self, engine):
         self._engine = engine
         self._bound_sig = None
+
+    @property
+    def skipped_steps(self):
+        """skipped steps known so far (0 without ``skip_nonfinite``): every report whose copy has landed, no synchronisation"""
+        return self._guard_reports.skipped if self._guard_reports is not None else 0
+
+    def drain_guard_reports(self, keep=1):
+        """``GuardRecord`` s, oldest first, of all guarded steps but the ``keep`` newest -- whose copies may still be in flight;
+        ``keep=0`` returns all and synchronises on the newest.  Each record is returned once."""
+        return self._guard_reports.ready(keep) if self._guard_reports is not None else []
 
     def set_ema(self, ema):
         """Attach (None: detach) a ``solver.ModelEMA``.  From now on ``step()`` performs the average's whole update: the
@@ -232,6 +322,10 @@ class AdamW(Optimizer):
             classes, cls = fold_classes(self.param_groups, list(zip(gis, steps)))
             emas = ema.entries_of(plist) if ema is not None else None
             eng = self._bind(plist, states, ams, cls, emas)
+            guard = self.skip_nonfinite
+            if guard != getattr(eng, '_guard_on', False):       # the handle's switch: moved only when it has to
+                _lib.check(eng.h, eng.lib.mc_optim_set_guard(eng.h, int(guard)), "mc_optim_set_guard")
+                eng._guard_on = guard
         except Exception:
             self._step_cache = None             # nothing was stepped: the state's own counts are the truth again
             raise
@@ -250,7 +344,10 @@ class AdamW(Optimizer):
                 who, w = "mc_clip_adamw_ema_step_classes", ema.weight()
                 rc = eng.lib.mc_clip_adamw_ema_step_classes(eng.h, table, len(classes), max_norm, self.norm_type, w, norm_out,
                                                             stream)
-        _lib.check(eng.h, rc, who)
+            _lib.check(eng.h, rc, who)
+            if guard:                           # the device's verdict on this step, read whenever the caller gets to it
+                self._step_calls += 1
+                self._guard_reports.push(eng.lib, eng.h, stream, self._step_calls, plist)
         # the kernels updated the parameters behind torch's back: advance their version counters
         # (host-only bookkeeping) so autograd and the engine's packed-weight cache see the change
         torch.autograd.graph.increment_version(plist)
@@ -259,18 +356,21 @@ class AdamW(Optimizer):
             if done:
                 torch.autograd.graph.increment_version(done)
             # everything the pass above did not step: buffers, parameters without a gradient; counts the update
-            ema.update_rest(ema.model, w, skip=frozenset(map(id, done)), engine=eng)
+            # (guarded: a no-op on the device after a skipped step, so that the whole average stays where it was)
+            ema.update_rest(ema.model, w, skip=frozenset(map(id, done)), engine=eng, guarded=guard)
         return loss
 
 
 _CLIP_ENGINES = {}
 
 
-def clip_grad_norm_(parameters, max_norm, norm_type=2.0, engine=None):
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, engine=None, error_if_nonfinite=False):
     """``torch.nn.utils.clip_grad_norm_`` for contiguous float32 HIP gradients, as two multi-tensor launches and the
     one-wave final kernel: the total ``norm_type``-norm of all gradients (returned as a device scalar), every gradient
     scaled in place by ``min(1, max_norm / (norm + 1e-6))``.  The gradient table is bound to the engine's handle once
-    and re-bound only when a gradient moved."""
+    and re-bound only when a gradient moved.  ``error_if_nonfinite=True`` is torch's argument: the norm is computed on its
+    own first and read back (a synchronisation, as torch's), and a NaN or infinite one raises torch's ``RuntimeError``
+    before any gradient is scaled."""
     if torch.is_tensor(parameters):
         parameters = [parameters]
     grads = [p.grad for p in parameters if p.grad is not None and p.grad.numel() > 0]
@@ -297,6 +397,16 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0, engine=None):
         eng._clip_sig = sig
     total = torch.zeros((), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
+        if error_if_nonfinite:
+            # max_norm 0: the norm passes alone, no gradient is touched
+            rc = eng.lib.mc_clip_grad_norm(eng.h, 0.0, p_norm, C.c_void_p(total.data_ptr()),
+                                           C.c_void_p(torch.cuda.current_stream().cuda_stream))
+            _lib.check(eng.h, rc, "mc_clip_grad_norm")
+            if not bool(torch.isfinite(total)):
+                raise RuntimeError(
+                    "The total norm of order %s for gradients from `parameters` is non-finite, so it cannot be clipped. To "
+                    "disable this error and scale the gradients by the non-finite norm anyway, set "
+                    "`error_if_nonfinite=False`" % (norm_type,))
         rc = eng.lib.mc_clip_grad_norm(eng.h, float(max_norm), p_norm, C.c_void_p(total.data_ptr()),
                                        C.c_void_p(torch.cuda.current_stream().cuda_stream))
     _lib.check(eng.h, rc, "mc_clip_grad_norm")

@@ -64,9 +64,10 @@ class ModelEMA:
                                        % (", ".join(diff[:4]), ", ..." if len(diff) > 4 else ""))
         return live
 
-    def average(self, pairs, w, engine=None):
+    def average(self, pairs, w, engine=None, guarded=False):
         """``e += w * (src - e)`` for every (e, src) of ``pairs`` in one ``mc_ema_update``; the table is re-bound only when a
-        pointer moved"""
+        pointer moved.  ``guarded`` (the fused AdamW with ``skip_nonfinite``): ``mc_ema_update_guarded``, which does nothing
+        on the device when the handle's last guarded step was skipped"""
         if not pairs:
             return
         dev = pairs[0][0].device
@@ -92,21 +93,24 @@ class ModelEMA:
             _lib.check(eng.h, eng.lib.mc_ema_bind(eng.h, n, E, S, N), "mc_ema_bind")
             self._bound_sig = eng._ema_sig = sig
         with torch.cuda.device(dev):
-            rc = eng.lib.mc_ema_update(eng.h, float(w), C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _lib.check(eng.h, rc, "mc_ema_update")
+            update = eng.lib.mc_ema_update_guarded if guarded else eng.lib.mc_ema_update
+            rc = update(eng.h, float(w), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _lib.check(eng.h, rc, "mc_ema_update_guarded" if guarded else "mc_ema_update")
         torch.autograd.graph.increment_version([e for e, _ in pairs])
 
     @torch.no_grad()
-    def update_rest(self, model, w, skip=(), engine=None):
+    def update_rest(self, model, w, skip=(), engine=None, guarded=False):
         """average every floating-point entry whose average is not in ``skip`` (ids of tensors of ``self.tensors`` that the
-        fused optimizer has just averaged), copy the integer ones, count the update"""
+        fused optimizer has just averaged), copy the integer ones, count the update.  ``guarded``: after a skipped step the
+        floating-point averages keep every bit; the update is counted and the integer entries (counters themselves) are
+        copied all the same -- the host does not wait to learn the outcome"""
         live = self._live(model)
         pairs, copies = [], []
         for k, e in self.tensors.items():
             if id(e) in skip:
                 continue
             (pairs if e.is_floating_point() else copies).append((e, live[k]))
-        self.average(pairs, w, engine)          # (raises before anything is written)
+        self.average(pairs, w, engine, guarded)     # (raises before anything is written)
         for e, s in copies:
             e.copy_(s)
         self.updates += 1
