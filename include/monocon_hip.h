@@ -324,6 +324,32 @@ int mc_clip_adamw_ema_step_classes(mc_handle *h, const mc_optim_class *classes, 
 int mc_ema_bind(mc_handle *h, int n, float *const ema[], const float *const src[], const int64_t numel[]);
 int mc_ema_update(mc_handle *h, double ema_weight, void *stream);
 
+/* Gradient accumulation over a window of micro-batches (every torch loop can call backward() several
+ * times before one optimizer.step(); the reference's loop steps once per batch).  mc_backward WRITES
+ * the "#grad" tensors, so the sum is kept beside them: mc_accum_bind registers n (gradient,
+ * accumulator) pairs -- caller-owned contiguous fp32 device tensors -- in a fourth table, beside the
+ * optimizer's, the clip's and the average's.  mc_grad_accumulate is ONE launch over it, called after
+ * the backward of each micro-batch but the window's only one (a window of 1 needs no call):
+ *   MC_ACCUM_BEGIN   acc = g                                  first micro-batch    (8 B/element)
+ *   MC_ACCUM_ADD     acc = acc + g                            those in between     (12 B/element)
+ *   MC_ACCUM_FINISH  g   = (acc + g) * scale; acc only read   last micro-batch     (12 B/element)
+ * FINISH leaves the window's mean (scale = 1 / micro-batches, folded by the caller in double) in the
+ * gradient tensors themselves: mc_clip_grad_norm, every mc_clip_adamw_* entry, the guard, the fused
+ * average and mc_allreduce_grads then run on it exactly as on one backward's gradients.
+ * Arithmetic, per element: one fp32 round-to-nearest add, then (FINISH) one fp32 round-to-nearest
+ * multiply by (float)scale, never contracted; the bits do not depend on the alignment of either
+ * pointer nor on an element's place in its tensor.  BEGIN and ADD ignore scale.
+ * The handle remembers whether a window is open: mc_accum_bind closes it, BEGIN opens it (BEGIN on an
+ * open window restarts it), ADD and FINISH fail without one, FINISH closes it.
+ * Everything is checked before anything is launched: no table bound; n <= 0, a NULL entry or
+ * numel <= 0; acc[i] overlapping grads[i]; an unknown mode; FINISH with a scale that is NaN, infinite
+ * or <= 0.  Python: solver.GradAccumulator, SOLVER.ACCUM_STEPS. */
+#define MC_ACCUM_BEGIN  0
+#define MC_ACCUM_ADD    1
+#define MC_ACCUM_FINISH 2
+int mc_accum_bind(mc_handle *h, int n, float *const grads[], float *const acc[], const int64_t numel[]);
+int mc_grad_accumulate(mc_handle *h, int mode, double scale, void *stream);
+
 /* Non-finite guard of the fused step (torch's fused AdamW has found_inf, GradScaler skips the step,
  * clip_grad_norm_ has error_if_nonfinite; the reference's loop has none): a step whose global gradient
  * norm, as computed, is NaN or infinite is skipped on the device -- no host round trip, no further

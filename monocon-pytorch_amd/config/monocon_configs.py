@@ -39,6 +39,11 @@ _DEFAULTS = {
         # the gradient norm is NaN or infinite; the loop reports the step one iteration late and gives up after
         # MAX_CONSECUTIVE skipped steps in a row -- solver/fused_adamw.py (skip_nonfinite)
         "NONFINITE_GUARD": {"ENABLE": False, "MAX_CONSECUTIVE": 10},
+        # ACCUM_STEPS (not in the reference's tree; 1 = its loop): N > 1 takes one optimizer step per window of N batches, on the
+        # mean of their gradients (global batch N x BATCH_SIZE on one device; every batch back-propagates its unscaled loss,
+        # BatchNorm statistics stay per batch, an epoch's last len(loader) % N batches step as a window of their own) --
+        # solver/grad_accum.py
+        "ACCUM_STEPS": 1,
     },
     "PERIOD": {"EVAL_PERIOD": 10, "LOG_PERIOD": 50},
 }

@@ -11,6 +11,8 @@
 // The *_guarded kernels (mc_optim_set_guard, off by default) are further instantiations beside those: the step skips
 // itself when the norm is not finite, decided on the device from the norm that is already there.  The unguarded
 // kernels are launched exactly as before while the guard is off.
+// grad_accum_kernel (mc_grad_accumulate) sums the gradients of a window of micro-batches in a table of its own and leaves
+// their mean in the gradient tensors: no kernel above gains an instantiation for it.
 #include <stdint.h>
 #include "conv_mfma.h"
 #include "train.h"
@@ -373,6 +375,68 @@ __global__ __launch_bounds__(256) void grad_scale_kernel(const OptTensor *tab, c
     }
 }
 
+// ---- gradient accumulation over a window of micro-batches (mc_accum_bind: the accumulator in .p, the gradient mc_backward
+// writes in .g).  BEGIN: acc = g (8 B/element).  ADD: acc = acc + g (12 B/element).  FINISH: g = (acc + g) * scale, acc only
+// read (12 B/element): the window's mean lands in the gradient tensors themselves, so the norm, the clip, every AdamW
+// instantiation, the guard and the gradient exchange run on it unchanged.
+// The arithmetic is one fp32 round-to-nearest add and (FINISH) one fp32 round-to-nearest multiply, each an instruction of
+// its own: contraction is switched off for the function (an add feeding a multiply is no fma pattern either way; the ISA of
+// FINISH shows v_add_f32 then v_mul_f32 per element).  Element-wise and the same two operations in the float4
+// body and in the scalar tail, so an element's bits depend neither on who walked it nor on the alignment of acc or g: the
+// body always runs, and a pointer that is not 16-byte aligned is read and written there with four dword accesses (as the
+// EMA pointer of adamw_chunk).
+enum { ACCUM_BEGIN = 0, ACCUM_ADD = 1, ACCUM_FINISH = 2 };      // == MC_ACCUM_*
+
+template <int MODE> __device__ __forceinline__ float accum_one(float a, float g, float scale) {
+#pragma clang fp contract(off)
+    if constexpr (MODE == ACCUM_BEGIN) return g;
+    const float s = a + g;
+    if constexpr (MODE == ACCUM_FINISH) return s * scale;
+    return s;
+}
+
+__device__ __forceinline__ f32x4 load4(const float *p, int i, bool a16) {
+    if (a16) return reinterpret_cast<const f32x4 *>(p)[i];
+    f32x4 v = {p[4 * i], p[4 * i + 1], p[4 * i + 2], p[4 * i + 3]};
+    return v;
+}
+__device__ __forceinline__ void store4(float *p, int i, bool a16, const f32x4 &v) {
+    if (a16) reinterpret_cast<f32x4 *>(p)[i] = v;
+    else { p[4 * i] = v[0]; p[4 * i + 1] = v[1]; p[4 * i + 2] = v[2]; p[4 * i + 3] = v[3]; }
+}
+
+// ALIGNED: acc and g of the chunk are both 16-byte aligned (a uniform choice, made once per chunk): the body is the plain
+// float4 loop of the other passes.  Otherwise the same loop with the misaligned pointer's accesses as dwords.
+template <int MODE, bool ALIGNED>
+__device__ __forceinline__ void accum_chunk(float *a, float *g, int count, float scale, bool a16, bool g16) {
+    float *dst = MODE == ACCUM_FINISH ? g : a;
+    const bool d16 = MODE == ACCUM_FINISH ? g16 : a16;
+    const int n4 = count >> 2;
+    for (int i = threadIdx.x; i < n4; i += 256) {
+        const f32x4 g4 = load4(g, i, ALIGNED || g16);
+        f32x4 a4 = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (MODE != ACCUM_BEGIN) a4 = load4(a, i, ALIGNED || a16);
+        f32x4 r;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) r[j] = accum_one<MODE>(a4[j], g4[j], scale);
+        store4(dst, i, ALIGNED || d16, r);
+    }
+    for (int i = (n4 << 2) + threadIdx.x; i < count; i += 256)
+        dst[i] = accum_one<MODE>(MODE != ACCUM_BEGIN ? a[i] : 0.f, g[i], scale);
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void grad_accum_kernel(const OptTensor *tab, const OptChunk *chunks, int nchunks, float scale) {
+    for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+        const OptChunk ck = chunks[c];
+        const OptTensor t = tab[ck.tensor];
+        float *a = t.p + ck.begin, *g = t.g + ck.begin;
+        const bool a16 = aligned16(a), g16 = aligned16(g);
+        if (a16 && g16) accum_chunk<MODE, true>(a, g, ck.count, scale, true, true);
+        else accum_chunk<MODE, false>(a, g, ck.count, scale, a16, g16);
+    }
+}
+
 constexpr int OPT_BLOCKS = 2048;
 static int opt_blocks(int nchunks) { return nchunks < OPT_BLOCKS ? nchunks : OPT_BLOCKS; }
 
@@ -428,6 +492,15 @@ hipError_t launch_adamw_classes(const OptTensor *tab, const OptChunk *chunks, in
 hipError_t launch_ema(const OptTensor *tab, const OptChunk *chunks, int nchunks, float w, hipStream_t st, const GuardRecord *guard) {
     if (guard) hipLaunchKernelGGL(ema_guarded_kernel, dim3(opt_blocks(nchunks)), dim3(256), 0, st, tab, chunks, nchunks, w, guard);
     else hipLaunchKernelGGL(ema_kernel, dim3(opt_blocks(nchunks)), dim3(256), 0, st, tab, chunks, nchunks, w);
+    return hipGetLastError();
+}
+
+hipError_t launch_grad_accum(const OptTensor *tab, const OptChunk *chunks, int nchunks, int mode, float scale, hipStream_t st) {
+    const int blocks = opt_blocks(nchunks);
+    if (mode == ACCUM_BEGIN) hipLaunchKernelGGL(grad_accum_kernel<ACCUM_BEGIN>, dim3(blocks), dim3(256), 0, st, tab, chunks, nchunks, scale);
+    else if (mode == ACCUM_ADD) hipLaunchKernelGGL(grad_accum_kernel<ACCUM_ADD>, dim3(blocks), dim3(256), 0, st, tab, chunks, nchunks, scale);
+    else if (mode == ACCUM_FINISH) hipLaunchKernelGGL(grad_accum_kernel<ACCUM_FINISH>, dim3(blocks), dim3(256), 0, st, tab, chunks, nchunks, scale);
+    else return hipErrorInvalidValue;            // (the entry point rejects it before this)
     return hipGetLastError();
 }
 

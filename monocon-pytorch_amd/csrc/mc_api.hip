@@ -601,6 +601,8 @@ int mc_destroy(mc_handle *h) {
     if (h->clip_chunks) (void)hipFree(h->clip_chunks);
     if (h->ema_tab) (void)hipFree(h->ema_tab);
     if (h->ema_chunks) (void)hipFree(h->ema_chunks);
+    if (h->accum_tab) (void)hipFree(h->accum_tab);
+    if (h->accum_chunks) (void)hipFree(h->accum_chunks);
     if (h->opt_ws) (void)hipFree(h->opt_ws);
     if (h->opt_guard) (void)hipFree(h->opt_guard);
     delete h;

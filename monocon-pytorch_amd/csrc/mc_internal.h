@@ -283,6 +283,11 @@ struct mc_handle {
     mc::OptTensor *ema_tab = nullptr;
     mc::OptChunk *ema_chunks = nullptr;
     int ema_nchunks = 0;
+    // gradient accumulation (mc_accum_bind): the (accumulator, gradient) table and whether a window is open
+    mc::OptTensor *accum_tab = nullptr;
+    mc::OptChunk *accum_chunks = nullptr;
+    int accum_nchunks = 0;
+    bool accum_open = false;
     // non-finite guard (mc_optim_set_guard): the step entries launch the guarded instantiations while it is on
     mc::GuardRecord *opt_guard = nullptr;   // the last guarded step's record (device)
     bool opt_guard_on = false;

@@ -481,6 +481,41 @@ int mc_ema_update(mc_handle *h, double ema_weight, void *stream) {
     return 0;
 }
 
+// ---- gradient accumulation over a window of micro-batches
+int mc_accum_bind(mc_handle *h, int n, float *const grads[], float *const acc[], const int64_t numel[]) {
+    if (!h) return -1;
+    if (n < 1 || !grads || !acc || !numel) return fail(h, "mc_accum_bind: bad argument");
+    std::vector<mc::OptTensor> tab(n);
+    for (int i = 0; i < n; ++i) {
+        if (!grads[i] || !acc[i] || numel[i] < 1) return fail(h, "mc_accum_bind: tensor %d has a null pointer / empty size", i);
+        if (numel[i] > INT32_MAX) return fail(h, "mc_accum_bind: tensor %d has more than 2^31-1 elements", i);
+        if (ranges_overlap(acc[i], grads[i], numel[i])) return fail(h, "mc_accum_bind: the accumulator of tensor %d aliases its gradient", i);
+        // the table's .p is the accumulator, its .g the gradient
+        tab[i] = mc::OptTensor{acc[i], grads[i], nullptr, nullptr, nullptr, 0};
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    h->accum_open = false;      // a window does not survive its table: ADD / FINISH need a BEGIN on the new one
+    return upload_opt_table(h, tab, numel, &h->accum_tab, &h->accum_chunks, &h->accum_nchunks);
+}
+
+int mc_grad_accumulate(mc_handle *h, int mode, double scale, void *stream) {
+    if (!h) return -1;
+    if (!h->accum_tab) return fail(h, "mc_grad_accumulate: call mc_accum_bind first");
+    if (mode != MC_ACCUM_BEGIN && mode != MC_ACCUM_ADD && mode != MC_ACCUM_FINISH)
+        return fail(h, "mc_grad_accumulate: unknown mode %d (MC_ACCUM_BEGIN, MC_ACCUM_ADD or MC_ACCUM_FINISH)", mode);
+    if (mode != MC_ACCUM_BEGIN && !h->accum_open)
+        return fail(h, "mc_grad_accumulate: %s without an open window (MC_ACCUM_BEGIN first; mc_accum_bind and MC_ACCUM_FINISH close it)",
+                    mode == MC_ACCUM_ADD ? "MC_ACCUM_ADD" : "MC_ACCUM_FINISH");
+    // !(scale > 0) is NaN, zero and negative; a float that overflows or underflows is no mean of a window either
+    if (mode == MC_ACCUM_FINISH && (!(scale > 0.0) || std::isinf(scale) || !((float)scale > 0.f) || std::isinf((float)scale)))
+        return fail(h, "mc_grad_accumulate: MC_ACCUM_FINISH needs a finite scale > 0 (1 / micro-batches of the window), got %g", scale);
+    HIPCHK(h, hipSetDevice(h->device));
+    const float s = mode == MC_ACCUM_FINISH ? (float)scale : 1.f;      // BEGIN and ADD ignore it
+    HIPCHK(h, mc::launch_grad_accum(h->accum_tab, h->accum_chunks, h->accum_nchunks, mode, s, static_cast<hipStream_t>(stream)));
+    h->accum_open = mode != MC_ACCUM_FINISH;
+    return 0;
+}
+
 // ---- non-finite guard
 int mc_optim_set_guard(mc_handle *h, int on) {
     if (!h) return -1;

@@ -175,6 +175,9 @@ hipError_t launch_adamw_classes(const OptTensor *tab, const OptChunk *chunks, in
 // stand-alone weight average e = ema_one(e, src, w) over a table whose .p is e and whose .g is src (mc_ema_bind)
 hipError_t launch_ema(const OptTensor *tab, const OptChunk *chunks, int nchunks, float w, hipStream_t st,
                       const GuardRecord *guard = nullptr);
+// gradient accumulation over a table whose .p is the accumulator and whose .g is the gradient (mc_accum_bind); mode is
+// MC_ACCUM_BEGIN (acc = g), MC_ACCUM_ADD (acc += g) or MC_ACCUM_FINISH (g = (acc + g) * scale): one launch
+hipError_t launch_grad_accum(const OptTensor *tab, const OptChunk *chunks, int nchunks, int mode, float scale, hipStream_t st);
 hipError_t launch_grad_scale(const OptTensor *tab, const OptChunk *chunks, int nchunks, const float *normcoef, hipStream_t st);
 int opt_partial_floats();
 

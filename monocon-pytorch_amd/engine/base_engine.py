@@ -54,6 +54,7 @@ class BaseEngine:
         # data parallelism averages gradients only: every replica starts from rank 0's weights and buffers
         hdist.sync_module_state(self.model)
         self.ema = None         # solver.ModelEMA when SOLVER.EMA.ENABLE (build_solver creates and attaches it)
+        self.grad_accum = None  # solver.GradAccumulator when SOLVER.ACCUM_STEPS > 1 (build_solver creates it)
         # SOLVER.NONFINITE_GUARD: optimizer steps skipped so far because the gradient norm was not finite (kept in the
         # checkpoints), how many of them in a row up to now, and how many in a row end the run
         guard_cfg = cfg.SOLVER.get('NONFINITE_GUARD', None)
@@ -188,7 +189,7 @@ class BaseEngine:
 
     # ------------------------------------------------------------------ checkpoints
     _ATTR_EXCEPT = ('cfg', 'writer', 'train_loader', 'test_loader', 'train_dataset', 'test_dataset', 'model', 'optimizer',
-                    'scheduler', 'ema', 'consecutive_skips', 'max_consecutive_skips')
+                    'scheduler', 'ema', 'grad_accum', 'consecutive_skips', 'max_consecutive_skips')
 
     def save_checkpoint(self, post_fix: str = None, save_after_update: bool = True, verbose: bool = True) -> None:
         if not self.is_main:

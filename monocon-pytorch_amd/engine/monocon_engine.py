@@ -11,6 +11,13 @@ automatically, scale it in the config if the larger global batch calls for it.  
 weights (``hipmonocon.dist.sync_module_state``); rank 0 alone evaluates and writes checkpoints.
 ``SOLVER.NONFINITE_GUARD`` needs no collective: every rank steps on the same all-reduced gradients, computes the same norm
 and takes the same decision to skip, so the replicas stay identical and every rank counts the same ``skipped_steps``.
+
+``SOLVER.ACCUM_STEPS`` N > 1 (default 1: the loop above, call for call): every optimizer step takes a window of N batches of
+the loader -- micro-batches: zero_grad, forward, backward of the UNSCALED loss, one ``mc_grad_accumulate`` launch
+(solver/grad_accum.py) -- and steps on the window's mean gradient; an epoch's last ``len(loader) % N`` batches form a shorter
+window of their own, windows never span epochs.  Iterations, the log period, the schedule, the weight average and the guard's
+reports count optimizer steps; the loss of a step is the mean of its micro-batches' losses.  Under data parallelism the
+gradient exchange is deferred to the window's end: one exchange of the mean per step, not overlapped with a backward.
 """
 import os
 from typing import Dict, List
@@ -21,9 +28,11 @@ from torch.utils.data.distributed import DistributedSampler
 
 from engine.base_engine import BaseEngine
 from model import MonoConDetector
-from solver import AdamW, CyclicScheduler, ModelEMA, build_param_groups
+from solver import AdamW, CyclicScheduler, GradAccumulator, ModelEMA, build_param_groups
+from solver.grad_accum import optimizer_steps_per_epoch
 from utils.decorators import decorator_timer
 from hipmonocon.feed import WORKER_CONTEXT, DeferredScalars, DevicePrefetcher, RingLoader, prepare_worker_context
+from hipmonocon import train as hip_train
 from utils.engine_utils import move_data_device, progress_to_string_bar, reduce_loss_dict, tprint
 
 
@@ -73,9 +82,14 @@ class MonoconEngine(BaseEngine):
         if ema_cfg is not None and ema_cfg.ENABLE:
             self.ema = ModelEMA(self.model, decay=float(ema_cfg.DECAY), warmup=bool(ema_cfg.WARMUP))
             optimizer.set_ema(self.ema)
+        # SOLVER.ACCUM_STEPS: N > 1 accumulates the gradients of N batches per optimizer step (solver/grad_accum.py); with 1
+        # there is no accumulator and the loop is the reference's
+        accum_steps = self.cfg.SOLVER.get('ACCUM_STEPS', 1)
+        self.grad_accum = GradAccumulator(self.model.parameters(), steps=accum_steps) if accum_steps > 1 else None
         scheduler = None
         if self.cfg.SOLVER.SCHEDULER.ENABLE:
-            total_steps = len(self.train_loader) * self.cfg.SOLVER.OPTIM.NUM_EPOCHS
+            # one schedule step per optimizer step: full windows and the epoch's shorter tail window
+            total_steps = optimizer_steps_per_epoch(len(self.train_loader), accum_steps) * self.cfg.SOLVER.OPTIM.NUM_EPOCHS
             scheduler = CyclicScheduler(optimizer, total_steps=total_steps, target_lr_ratio=(10, 1E-04),
                                         target_momentum_ratio=(0.85 / 0.95, 1.0), period_up=0.4)
         return optimizer, scheduler
@@ -156,27 +170,51 @@ class MonoconEngine(BaseEngine):
         # MONOCON_HIP_SYNC_LOOP=1: the reference's loop as written (upload on the compute stream, loss read inside the step)
         sync_loop = os.environ.get("MONOCON_HIP_SYNC_LOOP", "0") == "1"
         feed = self.train_loader if sync_loop else DevicePrefetcher(self.train_loader, self.current_device, self.model)
-        for batch_idx, data_dict in enumerate(feed):
-            self.optimizer.zero_grad()
-            data_dict = move_data_device(data_dict, self.current_device)      # (a no-op for what the prefetcher uploaded)
-            _, loss_dict = self.model(data_dict)
-            total_loss = reduce_loss_dict(loss_dict)
-            total_loss.backward()                       # HIP backward + (N > 1) gradient all-reduce
-            losses.push(total_loss)
-            if guarded:
-                iters.append(self.global_iters)
-            self.optimizer.step()                       # fused clip (SOLVER.CLIP_GRAD) + AdamW
-            if self.scheduler is not None:
-                self.scheduler.step()
-            logging = self.global_iters % self.log_period == 0 and self.is_main
-            collect(0 if (logging or sync_loop) else 1)
-            if logging:
-                bar = progress_to_string_bar(batch_idx + 1, len(self.train_loader), bins=20)
-                last = self.entire_losses[-100:] or [float('nan')]      # (empty: every step so far was skipped)
-                recent = sum(last) / len(last)
-                print("| Progress %s | LR %.6f | Loss %8.4f (%8.4f) |" % (bar, self.current_lr, last[-1], recent))
-                self._update_dict_to_writer(loss_dict, tag='loss')
-            self._iter_update()
+        # SOLVER.ACCUM_STEPS > 1: a window of micro-batches per optimizer step; everything below the `continue` runs once per
+        # window.  The ranks' exchange waits for the window's mean (one exchange per step instead of one per micro-batch)
+        accum = self.grad_accum
+        deferred = accum is not None and self.world > 1
+        if deferred:
+            hip_train.defer_grad_exchange(self.model, True)
+        n_batches = len(self.train_loader)
+        window = []                 # the total losses of the open window's micro-batches (device scalars)
+        try:
+            for batch_idx, data_dict in enumerate(feed):
+                self.optimizer.zero_grad()
+                data_dict = move_data_device(data_dict, self.current_device)      # (a no-op for what the prefetcher uploaded)
+                _, loss_dict = self.model(data_dict)
+                total_loss = reduce_loss_dict(loss_dict)
+                total_loss.backward()                       # HIP backward + (N > 1) gradient all-reduce
+                if accum is not None:
+                    window.append(total_loss.detach())
+                    if not accum.accumulate(last=batch_idx + 1 == n_batches):
+                        continue                            # the window is still open: the next micro-batch
+                    if deferred:
+                        hip_train.exchange_grads_now(self.model)
+                    # the step's loss: the mean over its micro-batches, formed on the device (nothing is read back here)
+                    total_loss = torch.stack(window).mean() if len(window) > 1 else window[0]
+                    window = []
+                losses.push(total_loss)
+                if guarded:
+                    iters.append(self.global_iters)
+                self.optimizer.step()                       # fused clip (SOLVER.CLIP_GRAD) + AdamW
+                if self.scheduler is not None:
+                    self.scheduler.step()
+                logging = self.global_iters % self.log_period == 0 and self.is_main
+                collect(0 if (logging or sync_loop) else 1)
+                if logging:
+                    bar = progress_to_string_bar(batch_idx + 1, len(self.train_loader), bins=20)
+                    last = self.entire_losses[-100:] or [float('nan')]      # (empty: every step so far was skipped)
+                    recent = sum(last) / len(last)
+                    print("| Progress %s | LR %.6f | Loss %8.4f (%8.4f) |" % (bar, self.current_lr, last[-1], recent))
+                    self._update_dict_to_writer(loss_dict, tag='loss')
+                self._iter_update()
+        finally:
+            if deferred:
+                hip_train.defer_grad_exchange(self.model, False)
+        if accum is not None and accum.pending:
+            raise RuntimeError("the train loader delivered fewer than its %d batches: a window of %d micro-batch(es) is still open "
+                               "at the end of the epoch, and windows never span epochs" % (n_batches, accum.pending))
         collect(0)
         self._epoch_update()
         return sum(epoch_losses) / max(len(epoch_losses), 1)

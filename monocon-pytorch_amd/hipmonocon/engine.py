@@ -456,6 +456,31 @@ class Engine:
         self._sig = None          # panels must be re-packed
         self.precision = int(mode)
 
+    # ---- gradient accumulation over a window of micro-batches (csrc/kernels_optim.hip; solver.GradAccumulator drives it)
+    def accum_bind(self, grads, accs):
+        """mc_accum_bind: the (gradient, accumulator) pairs of the window's table -- contiguous float32 tensors of this
+        device, pair by pair of one size; closes an open window"""
+        n = len(grads)
+        if n != len(accs):
+            raise _lib.MonoconHipError("accum_bind: %d gradients for %d accumulators" % (n, len(accs)))
+        for g, a in zip(grads, accs):
+            for t in (g, a):
+                if t.dtype != torch.float32 or not t.is_cuda or t.device != self.device or not t.is_contiguous():
+                    raise _lib.MonoconHipError("accum_bind needs contiguous float32 tensors on the engine's device")
+            if g.numel() != a.numel():
+                raise _lib.MonoconHipError("accum_bind: a gradient and its accumulator differ in size")
+        G = (C.c_void_p * max(n, 1))(*[g.data_ptr() for g in grads])
+        A = (C.c_void_p * max(n, 1))(*[a.data_ptr() for a in accs])
+        N = (C.c_int64 * max(n, 1))(*[g.numel() for g in grads])
+        with torch.cuda.device(self.device):
+            _lib.check(self.h, self.lib.mc_accum_bind(self.h, n, G, A, N), "mc_accum_bind")
+
+    def grad_accumulate(self, mode, scale=1.0):
+        """mc_grad_accumulate: one launch over the bound table on the current stream; ``mode`` is lib.ACCUM_BEGIN (acc = g),
+        lib.ACCUM_ADD (acc += g) or lib.ACCUM_FINISH (g = (acc + g) * scale)"""
+        with torch.cuda.device(self.device):
+            _lib.check(self.h, self.lib.mc_grad_accumulate(self.h, int(mode), float(scale), _stream()), "mc_grad_accumulate")
+
     # ---- data parallelism through the C-ABI (csrc/mc_comm.hip)
     def comm_unique_id(self):
         """rank 0: the 128-byte RCCL id the other ranks need for comm_init (ship it by any host-side channel)"""

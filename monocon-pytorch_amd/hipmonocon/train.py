@@ -115,7 +115,7 @@ class _HipTrainStep(torch.autograd.Function):
         _lib.check(eng.h, eng.lib.mc_train_generation(eng.h, C.byref(gen)), "mc_train_generation")
         ctx.generation = gen.value
         torch.autograd.graph.increment_version(tb.buffers)        # running statistics were updated in place
-        ctx.eng, ctx.tb, ctx.keep = eng, tb, (img, keep, losses)
+        ctx.eng, ctx.tb, ctx.keep, ctx.detector = eng, tb, (img, keep, losses), detector
         # the maps are differentiable outputs, and the backward reads them (loss gradients, activation derivatives):
         # saved as such, an in-place edit of one before backward() raises autograd's version error
         ctx.save_for_backward(*preds)
@@ -157,7 +157,10 @@ class _HipTrainStep(torch.autograd.Function):
         _lib.check(eng.h, rc, what)
         # data parallel: with a communicator owned by the handle mc_backward already exchanged the gradients bucket by
         # bucket, overlapped with the backbone's backward (csrc/mc_comm.hip); otherwise one all-reduce of the flat buffer
-        if eng.comm_world:
+        # (defer_grad_exchange: none of it -- the caller accumulates a window and calls exchange_grads_now once)
+        if getattr(ctx.detector, "_defer_grad_exchange", False):
+            pass
+        elif eng.comm_world:
             if not eng.comm_info()["overlap"]:
                 eng.allreduce_grads()
         else:
@@ -251,6 +254,49 @@ def note_labels_validated(detector, label):
     object.__setattr__(detector, "_mask_validated", (weakref.ref(mask), mask._version))
 
 
+def _hold_overlap(detector, eng):
+    """deferral is on: switch the handle's in-backward exchange off, once, remembering what it was"""
+    if eng is None or not eng.comm_world or getattr(detector, "_deferred_overlap", None) is not None:
+        return
+    was = eng.comm_info()["overlap"]
+    eng.comm_set_overlap(False)
+    object.__setattr__(detector, "_deferred_overlap", (eng, was))
+
+
+def defer_grad_exchange(detector, on):
+    """What DDP's ``no_sync`` does, for a loop that accumulates gradients over a window of micro-batches
+    (``solver.GradAccumulator``): while on, the backward of ``detector`` exchanges nothing -- neither ``mc_allreduce_grads``
+    nor the flat buffer's all-reduce -- and the handle's exchange overlapped with the backward is switched off
+    (``mc_comm_set_overlap(h, 0)``).  Turning it off restores the overlap setting that was found.  The mean over ranks
+    commutes with the sum over micro-batches, so ONE ``exchange_grads_now`` on the window's mean replaces one exchange per
+    micro-batch; it is not overlapped with any backward."""
+    on = bool(on)
+    object.__setattr__(detector, "_defer_grad_exchange", on)
+    if on:
+        _hold_overlap(detector, detector._rt.engine)
+        return
+    held = getattr(detector, "_deferred_overlap", None)
+    if held is not None:
+        object.__setattr__(detector, "_deferred_overlap", None)
+        eng, was = held
+        if eng.comm_world:                  # (the communicator may have been destroyed meanwhile)
+            eng.comm_set_overlap(was)
+
+
+def exchange_grads_now(detector):
+    """the one gradient exchange a backward without overlap performs, on what the gradient buffer holds now:
+    ``mc_allreduce_grads`` when the handle owns a communicator, else the all-reduce of the flat buffer through
+    torch.distributed -- which is nothing outside a distributed run.  For a window accumulated under ``defer_grad_exchange``."""
+    tb = getattr(detector, "_train_binding", None)
+    eng = detector._rt.engine
+    if tb is None or eng is None:
+        raise _lib.MonoconHipError("exchange_grads_now: the detector has not run a train step yet (no gradient buffer is bound)")
+    if eng.comm_world:
+        eng.allreduce_grads()
+    else:
+        tb.flat.allreduce_mean()
+
+
 def forward_train(detector, data_dict):
     img = data_dict["img"]
     if not img.is_cuda:
@@ -266,6 +312,8 @@ def forward_train(detector, data_dict):
     eng = detector._rt.get(tb.state(detector))
     if _dist.is_distributed():
         _dist.setup_engine_dp(eng, img.shape[0], img.shape[2], img.shape[3])      # collective, once per engine (its first step)
+    if getattr(detector, "_defer_grad_exchange", False):
+        _hold_overlap(detector, eng)       # (a communicator that was built just now starts with its overlap on)
     params = [p for _, p in tb.named]
     out = _HipTrainStep.apply(detector, tb, eng, img.contiguous(), label, detector.head.max_objs, *params)
     losses, preds = out[:10], out[10:]

@@ -14,7 +14,8 @@ def main():
     # (a function behind the __main__ guard: the loaders' workers come from a fork server and import this module again)
     ap = argparse.ArgumentParser()
     ap.add_argument('--config_file', type=str, default=None)
-    ap.add_argument('opts', nargs='*', help="KEY VALUE overrides, e.g. DATA.ROOT synthetic DATA.BATCH_SIZE 8")
+    ap.add_argument('opts', nargs='*', help="KEY VALUE overrides, e.g. DATA.ROOT synthetic DATA.BATCH_SIZE 8; SOLVER.ACCUM_STEPS 4 takes one optimizer "
+                                      "step per 4 batches, on the mean of their gradients (global batch 4 x DATA.BATCH_SIZE)")
     args = ap.parse_args()
 
     cfg = load_cfg(args.config_file) if args.config_file else get_default_cfg()
