@@ -324,6 +324,41 @@ int mc_clip_adamw_ema_step_classes(mc_handle *h, const mc_optim_class *classes, 
 int mc_ema_bind(mc_handle *h, int n, float *const ema[], const float *const src[], const int64_t numel[]);
 int mc_ema_update(mc_handle *h, double ema_weight, void *stream);
 
+/* LAMB (You et al. 2019, "Large Batch Optimization for Deep Learning"; timm's Lamb, apex's FusedLAMB; the
+ * reference's loop has none): the Adam update of every tensor rescaled by its trust ratio, so that one learning
+ * rate stays usable across layers of very different scale at a large batch.  Python:
+ * solver.AdamW(trust_ratio=True), SOLVER.LAMB.
+ * mc_clip_lamb_step_classes is mc_clip_adamw_ema_step_classes -- the same bound table (mc_optim_bind_classes,
+ * mc_optim_bind_ema), the same global norm_type-norm, clip coefficient, classes and ema_weight -- with the LAMB
+ * update in place of the AdamW one.  Per bound tensor, with the hyper-parameters of its class and t = its step:
+ *   g' = coef * g                   coef: the clip coefficient, negated for a maximize class
+ *   m  = beta1 m + (1 - beta1) g'
+ *   v  = beta2 v + (1 - beta2) g'^2
+ *   u  = (m / bc1) / (sqrt(v) / sqrt(bc2) + eps) + weight_decay * p       bc1 = 1 - beta1^t, bc2 = 1 - beta2^t
+ *   r  = |p|_2 / |u|_2  if bit c of adapt_mask is set (c the tensor's class) and |p|_2 > 0 and |u|_2 > 0, else 1
+ *        (norms over the whole tensor, p before the update; the comparisons are false for a NaN norm: r = 1,
+ *        and the NaN reaches p through u)
+ *   r  = min(r, trust_clip)         if trust_clip > 0 (0: no cap)
+ *   p  = p - lr * r * u
+ * A class whose bit is clear steps like AdamW up to rounding (the usual exemption of biases and norm weights).
+ * Three launches follow the norm's: the moments with (sum p^2, sum u^2) of every 65536-element chunk left in the
+ * chunk's own slot (24 B/param), one wave per tensor that joins its chunks in double and writes r, and the
+ * apply pass, which forms u again from p, m, v (16 B/param; 24 with the average, updated from the new p in
+ * registers when ema_weight > 0 and an average is attached).  No float atomics and a fixed order at every level
+ * of the sums: the same inputs give the same bits, whatever the alignment of the tensors.
+ * The guard (mc_optim_set_guard, mc_optim_guard_report, mc_ema_update_guarded) applies unchanged: a skipped
+ * step writes nothing to p, m, v, the averages and the ratios.  The workspace is allocated by the first LAMB
+ * step after a bind and freed with the table.
+ * Checked before anything is launched: no table bound; ncls outside 1..MC_OPT_MAX_CLASSES; a class index of
+ * the table >= ncls; step < 1; norm_type <= 0 or NaN; an amsgrad class (not supported); adapt_mask bits at or
+ * above ncls; trust_clip NaN, infinite or negative; ema_weight outside [0, 1].
+ * mc_lamb_ratios enqueues a copy of the last LAMB step's ratios, in table order, into dst: n floats, device or
+ * page-locked host memory.  It fails before any LAMB step on the bound table and when n is not the table's size. */
+int mc_clip_lamb_step_classes(mc_handle *h, const mc_optim_class *classes, int ncls, unsigned adapt_mask,
+                              double trust_clip, double max_norm, double norm_type, double ema_weight,
+                              float *out_norm, void *stream);
+int mc_lamb_ratios(mc_handle *h, float *dst, int n, void *stream);
+
 /* Gradient accumulation over a window of micro-batches (every torch loop can call backward() several
  * times before one optimizer.step(); the reference's loop steps once per batch).  mc_backward WRITES
  * the "#grad" tensors, so the sum is kept beside them: mc_accum_bind registers n (gradient,

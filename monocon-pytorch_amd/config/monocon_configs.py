@@ -44,6 +44,11 @@ _DEFAULTS = {
         # BatchNorm statistics stay per batch, an epoch's last len(loader) % N batches step as a window of their own) --
         # solver/grad_accum.py
         "ACCUM_STEPS": 1,
+        # LAMB (not in the reference's tree; off = its AdamW step): every tensor's update, weight decay included, is rescaled by
+        # its trust ratio |p| / |update| inside the fused step, for batches far larger than the 8 the recipe was tuned at.
+        # TRUST_CLIP > 0 caps the ratio; ALWAYS_ADAPT also adapts groups without weight decay (NO_DECAY_NORM_BIAS).  LR is still
+        # used exactly as configured -- solver/fused_adamw.py (trust_ratio)
+        "LAMB": {"ENABLE": False, "TRUST_CLIP": 0.0, "ALWAYS_ADAPT": False},
     },
     "PERIOD": {"EVAL_PERIOD": 10, "LOG_PERIOD": 50},
 }

@@ -13,6 +13,8 @@
 // kernels are launched exactly as before while the guard is off.
 // grad_accum_kernel (mc_grad_accumulate) sums the gradients of a window of micro-batches in a table of its own and leaves
 // their mean in the gradient tensors: no kernel above gains an instantiation for it.
+// The lamb_* kernels (mc_clip_lamb_step_classes, opt-in) are the layer-wise adaptive step: kernels of their own behind the
+// same global-norm pass; the AdamW, EMA, guard and accumulation kernels keep their code and their launches.
 #include <stdint.h>
 #include "conv_mfma.h"
 #include "train.h"
@@ -437,6 +439,178 @@ __global__ __launch_bounds__(256) void grad_accum_kernel(const OptTensor *tab, c
     }
 }
 
+// ---- LAMB (mc_clip_lamb_step_classes): the Adam update u of every tensor rescaled by its trust ratio r = |p| / |u|.
+// r needs both norms over the WHOLE tensor before one element of p moves, so the step is three launches behind the global
+// norm: lamb_moments_kernel (m, v and each chunk's (sum p^2, sum u^2): 24 B/param), lamb_ratio_kernel (one wave per tensor
+// over its chunks' sums) and lamb_apply_kernel (u again from p, m, v; p -= lr * r * u; the average: 16 or 24 B/param).  u is
+// recomputed, not stored: 40 B/param over the two passes against 48 with a stored u.
+// Determinism: a chunk's sums are left in the chunk's OWN slot, never added across workgroups with atomics, and every level
+// of the sum has a fixed order -- an element's lane follows from its index in the chunk alone (the float4 body always runs;
+// a pointer that is not 16-byte aligned is accessed there as four dwords, as in accum_chunk), then the wave's shuffles, the
+// four LDS partials in order, the chunks of a tensor in double in a fixed lane order.  Every fp32 expression below has its
+// fused operations spelled out (fmaf) and contraction off for the rest, so body and tail give an element the same bits.
+__device__ __forceinline__ void lamb_moments_one(float g, float &m, float &v, float coef, const LambHyper &hp) {
+#pragma clang fp contract(off)
+    g *= coef;
+    m = fmaf(m, hp.beta1, g * hp.one_minus_beta1);
+    v = fmaf(v, hp.beta2, (g * g) * hp.one_minus_beta2);
+}
+// u = (m / bc1) / (sqrt(v) / sqrt(bc2) + eps) + wd * p: the one statement of it, for the norms of pass 1 and the step of pass 3
+__device__ __forceinline__ float lamb_u(float p, float m, float v, const LambHyper &hp) {
+#pragma clang fp contract(off)
+    const float denom = sqrtf(v) / hp.sqrt_bc2 + hp.eps;
+    return fmaf(hp.wd, p, (m / hp.bc1) / denom);
+}
+__device__ __forceinline__ float lamb_sq4(float s, const f32x4 &x) {
+#pragma clang fp contract(off)
+    return s + (((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]) + x[3] * x[3]);
+}
+__device__ __forceinline__ float lamb_sq1(float s, float x) {
+#pragma clang fp contract(off)
+    return s + x * x;
+}
+
+// pass 1 over one chunk: m and v written, (sum p^2, sum u^2) of the lane's elements returned in sp / su
+template <bool ALIGNED>
+__device__ __forceinline__ void lamb_moments_chunk(const OptTensor &t, const OptChunk &ck, float coef, const LambHyper &hp,
+                                                   float &sp, float &su) {
+    const float *p = t.p + ck.begin, *g = t.g + ck.begin;
+    float *m = t.m + ck.begin, *v = t.v + ck.begin;
+    const bool p16 = ALIGNED || aligned16(p), g16 = ALIGNED || aligned16(g), m16 = ALIGNED || aligned16(m), v16 = ALIGNED || aligned16(v);
+    const int n4 = ck.count >> 2;
+    for (int i = threadIdx.x; i < n4; i += 256) {
+        const f32x4 p4 = load4(p, i, p16), g4 = load4(g, i, g16);
+        f32x4 m4 = load4(m, i, m16), v4 = load4(v, i, v16), u4;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float mj = m4[j], vj = v4[j];
+            lamb_moments_one(g4[j], mj, vj, coef, hp);
+            m4[j] = mj; v4[j] = vj;
+            u4[j] = lamb_u(p4[j], mj, vj, hp);
+        }
+        store4(m, i, m16, m4);
+        store4(v, i, v16, v4);
+        sp = lamb_sq4(sp, p4);
+        su = lamb_sq4(su, u4);
+    }
+    for (int i = (n4 << 2) + threadIdx.x; i < ck.count; i += 256) {
+        float mi = m[i], vi = v[i];
+        const float pi = p[i];
+        lamb_moments_one(g[i], mi, vi, coef, hp);
+        m[i] = mi; v[i] = vi;
+        sp = lamb_sq1(sp, pi);
+        su = lamb_sq1(su, lamb_u(pi, mi, vi, hp));
+    }
+}
+
+// GUARD: the step's guard record decides first (set: only the gradients are scanned for the culprit, nothing else is written)
+template <bool GUARD>
+__global__ __launch_bounds__(256) void lamb_moments_kernel(const OptTensor *tab, const OptChunk *chunks, int nchunks,
+                                                           const float *normcoef, LambTable tb, float *chunk_sums /*[nchunks][2]*/,
+                                                           GuardRecord *rec) {
+    if constexpr (GUARD) {
+        if (__builtin_amdgcn_readfirstlane(rec->skipped)) { guard_scan(tab, chunks, nchunks, rec); return; }
+    }
+    __shared__ float red[4][2];
+    const float coef0 = normcoef[1];
+    for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+        const OptChunk ck = chunks[c];
+        const OptTensor t = tab[ck.tensor];
+        const int k = __builtin_amdgcn_readfirstlane(t.cls) & (OPT_MAX_CLASSES - 1);
+        const LambHyper hp = tb.hp[k];
+        const float coef = ((tb.maximize >> k) & 1u) ? -coef0 : coef0;
+        float sp = 0.f, su = 0.f;
+        if (aligned16(t.p + ck.begin) && aligned16(t.g + ck.begin) && aligned16(t.m + ck.begin) && aligned16(t.v + ck.begin))
+            lamb_moments_chunk<true>(t, ck, coef, hp, sp, su);
+        else lamb_moments_chunk<false>(t, ck, coef, hp, sp, su);
+        for (int o = 32; o > 0; o >>= 1) { sp += __shfl_xor(sp, o); su += __shfl_xor(su, o); }
+        if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = sp; red[threadIdx.x >> 6][1] = su; }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            chunk_sums[2 * c] = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
+            chunk_sums[2 * c + 1] = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
+        }
+        __syncthreads();                         // red is written again by the workgroup's next chunk
+    }
+}
+
+// pass 2, one wave per tensor: its chunks' sums (contiguous in the chunk list: first_chunk[t] .. first_chunk[t + 1]) joined
+// in double, both roots in double.  r = |p| / |u| where the tensor's class adapts and both norms are > 0 -- false for a NaN,
+// which then reaches p through u, not through r -- else 1; capped at trust_clip when that is > 0.
+template <bool GUARD>
+__global__ __launch_bounds__(64) void lamb_ratio_kernel(const OptTensor *tab, int ntensors, const int *first_chunk,
+                                                        const float *chunk_sums, unsigned adapt, float trust_clip, float *ratio,
+                                                        const GuardRecord *rec) {
+    if constexpr (GUARD) {
+        if (__builtin_amdgcn_readfirstlane(rec->skipped)) return;
+    }
+    const int t = blockIdx.x;
+    if (t >= ntensors) return;
+    double sp = 0, su = 0;
+    for (int c = first_chunk[t] + threadIdx.x; c < first_chunk[t + 1]; c += 64) {
+        sp += (double)chunk_sums[2 * c];
+        su += (double)chunk_sums[2 * c + 1];
+    }
+    for (int o = 32; o > 0; o >>= 1) { sp += __shfl_xor(sp, o); su += __shfl_xor(su, o); }
+    if (threadIdx.x == 0) {
+        const double pn = sqrt(sp), un = sqrt(su);
+        const int k = tab[t].cls & (OPT_MAX_CLASSES - 1);
+        double r = (((adapt >> k) & 1u) && pn > 0.0 && un > 0.0) ? pn / un : 1.0;
+        if (trust_clip > 0.f && r > (double)trust_clip) r = (double)trust_clip;
+        ratio[t] = (float)r;
+    }
+}
+
+__device__ __forceinline__ float lamb_apply_one(float p, float m, float v, float step, const LambHyper &hp) {
+    return fmaf(-step, lamb_u(p, m, v, hp), p);          // p - (lr * r) * u
+}
+
+// pass 3 over one chunk; EMA: the tensor's average (e, may be null) follows the new p from the same registers
+template <bool ALIGNED, bool EMA>
+__device__ __forceinline__ void lamb_apply_chunk(const OptTensor &t, const OptChunk &ck, float step, const LambHyper &hp, float w) {
+    float *p = t.p + ck.begin;
+    const float *m = t.m + ck.begin, *v = t.v + ck.begin;
+    float *e = (EMA && t.e) ? t.e + ck.begin : nullptr;
+    const bool p16 = ALIGNED || aligned16(p), m16 = ALIGNED || aligned16(m), v16 = ALIGNED || aligned16(v), e16 = aligned16(e);
+    const int n4 = ck.count >> 2;
+    for (int i = threadIdx.x; i < n4; i += 256) {
+        f32x4 p4 = load4(p, i, p16);
+        const f32x4 m4 = load4(m, i, m16), v4 = load4(v, i, v16);
+        f32x4 e4 = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (EMA) { if (e) e4 = load4(e, i, e16); }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            p4[j] = lamb_apply_one(p4[j], m4[j], v4[j], step, hp);
+            if constexpr (EMA) { float ej = e4[j]; ema_one(ej, p4[j], w); e4[j] = ej; }
+        }
+        store4(p, i, p16, p4);
+        if constexpr (EMA) { if (e) store4(e, i, e16, e4); }
+    }
+    for (int i = (n4 << 2) + threadIdx.x; i < ck.count; i += 256) {
+        const float pi = lamb_apply_one(p[i], m[i], v[i], step, hp);
+        p[i] = pi;
+        if constexpr (EMA) { if (e) ema_one(e[i], pi, w); }
+    }
+}
+
+template <bool EMA, bool GUARD>
+__global__ __launch_bounds__(256) void lamb_apply_kernel(const OptTensor *tab, const OptChunk *chunks, int nchunks, LambTable tb,
+                                                         const float *ratio, float w, const GuardRecord *rec) {
+    if constexpr (GUARD) {
+        if (__builtin_amdgcn_readfirstlane(rec->skipped)) return;
+    }
+    for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+        const OptChunk ck = chunks[c];
+        const OptTensor t = tab[ck.tensor];
+        const int k = __builtin_amdgcn_readfirstlane(t.cls) & (OPT_MAX_CLASSES - 1);
+        const LambHyper hp = tb.hp[k];
+        const float step = hp.lr * ratio[ck.tensor];
+        if (aligned16(t.p + ck.begin) && aligned16(t.m + ck.begin) && aligned16(t.v + ck.begin))
+            lamb_apply_chunk<true, EMA>(t, ck, step, hp, w);
+        else lamb_apply_chunk<false, EMA>(t, ck, step, hp, w);
+    }
+}
+
 constexpr int OPT_BLOCKS = 2048;
 static int opt_blocks(int nchunks) { return nchunks < OPT_BLOCKS ? nchunks : OPT_BLOCKS; }
 
@@ -486,6 +660,25 @@ hipError_t launch_adamw_classes(const OptTensor *tab, const OptChunk *chunks, in
         else hipLaunchKernelGGL(adamw_classes_ema_kernel<false>, dim3(blocks), dim3(256), 0, st, tab, chunks, nchunks, normcoef, tb, ema_w);
     } else if (tb.amsgrad) hipLaunchKernelGGL(adamw_classes_kernel<true>, dim3(blocks), dim3(256), 0, st, tab, chunks, nchunks, normcoef, tb);
     else hipLaunchKernelGGL(adamw_classes_kernel<false>, dim3(blocks), dim3(256), 0, st, tab, chunks, nchunks, normcoef, tb);
+    return hipGetLastError();
+}
+
+// the three LAMB passes behind launch_grad_norm; ema_w as in launch_adamw_classes
+template <bool GUARD>
+static void launch_lamb_passes(const OptTensor *tab, const OptChunk *chunks, int nchunks, int ntensors, const float *normcoef,
+                               const LambTable &tb, const LambWorkspace &ws, hipStream_t st, float ema_w, GuardRecord *guard) {
+    const int blocks = opt_blocks(nchunks);
+    hipLaunchKernelGGL(lamb_moments_kernel<GUARD>, dim3(blocks), dim3(256), 0, st, tab, chunks, nchunks, normcoef, tb, ws.chunk_sums, guard);
+    hipLaunchKernelGGL(lamb_ratio_kernel<GUARD>, dim3(ntensors), dim3(64), 0, st, tab, ntensors, ws.first_chunk, ws.chunk_sums, tb.adapt,
+                       tb.trust_clip, ws.ratio, guard);
+    if (ema_w > 0.f) hipLaunchKernelGGL((lamb_apply_kernel<true, GUARD>), dim3(blocks), dim3(256), 0, st, tab, chunks, nchunks, tb, ws.ratio, ema_w, guard);
+    else hipLaunchKernelGGL((lamb_apply_kernel<false, GUARD>), dim3(blocks), dim3(256), 0, st, tab, chunks, nchunks, tb, ws.ratio, 0.f, guard);
+}
+
+hipError_t launch_lamb_classes(const OptTensor *tab, const OptChunk *chunks, int nchunks, int ntensors, const float *normcoef,
+                               const LambTable &tb, const LambWorkspace &ws, hipStream_t st, float ema_w, GuardRecord *guard) {
+    if (guard) launch_lamb_passes<true>(tab, chunks, nchunks, ntensors, normcoef, tb, ws, st, ema_w, guard);
+    else launch_lamb_passes<false>(tab, chunks, nchunks, ntensors, normcoef, tb, ws, st, ema_w, nullptr);
     return hipGetLastError();
 }
 

@@ -605,6 +605,7 @@ int mc_destroy(mc_handle *h) {
     if (h->accum_chunks) (void)hipFree(h->accum_chunks);
     if (h->opt_ws) (void)hipFree(h->opt_ws);
     if (h->opt_guard) (void)hipFree(h->opt_guard);
+    if (h->lamb_ws.chunk_sums) (void)hipFree(h->lamb_ws.chunk_sums);
     delete h;
     return 0;
 }

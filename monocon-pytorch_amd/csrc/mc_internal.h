@@ -292,6 +292,9 @@ struct mc_handle {
     mc::GuardRecord *opt_guard = nullptr;   // the last guarded step's record (device)
     bool opt_guard_on = false;
     bool opt_guard_ran = false; // a guarded step has run since the guard was switched on: the record is a step's
+    // LAMB (mc_clip_lamb_step_classes): one allocation, made by the first LAMB step after a bind and freed with the table
+    mc::LambWorkspace lamb_ws{nullptr, nullptr, nullptr};
+    bool lamb_ran = false;      // a LAMB step has been enqueued on the bound table: lamb_ws.ratio holds a step's ratios
     // train-step plan (mc_train_plan.hip)
     TrainState *train = nullptr;
     size_t train_bytes = 0;   // device memory owned by the train plan

@@ -296,6 +296,9 @@ static int optim_bind(mc_handle *h, const char *who, int n, float *const params[
     }
     h->opt_ntensors = 0;
     h->opt_has_ema = false;     // a new table has no averages: mc_optim_bind_ema attaches them again
+    if (h->lamb_ws.chunk_sums) (void)hipFree(h->lamb_ws.chunk_sums);    // the LAMB workspace goes with the table it was sized for
+    h->lamb_ws = mc::LambWorkspace{nullptr, nullptr, nullptr};
+    h->lamb_ran = false;
     h->opt_host.clear();
     h->opt_numel.clear();
     if (upload_opt_table(h, tab, numel, &h->opt_tab, &h->opt_chunks, &h->opt_nchunks)) return -1;
@@ -427,6 +430,98 @@ int mc_clip_adamw_step_classes(mc_handle *h, const mc_optim_class *classes, int 
 int mc_clip_adamw_ema_step_classes(mc_handle *h, const mc_optim_class *classes, int ncls, double max_norm, double norm_type,
                                    double ema_weight, float *out_norm, void *stream) {
     return step_classes(h, "mc_clip_adamw_ema_step_classes", classes, ncls, max_norm, norm_type, ema_weight, out_norm, stream);
+}
+
+// ---- LAMB: the per-tensor trust ratio on the same table, the same global norm and the same guard
+// chunk sums [2 * nchunks], ratio [n] (1 before the first step), first_chunk [n + 1]: one allocation per bound table
+static int ensure_lamb_ws(mc_handle *h) {
+    if (h->lamb_ws.chunk_sums) return 0;
+    const int n = h->opt_ntensors;
+    const size_t nsums = 2 * (size_t)h->opt_nchunks;
+    std::vector<float> host(nsums + n + n + 1, 0.f);
+    std::fill(host.begin() + nsums, host.begin() + nsums + n, 1.f);
+    int first = 0;      // upload_opt_table lists the chunks tensor by tensor, 65536 elements each
+    for (int i = 0; i <= n; ++i) {
+        std::memcpy(&host[nsums + n + i], &first, sizeof(int));
+        if (i < n) first += (int)((h->opt_numel[i] + 65535) >> 16);
+    }
+    if (first != h->opt_nchunks) return fail(h, "mc_clip_lamb_step_classes: the chunk list does not match the bound sizes");
+    void *q = nullptr;
+    HIPCHK(h, hipMalloc(&q, host.size() * sizeof(float)));
+    const hipError_t e = hipMemcpy(q, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) (void)hipFree(q);
+    HIPCHK(h, e);
+    float *base = static_cast<float *>(q);
+    h->lamb_ws = mc::LambWorkspace{base, base + nsums, reinterpret_cast<int *>(base + nsums + n)};
+    return 0;
+}
+
+int mc_clip_lamb_step_classes(mc_handle *h, const mc_optim_class *classes, int ncls, unsigned adapt_mask, double trust_clip,
+                              double max_norm, double norm_type, double ema_weight, float *out_norm, void *stream) {
+    const char *who = "mc_clip_lamb_step_classes";
+    if (!h) return -1;
+    if (!h->opt_tab || h->opt_ntensors < 1) return fail(h, "%s: call mc_optim_bind_classes first", who);
+    if (!classes || ncls < 1) return fail(h, "%s: bad argument", who);
+    if (ncls > MC_OPT_MAX_CLASSES)
+        return fail(h, "%s: %d hyper-parameter classes (distinct lr / betas / eps / weight_decay / step / maximize / adapts), "
+                       "at most %d fit one launch", who, ncls, MC_OPT_MAX_CLASSES);
+    if (h->opt_max_cls >= ncls)
+        return fail(h, "%s: the bound table uses class index %d but only %d classes were given", who, h->opt_max_cls, ncls);
+    mc::LambTable tb{};
+    for (int c = 0; c < ncls; ++c) {
+        const mc_optim_class &k = classes[c];
+        if (k.step < 1) return fail(h, "%s: class %d: step must be >= 1 (1-based, as torch.optim counts)", who, c);
+        mc::LambHyper &hp = tb.hp[c];
+        hp.beta1 = (float)k.beta1; hp.one_minus_beta1 = (float)(1.0 - k.beta1);
+        hp.beta2 = (float)k.beta2; hp.one_minus_beta2 = (float)(1.0 - k.beta2);
+        hp.sqrt_bc2 = (float)std::sqrt(1.0 - std::pow(k.beta2, (double)k.step));
+        hp.eps = (float)k.eps;
+        hp.bc1 = (float)(1.0 - std::pow(k.beta1, (double)k.step));
+        hp.wd = (float)k.weight_decay;
+        hp.lr = (float)k.lr;
+        if (k.maximize) tb.maximize |= 1u << c;
+    }
+    if (bad_norm_type(norm_type)) return fail(h, "%s: norm_type must be > 0 (inf allowed), got %g", who, norm_type);
+    if (max_norm != max_norm) return fail(h, "%s: max_norm is NaN", who);
+    for (int c = 0; c < ncls; ++c)
+        if (classes[c].amsgrad) return fail(h, "%s: class %d is amsgrad, which the LAMB step does not support", who, c);
+    if (ncls < 32 && (adapt_mask >> ncls)) return fail(h, "%s: adapt_mask 0x%x has bits at or above ncls = %d", who, adapt_mask, ncls);
+    if (!(trust_clip >= 0.0) || std::isinf(trust_clip))
+        return fail(h, "%s: trust_clip must be finite and >= 0 (0: no cap), got %g", who, trust_clip);
+    if (trust_clip > 0.0 && !((float)trust_clip > 0.f && !std::isinf((float)trust_clip)))
+        return fail(h, "%s: trust_clip %g is no positive finite float", who, trust_clip);
+    if (!(ema_weight >= 0.0 && ema_weight <= 1.0)) return fail(h, "%s: ema_weight must lie in [0, 1], got %g", who, ema_weight);
+    tb.adapt = adapt_mask;
+    tb.trust_clip = (float)trust_clip;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (ensure_lamb_ws(h)) return -1;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float *normcoef = h->opt_ws + mc::opt_partial_floats();
+    const float ema_w = h->opt_has_ema ? (float)ema_weight : 0.f;
+    mc::GuardRecord *guard = h->opt_guard_on ? h->opt_guard : nullptr;
+    HIPCHK(h, mc::launch_grad_norm(h->opt_tab, h->opt_chunks, h->opt_nchunks, h->opt_ws, normcoef, (float)max_norm, norm_type, st, guard));
+    HIPCHK(h, mc::launch_lamb_classes(h->opt_tab, h->opt_chunks, h->opt_nchunks, h->opt_ntensors, normcoef, tb, h->lamb_ws, st, ema_w, guard));
+    if (guard) h->opt_guard_ran = true;
+    h->lamb_ran = true;
+    if (out_norm) HIPCHK(h, hipMemcpyAsync(out_norm, normcoef, sizeof(float), hipMemcpyDeviceToDevice, st));
+    h->pack_clean = false;   // parameters changed: the packed panels are stale
+    return 0;
+}
+
+int mc_lamb_ratios(mc_handle *h, float *dst, int n, void *stream) {
+    if (!h) return -1;
+    if (!h->opt_tab || !h->lamb_ran) return fail(h, "mc_lamb_ratios: no mc_clip_lamb_step_classes has run on the bound table");
+    if (!dst) return fail(h, "mc_lamb_ratios: bad argument");
+    if (n != h->opt_ntensors) return fail(h, "mc_lamb_ratios: room for %d ratios, the bound table has %d tensors", n, h->opt_ntensors);
+    HIPCHK(h, hipSetDevice(h->device));
+    // an asynchronous copy needs device or page-locked host memory (as mc_optim_guard_report)
+    hipPointerAttribute_t attr{};
+    const hipError_t e = hipPointerGetAttributes(&attr, dst);
+    if (e != hipSuccess) (void)hipGetLastError();
+    if (e != hipSuccess || (attr.type != hipMemoryTypeDevice && attr.type != hipMemoryTypeHost))
+        return fail(h, "mc_lamb_ratios: dst must be device memory or page-locked host memory");
+    HIPCHK(h, hipMemcpyAsync(dst, h->lamb_ws.ratio, (size_t)n * sizeof(float), hipMemcpyDefault, static_cast<hipStream_t>(stream)));
+    return 0;
 }
 
 int mc_clip_bind(mc_handle *h, int n, float *const grads[], const int64_t numel[]) {

@@ -172,6 +172,17 @@ hipError_t launch_grad_norm(const OptTensor *tab, const OptChunk *chunks, int nc
                             float max_norm, double norm_type, hipStream_t st, GuardRecord *guard = nullptr);
 hipError_t launch_adamw_classes(const OptTensor *tab, const OptChunk *chunks, int nchunks, const float *normcoef,
                                 const AdamTable &tb, hipStream_t st, float ema_w = 0.f, GuardRecord *guard = nullptr);
+// LAMB (mc_clip_lamb_step_classes): one row per class, folded on the host in double and passed by value like AdamTable.
+// Unlike AdamHyper nothing is pre-multiplied into p: u = (m / bc1) / (sqrt(v) / sqrt_bc2 + eps) + wd * p, p -= lr * r * u.
+struct LambHyper { float beta1, one_minus_beta1, beta2, one_minus_beta2, sqrt_bc2, eps, bc1, wd, lr; };
+struct LambTable { LambHyper hp[OPT_MAX_CLASSES]; unsigned maximize, adapt; /* bit c: class c */ float trust_clip; /* 0: no cap */ };
+// device workspace of the LAMB step: (sum p^2, sum u^2) per chunk of the table, the ratio per tensor, and the index of every
+// tensor's first chunk in the chunk list ([ntensors + 1])
+struct LambWorkspace { float *chunk_sums, *ratio; int *first_chunk; };
+// the three passes behind launch_grad_norm: moments + per-chunk norms, per-tensor ratio, apply (+ the average when ema_w > 0)
+hipError_t launch_lamb_classes(const OptTensor *tab, const OptChunk *chunks, int nchunks, int ntensors, const float *normcoef,
+                               const LambTable &tb, const LambWorkspace &ws, hipStream_t st, float ema_w = 0.f,
+                               GuardRecord *guard = nullptr);
 // stand-alone weight average e = ema_one(e, src, w) over a table whose .p is e and whose .g is src (mc_ema_bind)
 hipError_t launch_ema(const OptTensor *tab, const OptChunk *chunks, int nchunks, float w, hipStream_t st,
                       const GuardRecord *guard = nullptr);

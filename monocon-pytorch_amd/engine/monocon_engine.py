@@ -11,6 +11,9 @@ automatically, scale it in the config if the larger global batch calls for it.  
 weights (``hipmonocon.dist.sync_module_state``); rank 0 alone evaluates and writes checkpoints.
 ``SOLVER.NONFINITE_GUARD`` needs no collective: every rank steps on the same all-reduced gradients, computes the same norm
 and takes the same decision to skip, so the replicas stay identical and every rank counts the same ``skipped_steps``.
+``SOLVER.LAMB`` (off by default) makes the fused step LAMB: every tensor's update is rescaled by its trust ratio (solver/fused_adamw.py),
+and the log line gains the min / median / max ratio of the step.  It adds no collective either -- the ranks form the same ratios from
+the same parameters and gradients -- and it changes nothing about ``LR``: that is still used exactly as configured.
 
 ``SOLVER.ACCUM_STEPS`` N > 1 (default 1: the loop above, call for call): every optimizer step takes a window of N batches of
 the loader -- micro-batches: zero_grad, forward, backward of the UNSCALED loss, one ``mc_grad_accumulate`` launch
@@ -70,10 +73,14 @@ class MonoconEngine(BaseEngine):
         # SOLVER.NONFINITE_GUARD: the step skips itself on the device when the gradient norm is NaN or infinite
         # (solver/fused_adamw.py); train_one_epoch learns of it one step late, like the loss
         guard_cfg = self.cfg.SOLVER.get('NONFINITE_GUARD', None)
+        # SOLVER.LAMB: the per-tensor trust ratio in the fused step (solver/fused_adamw.py); LR stays as configured
+        lamb_cfg = self.cfg.SOLVER.get('LAMB', None)
+        lamb = dict(trust_ratio=True, trust_clip=float(lamb_cfg.TRUST_CLIP), always_adapt=bool(lamb_cfg.ALWAYS_ADAPT)) \
+            if lamb_cfg is not None and lamb_cfg.ENABLE else {}
         optimizer = AdamW(groups, lr=optim.LR, weight_decay=optim.WEIGHT_DECAY, betas=(0.95, 0.99),
                           max_grad_norm=float(clip.MAX_NORM) if clip.ENABLE else None,
                           norm_type=float(clip.NORM_TYPE) if clip.ENABLE else 2.0,
-                          skip_nonfinite=bool(guard_cfg.ENABLE) if guard_cfg is not None else False)
+                          skip_nonfinite=bool(guard_cfg.ENABLE) if guard_cfg is not None else False, **lamb)
         # SOLVER.EMA: the optimizer's step keeps an average of the weights and BatchNorm statistics (solver/model_ema.py);
         # evaluate() runs on it and the checkpoints carry it.  Under data parallelism every rank keeps its own: the ranks
         # start from the same weights and apply the same all-reduced gradients, so the averages are identical and nothing
@@ -154,6 +161,7 @@ class MonoconEngine(BaseEngine):
         # read back while the NEXT one runs: nothing between two log lines drains the stream (hipmonocon/feed.py)
         losses = DeferredScalars()
         guarded = bool(getattr(self.optimizer, 'skip_nonfinite', False))
+        lamb = bool(getattr(self.optimizer, 'trust_ratio', False))
         iters = []                  # global iteration numbers of the steps whose loss has not been read yet
 
         def collect(keep):
@@ -207,6 +215,10 @@ class MonoconEngine(BaseEngine):
                     last = self.entire_losses[-100:] or [float('nan')]      # (empty: every step so far was skipped)
                     recent = sum(last) / len(last)
                     print("| Progress %s | LR %.6f | Loss %8.4f (%8.4f) |" % (bar, self.current_lr, last[-1], recent))
+                    if lamb:                                # SOLVER.LAMB: the adapting tensors' ratios of this step
+                        r = sorted(self.optimizer.trust_ratios(adapting_only=True).values())
+                        if r:
+                            print("| Trust ratio | min %.4g | median %.4g | max %.4g |" % (r[0], r[len(r) // 2], r[-1]))
                     self._update_dict_to_writer(loss_dict, tag='loss')
                 self._iter_update()
         finally:

@@ -14,7 +14,7 @@ NUM_PREDS = 10
 
 EXPORTS = (
     "mc_create", "mc_destroy", "mc_last_error", "mc_version", "mc_bind_params", "mc_pack_params",
-    "mc_forward_infer", "mc_backbone_forward", "mc_neck_forward", "mc_head_forward", "mc_decode", "mc_make_targets", "mc_losses", "mc_losses_backward", "mc_losses_backward_pred", "mc_forward_train", "mc_backward", "mc_backward_pred_grads", "mc_backward_image_grad", "mc_train_generation", "mc_head_forward_train", "mc_head_backward", "mc_head_backward_pred_grads", "mc_train_debug_node", "mc_infer_debug_node", "mc_optim_bind", "mc_clip_adamw_step", "mc_optim_bind_classes", "mc_clip_adamw_step_classes", "mc_clip_bind", "mc_clip_grad_norm", "mc_optim_bind_ema", "mc_clip_adamw_ema_step_classes", "mc_ema_bind", "mc_ema_update", "mc_optim_set_guard", "mc_optim_guard_report", "mc_ema_update_guarded", "mc_accum_bind", "mc_grad_accumulate", "mc_op_conv", "mc_op_conv_wgrad", "mc_op_conv_dgrad", "mc_op_stem", "mc_op_stem_dgrad", "mc_op_stem_dgrad_fused", "mc_op_maxpool2", "mc_op_deconv4x4",
+    "mc_forward_infer", "mc_backbone_forward", "mc_neck_forward", "mc_head_forward", "mc_decode", "mc_make_targets", "mc_losses", "mc_losses_backward", "mc_losses_backward_pred", "mc_forward_train", "mc_backward", "mc_backward_pred_grads", "mc_backward_image_grad", "mc_train_generation", "mc_head_forward_train", "mc_head_backward", "mc_head_backward_pred_grads", "mc_train_debug_node", "mc_infer_debug_node", "mc_optim_bind", "mc_clip_adamw_step", "mc_optim_bind_classes", "mc_clip_adamw_step_classes", "mc_clip_bind", "mc_clip_grad_norm", "mc_optim_bind_ema", "mc_clip_adamw_ema_step_classes", "mc_ema_bind", "mc_ema_update", "mc_optim_set_guard", "mc_optim_guard_report", "mc_ema_update_guarded", "mc_accum_bind", "mc_grad_accumulate", "mc_clip_lamb_step_classes", "mc_lamb_ratios", "mc_op_conv", "mc_op_conv_wgrad", "mc_op_conv_dgrad", "mc_op_stem", "mc_op_stem_dgrad", "mc_op_stem_dgrad_fused", "mc_op_maxpool2", "mc_op_deconv4x4",
     "mc_op_nchw_to_nhwc", "mc_op_nhwc_to_nchw", "mc_workspace_bytes", "mc_query_workspace", "mc_forward_cost",
     "mc_preprocess", "mc_preprocess_augmented", "mc_profile_forward", "mc_profile_train", "mc_set_precision", "mc_set_local_maximum_kernel", "mc_set_conv_cfg", "mc_bench_conv", "mc_bench_mfma_peak",
     "mc_comm_unique_id", "mc_comm_init", "mc_comm_destroy", "mc_comm_set_overlap", "mc_comm_info", "mc_comm_exposed_ms", "mc_allreduce_grads",
@@ -123,6 +123,8 @@ def load():
     lib.mc_ema_update_guarded.argtypes = [vp, d, vp]
     lib.mc_accum_bind.argtypes = [vp, i, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int64)]
     lib.mc_grad_accumulate.argtypes = [vp, i, d, vp]
+    lib.mc_clip_lamb_step_classes.argtypes = [vp, C.POINTER(OptimClass), i, C.c_uint, d, d, d, d, vp, vp]
+    lib.mc_lamb_ratios.argtypes = [vp, vp, i, vp]
     lib.mc_op_conv.argtypes = [vp, C.POINTER(vp), C.POINTER(i), i, i, i, i, vp, i, i, i, vp, vp, vp, i, vp, vp]
     lib.mc_op_conv_wgrad.argtypes = [vp, C.POINTER(vp), C.POINTER(i), i, i, i, i, vp, i, i, i, vp, vp]
     lib.mc_op_stem.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp, vp]

@@ -31,6 +31,18 @@ and the host does not wait to learn the outcome; the report carries the skip, a 
 Every ``step()`` enqueues a copy of the device record into a page-locked slot behind an event; ``skipped_steps`` and
 ``drain_guard_reports(keep=1)`` read them without a synchronisation.  Under data parallelism every rank sees the same
 all-reduced gradients, computes the same norm and takes the same decision: no collective is added.
+
+``trust_ratio=True`` turns the step into LAMB (You et al. 2019; timm's ``Lamb``, apex's ``FusedLAMB``): the Adam update ``u`` of
+every tensor -- weight decay included -- is rescaled by the tensor's trust ratio ``r = |p| / |u|`` before it is applied,
+``p -= lr * r * u`` (``mc_clip_lamb_step_classes``, the formula in include/monocon_hip.h: three launches behind the global norm
+instead of AdamW's one, 40 B/param instead of 16).  A group adapts when its ``trust_ratio`` is on (the constructor's value, or
+the group's own key) and it has ``weight_decay > 0`` or ``always_adapt`` is set -- timm's convention, which leaves the biases
+and norm weights of a no-decay group at ``r = 1``, AdamW up to rounding.  ``trust_clip > 0`` caps ``r``.  The state is AdamW's
+(``step``, ``exp_avg``, ``exp_avg_sq``), so checkpoints move freely between the two modes; ``load_state_dict`` keeps this
+optimizer's own ``trust_ratio`` settings.  ``amsgrad`` is not supported with it.  ``trust_ratios()`` reads the last step's
+ratios for logging.  ``set_ema``, ``skip_nonfinite``, ``GradAccumulator`` and data parallelism work as before: every rank steps
+on the same all-reduced gradients and forms the same norms and ratios from the same parameters, so no collective is added.
+With every ``trust_ratio`` off, ``step()`` is the AdamW path above, call for call.
 """
 import collections
 import ctypes as C
@@ -85,6 +97,33 @@ def fold_classes(param_groups, pairs):
                     % MAX_CLASSES)
         index[pair] = k
     return classes, tuple(map(index.__getitem__, pairs))
+
+
+def fold_lamb_classes(param_groups, pairs, adapts):
+    """``fold_classes`` for a LAMB step: ``adapts[gi]`` tells whether group ``gi`` uses the trust ratio, and two pairs are one
+    class when ``class_key(...) + (adapts,)`` agree.  Returns (classes, cls, adapt_mask): the ``class_key`` tuples in order of
+    first appearance, each tensor's index into them, and bit c set when class c adapts."""
+    index, classes, by_key, mask = {}, [], {}, 0
+    for pair in dict.fromkeys(pairs):
+        key = class_key(param_groups[pair[0]], pair[1]) + (bool(adapts[pair[0]]),)
+        k = by_key.get(key)
+        if k is None:
+            k = by_key[key] = len(classes)
+            classes.append(key[:-1])
+            if k >= MAX_CLASSES:
+                raise _lib.MonoconHipError(
+                    "fused LAMB: this step needs more than %d hyper-parameter classes (distinct lr / betas / eps / weight_decay "
+                    "/ maximize / adapting of the groups times distinct step counts of their parameters)" % MAX_CLASSES)
+            mask |= int(key[-1]) << k
+        index[pair] = k
+    return classes, tuple(map(index.__getitem__, pairs)), mask
+
+
+def check_trust_clip(trust_clip):
+    c = float(trust_clip)
+    if not 0.0 <= c < float("inf"):                  # negative, NaN and inf
+        raise ValueError("trust_clip must be finite and >= 0 (0: no cap), got %r" % (trust_clip,))
+    return c
 
 
 def _check_tensor(t, like, what):
@@ -157,7 +196,8 @@ class GuardReportQueue:
 
 class AdamW(Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, maximize=False,
-                 max_grad_norm=None, norm_type=2.0, engine=None, skip_nonfinite=False):
+                 max_grad_norm=None, norm_type=2.0, engine=None, skip_nonfinite=False, trust_ratio=False, trust_clip=0.0,
+                 always_adapt=False):
         if not 0.0 <= lr:
             raise ValueError("Invalid learning rate: %r" % (lr,))
         if not 0.0 <= eps:
@@ -170,6 +210,12 @@ class AdamW(Optimizer):
             raise TypeError("skip_nonfinite must be a bool, got %r" % (skip_nonfinite,))
         defaults = dict(_torch_defaults())
         defaults.update(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize)
+        # LAMB.  trust_ratio is no entry of `defaults`: the groups keep torch.optim.AdamW's keys, a group that sets its own
+        # 'trust_ratio' carries that one key more.  (Set before the groups are added: add_param_group checks against them.)
+        self.trust_ratio = bool(trust_ratio)
+        self.trust_clip = check_trust_clip(trust_clip)
+        self.always_adapt = bool(always_adapt)
+        self._ratio_params = None       # the bound parameters of the last LAMB step (trust_ratios)
         super().__init__(params, defaults)
         self.max_grad_norm = max_grad_norm
         self.norm_type = check_norm_type(norm_type)
@@ -207,7 +253,13 @@ class AdamW(Optimizer):
         """Restores the moments and the per-parameter ``step`` (torch.optim.AdamW's checkpoint layout, which
         is what the reference saves, engine/base_engine.py:155-219).  The kernels hold raw pointers to the moment
         tensors, which torch replaces here: the binding is dropped and rebuilt on the next step()."""
+        own = [g.get('trust_ratio') for g in self.param_groups]
         super().load_state_dict(state_dict)
+        # LAMB or not is this optimizer's choice, not the file's: the state is the same in both modes
+        for g, t in zip(self.param_groups, own):
+            g.pop('trust_ratio', None)
+            if t is not None:
+                g['trust_ratio'] = t
         self._bound_sig = None
         self._step_cache = None
         # torch hands the caller's own 'step' (and same-device moment) tensors through uncopied; step() updates
@@ -226,9 +278,39 @@ class AdamW(Optimizer):
         self._step_cache = None
 
     def add_param_group(self, param_group):
+        # one launch steps every group, and the LAMB step has no amsgrad form: no amsgrad group beside a trust_ratio one
+        if isinstance(param_group, dict):
+            flags = [(bool(g.get('amsgrad', self.defaults['amsgrad'])), bool(g.get('trust_ratio', self.trust_ratio)))
+                     for g in self.param_groups + [param_group]]
+            if any(a for a, _ in flags) and any(t for _, t in flags):
+                raise ValueError("amsgrad is not supported together with trust_ratio (LAMB)")
         super().add_param_group(param_group)
         self._bound_sig = None
         self._step_cache = None
+
+    def _adapts(self):
+        """per group: does it use the trust ratio (None: no group has ``trust_ratio`` on -- the AdamW path)"""
+        on = [bool(g.get('trust_ratio', self.trust_ratio)) for g in self.param_groups]
+        if not any(on):
+            return None
+        return [t and (float(g['weight_decay']) > 0.0 or self.always_adapt) for g, t in zip(self.param_groups, on)]
+
+    def trust_ratios(self, adapting_only=False):
+        """``{parameter: trust ratio}`` of the last LAMB ``step()`` (1.0 where the group does not adapt; ``adapting_only``
+        leaves those out): one copy of n floats and a synchronisation, only when called -- for logging.  After a step the
+        guard skipped: the ratios of the step before."""
+        if self._ratio_params is None:
+            raise _lib.MonoconHipError("trust_ratios: no step() with trust_ratio on has run")
+        plist, eng = self._ratio_params, self._engine
+        out = torch.empty(len(plist), dtype=torch.float32, device=plist[0].device)
+        with torch.cuda.device(plist[0].device):
+            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            _lib.check(eng.h, eng.lib.mc_lamb_ratios(eng.h, C.c_void_p(out.data_ptr()), len(plist), stream), "mc_lamb_ratios")
+        ratios = dict(zip(plist, out.cpu().tolist()))
+        if adapting_only:
+            keep = {p for g, a in zip(self.param_groups, self._adapts() or ()) if a for p in g['params']}
+            ratios = {p: r for p, r in ratios.items() if p in keep}
+        return ratios
 
     def zero_state(self):
         """forget the moments and step counts (a fresh optimizer over the same parameters)"""
@@ -318,8 +400,14 @@ class AdamW(Optimizer):
         for i in range(len(steps)):
             steps[i] += 1
         ema = self._ema
+        adapts = self._adapts()                 # None: AdamW
         try:
-            classes, cls = fold_classes(self.param_groups, list(zip(gis, steps)))
+            if adapts is None:
+                classes, cls = fold_classes(self.param_groups, list(zip(gis, steps)))
+            else:
+                if any(ams):
+                    raise ValueError("amsgrad is not supported together with trust_ratio (LAMB)")
+                classes, cls, adapt_mask = fold_lamb_classes(self.param_groups, list(zip(gis, steps)), adapts)
             emas = ema.entries_of(plist) if ema is not None else None
             eng = self._bind(plist, states, ams, cls, emas)
             guard = self.skip_nonfinite
@@ -337,15 +425,22 @@ class AdamW(Optimizer):
         norm_out = C.c_void_p(self.last_grad_norm.data_ptr())
         with torch.cuda.device(plist[0].device):
             stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)     # (the parameters' device's current stream)
-            if ema is None:
+            w = ema.weight() if ema is not None else 0.0
+            if adapts is not None:
+                who = "mc_clip_lamb_step_classes"
+                rc = eng.lib.mc_clip_lamb_step_classes(eng.h, table, len(classes), adapt_mask, self.trust_clip, max_norm,
+                                                       self.norm_type, w, norm_out, stream)
+            elif ema is None:
                 who = "mc_clip_adamw_step_classes"
                 rc = eng.lib.mc_clip_adamw_step_classes(eng.h, table, len(classes), max_norm, self.norm_type, norm_out, stream)
             else:
-                who, w = "mc_clip_adamw_ema_step_classes", ema.weight()
+                who = "mc_clip_adamw_ema_step_classes"
                 rc = eng.lib.mc_clip_adamw_ema_step_classes(eng.h, table, len(classes), max_norm, self.norm_type, w, norm_out,
                                                             stream)
             _lib.check(eng.h, rc, who)
-            if guard:                           # the device's verdict on this step, read whenever the caller gets to it
+            if adapts is not None:
+                self._ratio_params = plist      # the table mc_lamb_ratios reads
+            if guard:                          # the device's verdict on this step, read whenever the caller gets to it
                 self._step_calls += 1
                 self._guard_reports.push(eng.lib, eng.h, stream, self._step_calls, plist)
         # the kernels updated the parameters behind torch's back: advance their version counters
